@@ -11,10 +11,18 @@ N > 1: launched by torch.distributed.run, one rank per GPU; face layers are exch
 every step on a halo stream that overlaps the interior sweep (sailfish_amd/slab.py).  --force_distributed takes the
 same path with a single rank (the slab is its own ring neighbour; RCCL send / recv to self).
 
-Prints ONE JSON line on rank 0 (field list: DESIGN.md §6).  `value` is the MEDIAN of the timed blocks of exactly K
-steps (each bracketed by barrier + synchronize, max over ranks; blocks are repeated until --min_seconds are timed, for
---repeats fresh placements); `best_value` is the fastest block (what rounds 3-4 reported as `value`: not directly
-comparable), every block is in `config`.
+Prints ONE JSON line on rank 0 (field list: DESIGN.md §6).  A plain run does only what the headline needs: set-up
+(placement by measurement included), warm-up, ONE timed block of exactly K steps of one access pattern (bracketed by
+barrier + synchronize, max over ranks), the --dump-outputs files, the line.
+
+--full adds everything else the line used to carry: both access patterns (`auto`), blocks repeated until --min_seconds
+are timed for --repeats fresh placements (`value` = the MEDIAN block, `best_value` the fastest), the check of the final
+state against the CPU oracle, the runner-path leg, the CPU baseline, the sweep-only and halo-timing legs of N > 1 runs
+and the GPU state before / after.
+
+--dump-outputs DIR: after the timed steps, a fixed seeded sample of the populations the last timed step left behind
+(what SlabSim.get_dist() returns) as DIR/dist.npy (DIR/dist_rank<r>.npy for N > 1), at most 48 MB in all; the
+initial state is seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -44,9 +52,15 @@ def parse_args():
     ap.add_argument('--axis', default='z', choices=['x', 'y', 'z'], help='axis the box is cut along')
     ap.add_argument('--force_distributed', action='store_true',
                     help='one rank, but through the halo path (pack, RCCL send / recv to self, unpack)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: both access patterns, repeated blocks, validation against the '
+                         'oracle, runner path, CPU baseline, halo timing, GPU state (see the module docstring)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='write a fixed seeded sample of the state the last timed step left behind as DIR/<name>.npy')
     ap.add_argument('--access_pattern', default='auto', choices=['auto', 'AA', 'AB'],
-                    help='AA = in-place single copy, AB = two copies (the reference default); auto times both '
-                         'with the same K steps and reports the faster one')
+                    help='AA = in-place single copy, AB = two copies (the reference default); auto: with --full both are '
+                         'timed with the same K steps and the faster one is reported, a plain run times AB (the faster of '
+                         'the two in most recorded --full runs, by under 1 %%)')
     ap.add_argument('--model', default='bgk', choices=['bgk', 'mrt'])
     ap.add_argument('--precision', default='single', choices=['single', 'double'])
     ap.add_argument('--no_fused_periodic', action='store_true',
@@ -55,7 +69,7 @@ def parse_args():
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--cpu_seconds', type=float, default=10.0)
     ap.add_argument('--repeats', type=int, default=2,
-                    help='each candidate access pattern is timed this many times (K steps each)')
+                    help='--full: each candidate access pattern is timed this many times (K steps each)')
     ap.add_argument('--no_placement_tune', action='store_true',
                     help='place the distribution arrays once instead of by measurement (sailfish_amd/placement.py choose())')
     ap.add_argument('--prewarm_steps', type=int, default=300,
@@ -64,13 +78,16 @@ def parse_args():
     ap.add_argument('--no_runner_path', action='store_true',
                     help='skip the leg through LBSimulationController / SubdomainRunner.step() (N = 1 only)')
     ap.add_argument('--min_seconds', type=float, default=0.5,
-                    help='the block of exactly K timed steps is repeated until at least this much time has been timed '
+                    help='--full: the block of exactly K timed steps is repeated until at least this much time has been timed '
                          '(every block bracketed by barrier + synchronize; median block = value, the best one is reported too)')
     ap.add_argument('--halo_timing_steps', type=int, default=20,
-                    help='N > 1: steps of the separate leg that brackets the halo stream with timing events')
+                    help='--full, N > 1: steps of the separate leg that brackets the halo stream with timing events')
     ap.add_argument('--no_validate', action='store_true',
                     help='skip the check of the final state against the CPU oracle after the timed region')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def gpu_state():
@@ -123,6 +140,33 @@ def median_block(blocks):
     """Index of the median timed block (the lower of the two middle ones for an even count: always a block that ran)."""
     order = np.argsort(np.asarray(blocks, dtype=np.float64), kind='stable')
     return int(order[(len(order) - 1) // 2])
+
+
+def sample_state(sim, budget_bytes, seed=20240601):
+    """The populations the last step left behind, as a caller of the slab driver receives them (SlabSim.get_dist(): the
+    current copy, [Q, z, y, x], the in-place layout for AA), sampled so that the whole fits in `budget_bytes`: up to 32
+    z-planes of the real box and the same count of nodes in each, both drawn with a fixed seed.  Only those planes are
+    read from the device.  Returns a [Q, planes * nodes] array of the simulation's dtype."""
+    d = sim.desc
+    nx, ny, nz = d.lat_nx - 2, d.lat_ny - 2, d.lat_nz - 2
+    isz = sim.dtype().itemsize
+    rng = np.random.RandomState(seed)
+    planes = np.sort(rng.choice(nz, min(nz, 32), replace=False)) + 1
+    per_plane = max(1, min(nx * ny, budget_bytes // (sim.Q * isz * len(planes))))
+    cells = np.sort(rng.choice(nx * ny, per_plane, replace=False))
+    idx = (cells // nx + 1) * d.arr_nx + cells % nx + 1       # real node (x, y) -> index in an [arr_ny, arr_nx] plane
+    if sim.halo:
+        sim.materialise_faces()
+    sim.sync()
+    nxy = d.arr_nx * d.arr_ny
+    base = sim.gpu_dist[sim.current_dist_index()]
+    plane = np.empty(nxy, dtype=sim.dtype)
+    out = np.empty((sim.Q, len(planes), per_plane), dtype=sim.dtype)
+    for q in range(sim.Q):
+        for k, z in enumerate(planes):
+            sim.backend.from_buf(base + (q * sim.stride + int(z) * nxy) * isz, plane)
+            out[q, k] = plane[idx]
+    return out.reshape(sim.Q, -1)
 
 
 def rccl_ranks_of(exchanger, dist_backend, world, peer=None):
@@ -398,6 +442,8 @@ def main():
     wd.close()
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs: the sample of all ranks together
+
 WATCH_DETAIL = None      # set by run(): what the watchdog adds to a rank's state (transport counters)
 
 
@@ -473,7 +519,7 @@ def run(args, world, rank, wd):
         if distributed:
             torch.distributed.barrier()
 
-    def measure(pattern, check=False):
+    def measure(pattern, check=False, last=False):
         wd.phase('setup', pattern=pattern)
         sim = SlabSim(backend, sym.D3Q19, tuple(local), rank=rank, world=world, model=args.model,
                       precision=args.precision, access_pattern=pattern, visc=args.visc,
@@ -492,6 +538,7 @@ def run(args, world, rank, wd):
                 sim.step()
             barrier(sim)
             test_stall(wd, rank, 'first_exchange')
+        if sim.halo and args.full:
             wd.phase('setup', pattern=pattern, what='sweep-only reference')
             # what the sweep launches cost when nothing is waited for (reference for the overlap figure)
             for _ in range(10):
@@ -503,15 +550,16 @@ def run(args, world, rank, wd):
             e1 = backend.make_event(sim.calc_stream, timing=True)
             e1.synchronize()
             res['sweep_only_ms'] = e1.time_since(e0) / 20
-            sim.init_synthetic(seed=1234)
+        if sim.halo:
+            sim.init_synthetic(seed=1234)           # the timed steps start from the initial state, with or without --full
         wd.phase('warmup', pattern=pattern)
         for _ in range(args.prewarm_steps + (args.prewarm_steps & 1)):   # untimed, even count: GPU clocks ramp up
             sim.step()
         for _ in range(args.warmup):
             sim.step()
         test_stall(wd, rank, 'warmup')
-        # timed region: blocks of EXACTLY K steps, each bracketed by barrier + synchronize, max over ranks; repeated until
-        # --min_seconds have been timed (the driver's K = 20 is 64 ms at 512^3: too short a sample on its own)
+        # timed region: blocks of EXACTLY K steps, each bracketed by barrier + synchronize, max over ranks; one block in a
+        # plain run, with --full repeated until --min_seconds have been timed (K = 20 is 64 ms at 512^3)
         blocks, host, kernel = [], [], []
         total = 0.0
         while True:
@@ -536,8 +584,10 @@ def run(args, world, rank, wd):
             kernel.append(ev1.time_since(ev0) / args.steps)   # HIP events on the sweep's own stream
             host.append(per_step)
             total += elapsed
-            if total >= args.min_seconds or len(blocks) >= 200:
+            if not args.full or total >= args.min_seconds or len(blocks) >= 200:
                 break
+        if last and args.dump_outputs:
+            res['outputs'] = sample_state(sim, DUMP_BYTES // world)
         res['elapsed'] = blocks[median_block(blocks)]    # the median block; the best one is reported beside it
         res['blocks'] = blocks
         res['kernels'] = kernel                          # per block: HIP events on the sweep's own stream / K
@@ -549,13 +599,14 @@ def run(args, world, rank, wd):
         res['host_ms'] = float(flat.mean())
         res['host_ms_median'] = float(np.median(flat))
         if sim.halo:
-            # a separate short leg with timing events around the halo stream's work (entry-by-entry enqueue: the timed
-            # region above replays step plans, which carry no timing events)
-            wd.phase('halo_timing', pattern=pattern)
-            sim.start_halo_timing()
-            for _ in range(args.halo_timing_steps + (args.halo_timing_steps & 1)):
-                sim.step()
-            res['halo_ms'] = sim.stop_halo_timing()
+            if args.full:
+                # a separate short leg with timing events around the halo stream's work (entry-by-entry enqueue: the
+                # timed region above replays step plans, which carry no timing events)
+                wd.phase('halo_timing', pattern=pattern)
+                sim.start_halo_timing()
+                for _ in range(args.halo_timing_steps + (args.halo_timing_steps & 1)):
+                    sim.step()
+                res['halo_ms'] = sim.stop_halo_timing()
             res['step_plans'] = sorted(str(k) for k in getattr(sim, '_plans', {}))
             res['rccl_ranks'] = rccl_ranks_of(getattr(sim, 'exchanger', None),
                                               torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
@@ -568,16 +619,21 @@ def run(args, world, rank, wd):
         sim.release()
         return res
 
-    st_before = None if (args.no_gpu_state or rank) else gpu_state()
-    patterns = ['AA', 'AB'] if args.access_pattern == 'auto' else [args.access_pattern]
+    full = args.full
+    st_before = None if (args.no_gpu_state or rank or not full) else gpu_state()
+    if args.access_pattern == 'auto':
+        patterns = ['AA', 'AB'] if full else ['AB']
+    else:
+        patterns = [args.access_pattern]
     runs = dict((p, []) for p in patterns)
     mass0 = [None]
-    reps = max(1, args.repeats)
+    reps = max(1, args.repeats) if full else 1
+    validate_last = full and not args.no_validate
     for i in range(reps):
         for pat in patterns:
-            runs[pat].append(measure(pat, check=(i == reps - 1 and not args.no_validate)))
+            runs[pat].append(measure(pat, check=(i == reps - 1 and validate_last), last=(i == reps - 1)))
     rejected = None
-    if distributed and not args.no_validate and os.environ.get('SLF_HALO_TRANSPORT', 'auto') == 'auto':
+    if distributed and validate_last and os.environ.get('SLF_HALO_TRANSPORT', 'auto') == 'auto':
         # the peer transport has only ever run between processes that SHARE a device (the build pool has single-GPU boxes):
         # if its start-up check passed on this node but the seam layers of the final state do not match the oracle, the
         # figures above are not reported -- the run is repeated over RCCL / torch.distributed and the line says so.  (The
@@ -592,8 +648,8 @@ def run(args, world, rank, wd):
             runs = dict((p, []) for p in patterns)
             for i in range(reps):
                 for pat in patterns:
-                    runs[pat].append(measure(pat, check=(i == reps - 1)))
-    st_after = None if (args.no_gpu_state or rank) else gpu_state()
+                    runs[pat].append(measure(pat, check=(i == reps - 1), last=(i == reps - 1)))
+    st_after = None if (args.no_gpu_state or rank or not full) else gpu_state()
     wd.phase('report')
     # per access pattern: every timed block of every repeat; the pattern with the better MEDIAN block is reported
     pooled = dict((p, [b for r in rs for b in r['blocks']]) for p, rs in runs.items())
@@ -603,6 +659,10 @@ def run(args, world, rank, wd):
     # the sweep time of that very block
     kernel_ms = [k for r in runs[args.access_pattern] for k in r['kernels']][median_block(pooled[args.access_pattern])]
     best = min(runs[args.access_pattern], key=lambda r: r['elapsed'])
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'dist.npy' if world == 1 else 'dist_rank%d.npy' % rank),
+                runs[args.access_pattern][-1]['outputs'])
     per_rank = None
     if distributed:
         mine = dict((k, round(best[k], 4)) for k in ('kernel_ms', 'halo_ms', 'sweep_only_ms', 'host_ms', 'host_ms_median') if k in best)
@@ -636,9 +696,10 @@ def run(args, world, rank, wd):
                'periodic': 'in-sweep wrap' if not args.no_fused_periodic else 'ghost-layer PBC kernels',
                'decomposition': ('%s-slabs x%d, halo: %s' % (args.axis, world, (best.get('halo_transport') or '?').split(':')[0].split(' (')[0]))
                if distributed else 'single subdomain',
-               'visc': args.visc, 'block_x': best['block'], 'repeats': max(1, args.repeats),
-               'value_is': 'median block of exactly K steps (blocks repeated until --min_seconds are timed, per repeat); '
-                           'best_value = the fastest block',
+               'visc': args.visc, 'block_x': best['block'], 'repeats': reps,
+               'value_is': ('median block of exactly K steps (blocks repeated until --min_seconds are timed, per repeat); '
+                            'best_value = the fastest block') if full else
+                           'the one timed block of exactly K steps (plain run; --full: median of repeated blocks)',
                'timed_blocks': len(all_mlups), 'timed_seconds': round(sum(b for r in runs[args.access_pattern] for b in r['blocks']), 3),
                'median_mlups': round(to_mlups(elapsed), 1),
                'runs_mlups': [round(v, 1) for v in (all_mlups if len(all_mlups) <= 12 else all_mlups[:4] + all_mlups[-8:])],
@@ -651,10 +712,6 @@ def run(args, world, rank, wd):
         if rejected:
             cfg['peer_transport_rejected'] = rejected
         if distributed:
-            hm = max(r.get('halo_ms', 0.0) for r in per_rank)
-            so = max(r.get('sweep_only_ms', 0.0) for r in per_rank)
-            step_ms = elapsed / args.steps * 1e3
-            exposed = max(0.0, step_ms - so)
             cfg.update({'rccl_ranks': best.get('rccl_ranks', 0),
                         'rccl_ranks_is': 'ncclCommCount of the communicator the halos travel over (C ABI slf_comm_count); '
                                          '0 = not over RCCL',
@@ -662,14 +719,21 @@ def run(args, world, rank, wd):
                         'dist_backend': torch.distributed.get_backend(),
                         'halo_transport': best.get('halo_transport'),
                         'host_ms_median': round(max(r.get('host_ms_median', 0.0) for r in per_rank), 4),
-                        'per_rank': per_rank,
-                        'halo_overlap_frac': round(max(0.0, min(1.0, 1.0 - exposed / hm)), 3) if hm > 0 else None,
+                        'per_rank': per_rank})
+        if distributed and full:            # the sweep-only and halo-timing legs ran
+            hm = max(r.get('halo_ms', 0.0) for r in per_rank)
+            so = max(r.get('sweep_only_ms', 0.0) for r in per_rank)
+            step_ms = elapsed / args.steps * 1e3
+            exposed = max(0.0, step_ms - so)
+            cfg.update({'halo_overlap_frac': round(max(0.0, min(1.0, 1.0 - exposed / hm)), 3) if hm > 0 else None,
                         'halo_exposed_ms': round(exposed, 4)})
         if st_before or st_after:
             cfg['gpu_state'] = {'before': st_before, 'after': st_after}
         out = {
             'metric': 'MLUPS (million lattice updates/s), %s' % what,
-            'value': round(to_mlups(elapsed), 1), 'value_kind': 'median block (rounds 3-4 reported the fastest block: best_value)',
+            'value': round(to_mlups(elapsed), 1),
+            'value_kind': 'median block (rounds 3-4 reported the fastest block: best_value)' if full else
+                          'the one timed block of exactly K steps',
             'best_value': round(max(all_mlups), 1),
             'unit': 'MLUPS', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
@@ -680,10 +744,10 @@ def run(args, world, rank, wd):
                          'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': load_traffic(wkey),
                          'bytes_per_update': bpu, 'kernel_ms': round(kernel_ms, 4)},
         }
-        if world == 1 and not args.no_runner_path and not distributed and args.scaling == 'weak':
+        if full and world == 1 and not args.no_runner_path and not distributed and args.scaling == 'weak':
             cfg['runner_path'] = runner_path(args, local_rank)
             cfg['runner_path']['vs_value'] = round(cfg['runner_path']['mlups'] / out['value'], 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args)
         print(json.dumps(out))
     if distributed:

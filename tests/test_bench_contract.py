@@ -130,3 +130,42 @@ def test_rccl_ranks_come_from_the_communicator_not_from_the_process_group():
     assert bench.rccl_ranks_of(Staged(), 'nccl', 2) == 2            # SLF_HALO_TRANSPORT=torch: torch's own communicator
     hdr = open(os.path.join(ROOT, 'include', 'sailfish_hip.h')).read()
     assert 'int slf_comm_count(slf_comm* comm, int* nranks, int* rank);' in hdr
+
+
+def test_dump_sample_is_the_state_a_caller_gets():
+    """--dump-outputs: sample_state() reads the seeded z-planes of the current copy from the device and keeps the same
+    seeded nodes of each -- exactly the values SlabSim.get_dist() holds there, within the byte budget, the same every run."""
+    import numpy as np
+    from sailfish_amd import hipabi, sym
+    from sailfish_amd.box import make_box_desc
+    bench = _bench_module()
+    desc = make_box_desc(sym.D3Q19, (40, 24, 18), precision='single', access_pattern='AA', visc=0.1,
+                         periodic_fused=[1, 1, 1], fluid_only=True)
+    stride = hipabi.dist_stride(desc)
+    shape = (desc.arr_nz, desc.arr_ny, desc.arr_nx)
+    mem = np.random.RandomState(5).rand(19 * stride).astype(np.float32)
+
+    class Backend(object):
+        def from_buf(self, addr, out):          # "device" addresses are byte offsets into mem
+            out[:] = mem[addr // 4:addr // 4 + out.size]
+
+    class Sim(object):
+        Q, dtype, halo, gpu_dist, stride, backend = 19, np.float32, False, [0], None, Backend()
+
+        def sync(self):
+            pass
+
+        def current_dist_index(self):
+            return 0
+
+    sim = Sim()
+    sim.desc, sim.stride = desc, stride
+    budget = 200000
+    out = bench.sample_state(sim, budget)
+    assert out.dtype == np.float32 and out.shape[0] == 19 and out.nbytes <= budget
+    assert np.array_equal(out, bench.sample_state(sim, budget))
+    real = mem.reshape(19, stride)[:, :np.prod(shape)].reshape((19,) + shape)[:, 1:-1, 1:desc.lat_ny - 1, 1:desc.lat_nx - 1]
+    rows = real.reshape(19, -1)
+    for col in range(out.shape[1]):
+        hits = np.nonzero((rows == out[:, col:col + 1]).all(axis=0))[0]
+        assert len(hits) == 1, col                  # every sampled column is one real node's 19 populations

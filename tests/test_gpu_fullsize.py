@@ -211,7 +211,7 @@ def test_config4_eight_subdomains_full_extent(axis, transport):
                SLF_HALO_TRANSPORT=transport)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--scaling', 'strong', '--domain', '1024x512x512',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '8', '--scaling', 'strong', '--domain', '1024x512x512',
            '--axis', axis, '--steps', '4', '--warmup', '2', '--prewarm_steps', '4', '--repeats', '1', '--no_cpu_baseline',
            '--no_gpu_state', '--min_seconds', '0.05', '--halo_timing_steps', '4']
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env, timeout=1500)

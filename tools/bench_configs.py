@@ -228,7 +228,7 @@ def main():
             env.update(SLF_DIST_BACKEND='gloo', SLF_FORCE_DEVICE='0')
         for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
             env.pop(k, None)
-        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--scaling', 'strong', '--domain', '1024x512x512',
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '8', '--scaling', 'strong', '--domain', '1024x512x512',
                '--axis', axis, '--steps', '20', '--warmup', '5', '--prewarm_steps', '20', '--repeats', '1', '--no_cpu_baseline',
                '--no_gpu_state', '--min_seconds', '0.1', '--halo_timing_steps', '4']
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, env=env).stdout.decode(errors='replace')

@@ -35,10 +35,10 @@ while [ $# -gt 0 ]; do
     probe)
       timeout 900 python tools/probe/box_probe.py --out $O/box_probe $PROBE_ARGS 2>&1 | tee $O/box_probe.log | tail -60 ;;
     bench)
-      timeout 900 python bench.py $BENCH_ARGS 2>&1 | tail -1 | tee $O/bench.json | cut -c1-1500 ;;
+      timeout 900 python bench.py --full $BENCH_ARGS 2>&1 | tail -1 | tee $O/bench.json | cut -c1-1500 ;;
     trace)
       ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- \
-          python $R/bench.py --steps 100 --warmup 10 --no_cpu_baseline --no_runner_path --no_validate $BENCH_ARGS > $O/trace.log 2>&1 )
+          python $R/bench.py --full --steps 100 --warmup 10 --no_cpu_baseline --no_runner_path --no_validate $BENCH_ARGS > $O/trace.log 2>&1 )
       summarise_trace $O/trace $O/kernel_stats.csv; tail -1 $O/trace.log | cut -c1-400 ;;
     pmc)
       i=0
@@ -47,13 +47,13 @@ while [ $# -gt 0 ]; do
         [ "$C" = SKIP ] && break
         i=$((i+1))
         ( cd /tmp && timeout 600 rocprofv3 --pmc $C --output-format csv -d $O/pmc/p$i -o pmc -- \
-            python $R/bench.py --steps 20 --warmup 4 --no_cpu_baseline --no_runner_path --no_validate --repeats 1 --prewarm_steps 0 $BENCH_ARGS > $O/pmc_p$i.log 2>&1 )
+            python $R/bench.py --full --steps 20 --warmup 4 --no_cpu_baseline --no_runner_path --no_validate --repeats 1 --prewarm_steps 0 $BENCH_ARGS > $O/pmc_p$i.log 2>&1 )
       done
       python tools/pmc_summary.py $O/pmc | tee $O/pmc_summary.txt ;;
     torchrun)
       for mode in "--scaling weak" "--scaling strong --domain 1024x512x512 --axis z" "--scaling strong --domain 1024x512x512 --axis x"; do
         timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-          bench.py --gpus 1 --steps 100 --warmup 10 --no_cpu_baseline --force_distributed $mode 2>&1 | tail -1 | tee -a $O/torchrun.jsonl | cut -c1-1200
+          bench.py --full --gpus 1 --steps 100 --warmup 10 --no_cpu_baseline --force_distributed $mode 2>&1 | tail -1 | tee -a $O/torchrun.jsonl | cut -c1-1200
       done ;;
     configs)
       timeout 1500 python tools/bench_configs.py $CONFIG_ARGS 2>&1 | tee $O/configs.jsonl | tail -12 ;;

@@ -14,5 +14,5 @@ if [ "$slow" = 1 ] || [ -n "$FORCE_PROBE" ]; then
     echo "$opt: $(one $opt)"
   done
   timeout 300 python tools/perf_probe.py --dims 256x256x256 --variants 11 --blocks 576 --modes even,odd,ab 2>&1 | grep variant
-  timeout 300 python bench.py --steps 60 --no_cpu_baseline --repeats 1 --prewarm_steps 100 | cut -c1-140
+  timeout 300 python bench.py --full --steps 60 --no_cpu_baseline --repeats 1 --prewarm_steps 100 | cut -c1-140
 fi

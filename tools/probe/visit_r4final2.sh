@@ -3,8 +3,8 @@ export GPU_TAG=r4final2
 O=gpurun_out/r4final2; mkdir -p $O
 bash tools/gpu.sh host smoke
 ( time timeout 1500 python -m pytest tests -m gpu -q --durations=8 ) > $O/pytest_gpu.log 2>&1; tail -14 $O/pytest_gpu.log
-timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-600 $O/bench_final.json
-timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-600 $O/bench_final.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
 for pat in AA; do
   BENCH_ARGS="--access_pattern $pat" bash tools/gpu.sh trace; cp $O/kernel_stats.csv $O/kernel_stats_${pat}_final.csv; rm -rf $O/trace
 done

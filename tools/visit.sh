@@ -10,14 +10,14 @@ case $NAME in
     ( time timeout 900 python -m pytest tests/test_gpu_physics3d.py -m gpu -q -s --durations=12 ) > $O/pytest_physics3d.log 2>&1; grep -v "^$" $O/pytest_physics3d.log | tail -60
     ( time timeout 1500 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -s -k eight_subdomains --durations=4 ) > $O/pytest_config4_8.log 2>&1; tail -25 $O/pytest_config4_8.log
     ( time timeout 1200 python -m pytest tests/test_gpu_two_ranks.py tests/test_gpu_face_kernels.py -m gpu -q -x --durations=6 ) > $O/pytest_ranks.log 2>&1; tail -15 $O/pytest_ranks.log
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd.json; cut -c1-700 $O/bench_driver_cmd.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd.json; cut -c1-700 $O/bench_driver_cmd.json
     ;;
   r5v2)   # what bounds the Shan-Chen kernels (SQ counters, kernel trace) + the x-slab step against RCCL's channel count
     TRACE_CONFIGS="4" bash tools/gpu.sh tracecfg sqcfg; rm -rf $O/trace_cfg*/ $O/sq_cfg*/
     X="--force_distributed --scaling strong --domain 128x512x512 --axis x --no_cpu_baseline --no_gpu_state --access_pattern AA --repeats 1"
     for ch in default 1 2 4; do
       if [ $ch = default ]; then unset NCCL_MAX_NCHANNELS; else export NCCL_MAX_NCHANNELS=$ch; fi
-      timeout 300 python bench.py $X 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config']; r=c['per_rank'][0]; print('nchannels $ch', d['value'], d['best_value'], d['ms_per_step'], 'kernel', r['kernel_ms'], 'sweep_only', r['sweep_only_ms'], 'halo', r['halo_ms'], 'exposed', c['halo_exposed_ms'], c['validated'])" | tee -a $O/xslab_nchannels.txt
+      timeout 300 python bench.py --full $X 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config']; r=c['per_rank'][0]; print('nchannels $ch', d['value'], d['best_value'], d['ms_per_step'], 'kernel', r['kernel_ms'], 'sweep_only', r['sweep_only_ms'], 'halo', r['halo_ms'], 'exposed', c['halo_exposed_ms'], c['validated'])" | tee -a $O/xslab_nchannels.txt
     done
     unset NCCL_MAX_NCHANNELS
     ;;
@@ -28,7 +28,7 @@ case $NAME in
     X="--gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis x --no_cpu_baseline --no_gpu_state --access_pattern AA --repeats 1"
     for ch in default 1 2 4; do
       if [ $ch = default ]; then unset NCCL_MAX_NCHANNELS; else export NCCL_MAX_NCHANNELS=$ch; fi
-      timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py $X 2>&1 | tail -1 > $O/xslab_$ch.json
+      timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full $X 2>&1 | tail -1 > $O/xslab_$ch.json
       python -c "import sys,json; d=json.load(open('$O/xslab_$ch.json')); c=d['config']; r=c['per_rank'][0]; print('nchannels $ch', d['value'], d['best_value'], d['ms_per_step'], 'kernel', r['kernel_ms'], 'sweep_only', r['sweep_only_ms'], 'halo', r['halo_ms'], 'exposed', c['halo_exposed_ms'], c['validated'], c['rccl_ranks'])" 2>&1 | tail -1 | tee -a $O/xslab_nchannels.txt
     done
     unset NCCL_MAX_NCHANNELS
@@ -38,7 +38,7 @@ case $NAME in
     X="--gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis x --no_cpu_baseline --no_gpu_state --access_pattern AA --repeats 1"
     for ch in 8 16 32; do
       export NCCL_MIN_NCHANNELS=$ch
-      timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py $X 2>&1 | tail -1 > $O/xslab_min$ch.json
+      timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full $X 2>&1 | tail -1 > $O/xslab_min$ch.json
       python -c "import sys,json; d=json.load(open('$O/xslab_min$ch.json')); c=d['config']; r=c['per_rank'][0]; print('min_nchannels $ch', d['value'], d['best_value'], d['ms_per_step'], 'kernel', r['kernel_ms'], 'sweep_only', r['sweep_only_ms'], 'halo', r['halo_ms'], 'exposed', c['halo_exposed_ms'], c['validated'], c['rccl_ranks'])" 2>&1 | tail -1 | tee -a $O/xslab_min_nchannels.txt
     done
     unset NCCL_MIN_NCHANNELS
@@ -76,8 +76,8 @@ case $NAME in
   r5final)   # round-5 evidence visit: everything DESIGN.md / profiles/traffic.json quote for the shipped kernels
     bash tools/gpu.sh host smoke
     ( time timeout 2400 python -m pytest tests -m gpu -q --durations=12 ) > $O/pytest_gpu_final.log 2>&1; tail -22 $O/pytest_gpu_final.log
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
     for pat in AA AB; do
       BENCH_ARGS="--access_pattern $pat" bash tools/gpu.sh trace pmc; cp $O/kernel_stats.csv $O/kernel_stats_${pat}_final.csv; cp $O/pmc_summary.txt $O/pmc_summary_${pat}_512.txt; rm -rf $O/trace $O/pmc
     done
@@ -91,10 +91,10 @@ case $NAME in
     ;;
   r5final2)   # after the last test / doc changes: the tests that changed, the bench lines with `traffic` from the re-stamped file, f64
     ( time timeout 900 python -m pytest tests/test_gpu_face_kernels.py tests/test_gpu_comm.py tests/test_gpu_resident.py tests/test_gpu_sc.py -m gpu -q --durations=3 ) > $O/pytest_changed.log 2>&1; tail -8 $O/pytest_changed.log
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-300 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
-    timeout 900 python bench.py --precision double --no_cpu_baseline 2>&1 | tail -1 > $O/bench_f64_final.json; cut -c1-300 $O/bench_f64_final.json
-    timeout 900 python bench.py --model mrt --no_cpu_baseline 2>&1 | tail -1 > $O/bench_mrt_final.json; cut -c1-300 $O/bench_mrt_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-300 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full --precision double --no_cpu_baseline 2>&1 | tail -1 > $O/bench_f64_final.json; cut -c1-300 $O/bench_f64_final.json
+    timeout 900 python bench.py --full --model mrt --no_cpu_baseline 2>&1 | tail -1 > $O/bench_mrt_final.json; cut -c1-300 $O/bench_mrt_final.json
     ;;
   r5dn)   # do-nothing outlets (in place) and full-slip walls: their tests first, the headline line and the two PMC passes
           # profiles/traffic.json is stamped from (the kernel sources changed), then the whole GPU suite
@@ -107,8 +107,8 @@ case $NAME in
       rm -rf $O/pmc
     done
     cp profiles/traffic.json $O/traffic.json
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
     ( time timeout 2400 python -m pytest tests -m gpu -q --durations=8 ) > $O/pytest_gpu_final.log 2>&1; tail -16 $O/pytest_gpu_final.log
     ;;
   r5last)   # the remaining evidence files on the final sources: smoke(), kernel traces of the headline command, f64 / MRT lines,
@@ -117,8 +117,8 @@ case $NAME in
     for pat in AA AB; do
       BENCH_ARGS="--access_pattern $pat" bash tools/gpu.sh trace; cp $O/kernel_stats.csv $O/kernel_stats_${pat}_final.csv; rm -rf $O/trace
     done
-    timeout 900 python bench.py --precision double --no_cpu_baseline 2>&1 | tail -1 > $O/bench_f64_final.json; cut -c1-300 $O/bench_f64_final.json
-    timeout 900 python bench.py --model mrt --no_cpu_baseline 2>&1 | tail -1 > $O/bench_mrt_final.json; cut -c1-300 $O/bench_mrt_final.json
+    timeout 900 python bench.py --full --precision double --no_cpu_baseline 2>&1 | tail -1 > $O/bench_f64_final.json; cut -c1-300 $O/bench_f64_final.json
+    timeout 900 python bench.py --full --model mrt --no_cpu_baseline 2>&1 | tail -1 > $O/bench_mrt_final.json; cut -c1-300 $O/bench_mrt_final.json
     timeout 600 python tools/bench_configs.py 2>/dev/null | grep '^{' > $O/configs_final.jsonl; cut -c1-140 $O/configs_final.jsonl
     ;;
   r5duct)   # what the level-2 kernels cost where EVERY row holds boundary nodes: an open duct along x against one along z
@@ -220,13 +220,13 @@ c.run(ignore_cmdline=True)
     for tr in peer rccl; do
       for ax in x z; do
         SLF_HALO_TRANSPORT=$tr timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 \
-          bench.py --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis $ax $X 2> $O/one_${tr}_$ax.err | tail -1 > $O/one_${tr}_$ax.json
+          bench.py --full --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis $ax $X 2> $O/one_${tr}_$ax.err | tail -1 > $O/one_${tr}_$ax.json
         line "one rank $tr $ax" < $O/one_${tr}_$ax.json | tee -a $O/summary.txt
       done
     done
     for n in 2 8; do
       for ax in x z; do
-        SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus $n --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n${n}_$ax.err | tail -1 > $O/n${n}_$ax.json
+        SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus $n --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n${n}_$ax.err | tail -1 > $O/n${n}_$ax.json
         line "$n processes $ax" < $O/n${n}_$ax.json | tee -a $O/summary.txt
       done
     done
@@ -239,12 +239,12 @@ c.run(ignore_cmdline=True)
     for q in 3 4; do GPU_MAX_HW_QUEUES=$q timeout 120 tools/probe/ipc_probe 8 262144 10 256 2>&1 | grep "ring ping" | sed "s/^/queues $q: /" | tee -a $O/summary.txt; done
     for q in 2 3 4; do
       for ch in 4 2 1; do
-        GPU_MAX_HW_QUEUES=$q SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 600 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_q${q}_c$ch.err | tail -1 > $O/n8_x_q${q}_c$ch.json
+        GPU_MAX_HW_QUEUES=$q SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 600 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_q${q}_c$ch.err | tail -1 > $O/n8_x_q${q}_c$ch.json
         line "8 processes x, $q queues, $ch chunks" < $O/n8_x_q${q}_c$ch.json | tee -a $O/summary.txt
       done
     done
     for q in 3 4; do
-      GPU_MAX_HW_QUEUES=$q SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 600 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X 2> $O/n8_z_q$q.err | tail -1 > $O/n8_z_q$q.json
+      GPU_MAX_HW_QUEUES=$q SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 600 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X 2> $O/n8_z_q$q.err | tail -1 > $O/n8_z_q$q.json
       line "8 processes z, $q queues" < $O/n8_z_q$q.json | tee -a $O/summary.txt
     done
     ;;
@@ -255,18 +255,18 @@ c.run(ignore_cmdline=True)
     line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d.get('config',{}); r=(c.get('per_rank') or [{}])[0]; print('$1', d.get('value'), d.get('ms_per_step'), c.get('access_pattern'), 'validated', c.get('validated'), 'exposed', c.get('halo_exposed_ms'), 'sweep_only', r.get('sweep_only_ms'), '|', (c.get('halo_transport') or '')[:24], d.get('error'))" 2>&1 | tail -1; }
     for tr in peer rccl; do
       SLF_HALO_TRANSPORT=$tr timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 \
-        bench.py --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis x $X 2> $O/one_${tr}_x.err | tail -1 > $O/one_${tr}_x.json
+        bench.py --full --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis x $X 2> $O/one_${tr}_x.err | tail -1 > $O/one_${tr}_x.json
       line "one rank $tr x" < $O/one_${tr}_x.json | tee -a $O/summary.txt
     done
     for ch in 4 2 1; do
-      SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_c$ch.err | tail -1 > $O/n8_x_c$ch.json
+      SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_c$ch.err | tail -1 > $O/n8_x_c$ch.json
       line "8 processes x, $ch chunks" < $O/n8_x_c$ch.json | tee -a $O/summary.txt
     done
     for v in "SLF_HALO_PRIORITY=1 SLF_CALC_STREAMS=2" "SLF_HALO_PRIORITY=0 SLF_CALC_STREAMS=2" "SLF_HALO_PRIORITY=1 SLF_CALC_STREAMS=1"; do
-      env $v SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X --no_validate --access_pattern AA 2> $O/n8_z.err | tail -1 > $O/n8_z.json
+      env $v SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X --no_validate --access_pattern AA 2> $O/n8_z.err | tail -1 > $O/n8_z.json
       line "8 processes z, $v" < $O/n8_z.json | tee -a $O/summary.txt
     done
-    SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 2 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n2_x.err | tail -1 > $O/n2_x.json
+    SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 2 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n2_x.err | tail -1 > $O/n2_x.json
     line "2 processes x" < $O/n2_x.json | tee -a $O/summary.txt
     tail -n 5 $O/*.err | tail -n 40
     ;;
@@ -278,20 +278,20 @@ c.run(ignore_cmdline=True)
     for tr in peer rccl; do
       for ax in x z; do
         SLF_HALO_TRANSPORT=$tr timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 \
-          bench.py --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis $ax $X 2> $O/one_${tr}_$ax.err | tail -1 > $O/one_${tr}_$ax.json
+          bench.py --full --gpus 1 --force_distributed --scaling strong --domain 128x512x512 --axis $ax $X 2> $O/one_${tr}_$ax.err | tail -1 > $O/one_${tr}_$ax.json
         line "one rank $tr $ax" < $O/one_${tr}_$ax.json | tee -a $O/summary.txt
       done
     done
     for ch in 4 2 1; do
-      SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_c$ch.err | tail -1 > $O/n8_x_c$ch.json
+      SLF_XFACE_CHUNKS=$ch SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis x $X 2> $O/n8_x_c$ch.err | tail -1 > $O/n8_x_c$ch.json
       line "8 processes x, $ch chunks" < $O/n8_x_c$ch.json | tee -a $O/summary.txt
     done
     for v in "SLF_CALC_STREAMS=2" "SLF_CALC_STREAMS=1"; do
-      env $v SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X 2> $O/n8_z.err | tail -1 > $O/n8_z_$v.json
+      env $v SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis z $X 2> $O/n8_z.err | tail -1 > $O/n8_z_$v.json
       line "8 processes z, $v" < $O/n8_z_$v.json | tee -a $O/summary.txt
     done
     for ax in x z; do
-      SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 2 --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n2_$ax.err | tail -1 > $O/n2_$ax.json
+      SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 2 --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n2_$ax.err | tail -1 > $O/n2_$ax.json
       line "2 processes $ax" < $O/n2_$ax.json | tee -a $O/summary.txt
     done
     grep -v "socket.cpp\|amdgpu.ids" $O/*.err | tail -n 30
@@ -302,13 +302,13 @@ c.run(ignore_cmdline=True)
     line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d.get('config',{}); r=(c.get('per_rank') or [{}])[0]; print('$1', d.get('value'), d.get('ms_per_step'), c.get('access_pattern'), 'validated', c.get('validated'), dict((k, v.get('populations_bit_identical')) for k, v in c.get('validation', {}).items()), 'exposed', c.get('halo_exposed_ms'), '|', (c.get('halo_transport') or '')[:24], d.get('error'))" 2>&1 | tail -1; }
     for ax in x z; do
       for pat in AB auto; do
-        SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 2 --scaling strong --domain 512x256x256 --axis $ax --access_pattern $pat $X 2> $O/n2_${ax}_$pat.err | tail -1 > $O/n2_${ax}_$pat.json
+        SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 2 --scaling strong --domain 512x256x256 --axis $ax --access_pattern $pat $X 2> $O/n2_${ax}_$pat.err | tail -1 > $O/n2_${ax}_$pat.json
         line "2 processes $ax $pat" < $O/n2_${ax}_$pat.json | tee -a $O/summary.txt
       done
     done
     ( time timeout 1500 python -m pytest tests/test_gpu_two_ranks.py -m gpu -q --durations=8 -k "stops or controller_branch or equal_one_box" ) > $O/pytest_peer.log 2>&1; tail -12 $O/pytest_peer.log
     for ax in x z; do
-      SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --gpus 8 --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n8_$ax.err | tail -1 > $O/n8_$ax.json
+      SLF_DIST_BACKEND=gloo SLF_FORCE_DEVICE=0 timeout 900 python bench.py --full --gpus 8 --scaling strong --domain 1024x512x512 --axis $ax $X 2> $O/n8_$ax.err | tail -1 > $O/n8_$ax.json
       line "8 processes $ax" < $O/n8_$ax.json | tee -a $O/summary.txt
     done
     grep -v "socket.cpp\|amdgpu.ids" $O/*.err | tail -n 30
@@ -430,8 +430,8 @@ PYEOF
       rm -rf $O/pmc
     done
     cp profiles/traffic.json $O/traffic.json
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
     ;;
   r6s3)   # the planes in the in-place pattern: parity, checkpoints, then 256^3 in 4 x-slabs AA with / without
     ( time timeout 1500 python -m pytest tests/test_gpu_sc.py -m gpu -q -x --durations=5 ) > $O/pytest_sc_all.log 2>&1; tail -12 $O/pytest_sc_all.log
@@ -508,8 +508,8 @@ PYEOF
       rm -rf $O/pmc
     done
     cp profiles/traffic.json $O/traffic.json
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
     for pat in AA AB; do
       BENCH_ARGS="--access_pattern $pat" bash tools/gpu.sh trace; cp $O/kernel_stats.csv $O/kernel_stats_${pat}_final.csv; rm -rf $O/trace
     done
@@ -575,16 +575,16 @@ PYEOF
       rm -rf $O/pmc
     done
     cp profiles/traffic.json $O/traffic.json
-    timeout 900 python bench.py 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
+    timeout 900 python bench.py --full 2>&1 | tail -1 > $O/bench_final.json; cut -c1-400 $O/bench_final.json
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | tail -1 > $O/bench_driver_cmd_final.json; cut -c1-300 $O/bench_driver_cmd_final.json
     for pat in AA AB; do
       BENCH_ARGS="--access_pattern $pat" bash tools/gpu.sh trace; cp $O/kernel_stats.csv $O/kernel_stats_${pat}_final.csv; rm -rf $O/trace
     done
     # the same box, back to back: the 256^3 box of BASELINE config 2 through bench.py and through the host stack, and the headline again
-    timeout 600 python bench.py --size 256 --no_cpu_baseline --no_gpu_state 2>&1 | tail -1 > $O/bench_256.json; cut -c1-200 $O/bench_256.json
+    timeout 600 python bench.py --full --size 256 --no_cpu_baseline --no_gpu_state 2>&1 | tail -1 > $O/bench_256.json; cut -c1-200 $O/bench_256.json
     timeout 1500 python tools/bench_configs.py 2>/dev/null | grep '^{' > $O/configs_final.jsonl; cut -c1-150 $O/configs_final.jsonl
     timeout 900 python tools/bench_configs.py --only 6xa,6xb,7a,7b,7c,7d,8a,8b,9a,9b 2>/dev/null | grep '^{' >> $O/configs_final.jsonl; tail -10 $O/configs_final.jsonl | cut -c1-150
-    timeout 600 python bench.py --steps 20 --warmup 5 --no_cpu_baseline 2>&1 | tail -1 > $O/bench_driver_cmd_after_configs.json; cut -c1-200 $O/bench_driver_cmd_after_configs.json
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no_cpu_baseline 2>&1 | tail -1 > $O/bench_driver_cmd_after_configs.json; cut -c1-200 $O/bench_driver_cmd_after_configs.json
     bash tools/gpu.sh torchrun; mv $O/torchrun.jsonl $O/torchrun_final_peer.jsonl
     SLF_HALO_TRANSPORT=rccl bash tools/gpu.sh torchrun; mv $O/torchrun.jsonl $O/torchrun_final_rccl.jsonl
     ( time timeout 2700 python -m pytest tests -m gpu -q --durations=12 ) > $O/pytest_gpu_final.log 2>&1; tail -22 $O/pytest_gpu_final.log
