@@ -351,7 +351,7 @@ class TorchDistConnector(NoQuiesce):
 
     def exchange_pieces(self, runner, pieces):
         """pieces: [(neighbour id, send address, receive address, elements)] -- ranges of the x-face buffers that a
-        z-chunk of the sweep has completed (subdomain_runner._run_sweep_xface); one batched group, on the data stream."""
+        z-chunk of the sweep has completed (SubdomainRunner._program_xface); one batched group, on the data stream."""
         import torch
         if not pieces:
             return

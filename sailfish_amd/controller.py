@@ -112,7 +112,7 @@ class LocalGroup(object):
             mine = msgs[r._spec.id]
             if not mine:
                 continue
-            if getattr(r, '_nnx', None) is not None and r._nnx_serial(self):
+            if r._nnx is not None and r._nnx_serial(self):
                 continue        # shared planes, one calc stream: nothing to move and nothing to order
             sh = r._data_stream
             for nid, (_, _, _, recv_buf, n_recv) in sorted(mine.items()):
@@ -156,47 +156,25 @@ class LocalGroup(object):
         receive buffer (per step parity), and the per-step device copies between them (a quarter of the GPU's time in a
         traced three-slab pipe run, profiles/r05/kernel_stats_pipe_3x_before.csv) disappear; the events that order A's
         reads after B's sweep stay.  A.recv keeps its memory and content (it may have been primed from a restored state)."""
-        from sailfish_amd import xface
         if os.environ.get('SLF_XFACE_SHARE', '1') == '0':
             return
         done = 0
         for r in self.runners:
-            # the binary Shan-Chen model's planes (xface.NNPlanes): the neighbour's send buffer of a link BECOMES my receive
-            # buffer of the same link, per kind and step parity (a link's buffer holds its faces in the order both sides use)
-            if getattr(r, '_nnx', None) is None:
+            if not r._halo.shareable:
                 continue
-            for kind, links in (('dist', r._links), ('macro', r._macro_links)):
-                for nid, link in links.items():
+            # the neighbour's send buffers of a link BECOME my receive buffers of the same link, per kind and step parity (a
+            # link's buffer holds its faces in the order both sides use: halo.face_layout)
+            for kind in ('dist', 'macro'):
+                for nid, link in r._halo.of_kind(kind).items():
                     nb = self.by_id.get(nid)
-                    if nb is None or getattr(nb, '_nnx', None) is None or nb.backend.gpu_id != r.backend.gpu_id:
+                    if nb is None or type(nb._halo) is not type(r._halo) or nb.backend.gpu_id != r.backend.gpu_id:
                         continue
-                    nlink = (nb._links if kind == 'dist' else nb._macro_links)[r._spec.id]
-                    for par in (0, 1):
-                        nlink.send_bufs[par] = link.recv_bufs[par]
-                        done += 1
-                    nlink.send_buf = nlink.send_bufs[0]
-                    nb._nnx_place(kind, r._spec.id)
-                    r._nnx.shared = nb._nnx.shared = True
+                    nb._halo.adopt(kind, r._spec.id, link.recv_bufs)
+                    r._halo.planes.shared = True
+                    done += len(link.recv_bufs)
         for r in self.runners:
-            if getattr(r, '_nnx', None) is not None and r._nnx.shared:
-                r._nnx_prime()          # the send planes are final now: the densities the pass in front never rewrites
-        for r in self.runners:
-            if r._xface is None:
-                continue
-            sp = r._spec
-            for face, nid in sp.connecting_subdomains():
-                if face not in (sp.X_LOW, sp.X_HIGH):
-                    continue
-                nb = self.by_id.get(nid)
-                if nb is None or nb._xface is None or nb.backend.gpu_id != r.backend.gpu_id:
-                    continue
-                f = xface.LOW if face == sp.X_LOW else xface.HIGH
-                for par in (0, 1):
-                    if r._xface.recv[par][f] and nb._xface.send[par][1 - f]:
-                        nb._xface.send[par][1 - f] = r._xface.recv[par][f]
-                        done += 1
-                r._xface.shared = nb._xface.shared = True
-                r._xface._bound = nb._xface._bound = None
+            if r._nnx is not None and r._nnx.shared:
+                r._halo.prime()         # the send planes are final now: the densities the pass in front never rewrites
         if done:
             self.runners[0].config.logger.debug('x-face buffers shared between the subdomains of this process: %d' % done)
         self._serialise_sweeps()
@@ -215,7 +193,7 @@ class LocalGroup(object):
         if os.environ.get('SLF_GROUP_ONE_STREAM', '1') == '0' or len(rs) < 2:
             return
         def shared_planes(r):
-            if getattr(r, '_nnx', None) is not None:
+            if r._nnx is not None:
                 return r._nnx.shared
             return r._xface is not None and r._xface.shared and len(r._xchunks.order) == 1
 
@@ -260,8 +238,7 @@ class LocalGroup(object):
                 r.backend.set_iteration(it)
             self._program(DirectQueue(b0), it, reqs)
         for r in rs:
-            if r._xface is not None:
-                r._xface._bound = None
+            r._halo.unbind()
             r._sim.iteration += 1
             r.backend.set_iteration(r._sim.iteration)
 

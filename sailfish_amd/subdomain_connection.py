@@ -26,11 +26,23 @@ import numpy as np
 
 
 
-class HaloLink(object):
+class Link(object):
+    """One neighbour relation of one exchange ('dist': populations, 'macro': fields of the non-local models), the same
+    for every halo scheme (sailfish_amd/halo.py): device buffers and kernels by the parity of the step they serve."""
+
+    def __init__(self, neighbour_id, faces=None, n_send=0, n_recv=0):
+        self.neighbour_id = neighbour_id
+        self.faces = faces                              # x-face schemes: my faces that lead to this neighbour (low, high)
+        self.n_send, self.n_recv = n_send, n_recv       # elements of one message
+        self.send_bufs = self.recv_bufs = None          # [parity] device addresses
+        self.packs, self.unpacks = [[], []], [[], []]   # [parity] kernels; none where the sweeps fill the buffers themselves
+
+
+class HaloLink(Link):
     """Index lists (uint64, q * dist_stride + node index) of one directed neighbour relation."""
 
     def __init__(self, neighbour_id):
-        self.neighbour_id = neighbour_id
+        Link.__init__(self, neighbour_id)
         self.push_send = self.push_recv = self.pull_send = self.pull_recv = None
 
     @property
@@ -246,11 +258,11 @@ def ghost_owned_by_others(spec, specs, gsize, periodic):
     return out
 
 
-class MacroLink(object):
+class MacroLink(Link):
     """Node index lists (uint64) of one neighbour relation for macroscopic fields."""
 
     def __init__(self, neighbour_id):
-        self.neighbour_id = neighbour_id
+        Link.__init__(self, neighbour_id)
         self.send = np.zeros(0, dtype=np.uint64)
         self.recv = np.zeros(0, dtype=np.uint64)
 

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from sailfish_amd import hipabi, io, subdomain_connection, util, xface
+from sailfish_amd import halo, hipabi, io, subdomain_connection, util, xface
 from sailfish_amd import node_type as nt
 from sailfish_amd.lb_base import LBSim  # noqa: F401  (type reference)
 from sailfish_amd.profile import TimeProfile
@@ -59,7 +59,7 @@ class SubdomainRunner(object):
         self._gpu_grids_primary = []
         self._gpu_grids_secondary = []
         self._kernels_prepared = False
-        self._links = {}
+        self._halo = halo.Halo()
         self._connector = None
         self._all_specs = None
         self._global_size = None
@@ -372,225 +372,27 @@ class SubdomainRunner(object):
         kernel = self.get_kernel(name, args, args_format, needs_iteration=needs_iteration)
         self.backend.run_kernel(kernel, None, self._calc_stream)
 
-    # ------------------------------------------------------------------ halo
+    # ------------------------------------------------------------------ halo (sailfish_amd/halo.py)
     def _init_halo(self):
-        """Index lists, device buffers and pack / unpack kernels for every neighbour.  A model with
-        several lattices (binary fluids) sends them back to back in one message per neighbour."""
-        self._links = {}
-        self._macro_links = {}
-        self._ev_halo = None
-        if self._all_specs is None or len(self._all_specs) < 2:
-            return
-        if self._connector is None:
-            from sailfish_amd.connector import LocalConnector
-            self._connector = LocalConnector()
-        if self._x_faces_only():
-            return self._init_xface_halo()
-        arr = list(reversed(self._physical_size))
-        dense_nodes = self._get_nodes()
-        links = subdomain_connection.build_halo_links(self._spec, self._all_specs, self._global_size,
-                                                      self._global_periodic, self._sim.grid, arr,
-                                                      dense_nodes if self.indirect else self._dist_stride,
-                                                      fused=self._fused)
-        if self.indirect:
-            self._translate_halo_links(links, self._host_indirect_address, dense_nodes, self._dist_stride)
-        b = self.backend
-        if self._connector is None:
-            from sailfish_amd.connector import LocalConnector
-            self._connector = LocalConnector()
-        aa = self.config.access_pattern == 'AA'
-        modes = ('push', 'pull') if aa else ('push',)
-        n_grids = len(self._gpu_grids_primary)
-        isz = np.dtype(self.float).itemsize
-        # zero-copy connectors (connector.PeerConnector): my pack kernels write the neighbour's receive buffer, which is
-        # mapped here; two sets that alternate by step parity
-        zc = getattr(self._connector, 'zero_copy', False)
-        todo = []
-        for nid in sorted(links):
-            link = links[nid]
-            n_send = max(len(link.push_send), len(link.pull_send))
-            n_recv = max(len(link.push_recv), len(link.pull_recv))
-            if n_send == 0 and n_recv == 0:
-                continue
-            if zc:
-                link.recv_bufs = [self._connector.alloc_recv(self, 'dist', nid, par, n_recv * n_grids, self.float) for par in (0, 1)]
-            else:
-                link.send_buf = self._connector.alloc_buffer(self, n_send * n_grids, self.float)
-                link.recv_buf = self._connector.alloc_buffer(self, n_recv * n_grids, self.float)
-                link.send_bufs, link.recv_bufs = [link.send_buf] * 2, [link.recv_buf] * 2
-            todo.append((nid, link))
-        if zc:
-            self._connector.resolve(self)            # collective: every rank, whatever its links
-        for nid, link in todo:
-            if zc:
-                link.send_bufs = [self._connector.send_addr(self, 'dist', nid, par) for par in (0, 1)]
-                link.send_buf, link.recv_buf = link.send_bufs[0], link.recv_bufs[0]
-            link.kernels = {}
-            for mode in modes:
-                s_idx = getattr(link, mode + '_send')
-                r_idx = getattr(link, mode + '_recv')
-                g_s = b.alloc_buf(like=s_idx) if len(s_idx) else 0
-                g_r = b.alloc_buf(like=r_idx) if len(r_idx) else 0
-                for copy in range(1 if not self._gpu_grids_secondary else 2):
-                    # the parity of the steps these kernels serve: in place the even steps pull, two-copy the steps that
-                    # write copy `copy`
-                    par = (0 if mode == 'pull' else 1) if aa else 1 - copy
-                    packs, unpacks = [], []
-                    for g in range(n_grids):
-                        dist = self.gpu_dist(g, copy)
-                        if len(s_idx):
-                            packs.append(self.get_kernel('CollectSparseData', [
-                                g_s, dist, link.send_bufs[par] + g * len(s_idx) * isz, len(s_idx)], 'PPPi'))
-                        if len(r_idx):
-                            unpacks.append(self.get_kernel('DistributeSparseData', [
-                                g_r, dist, link.recv_bufs[par] + g * len(r_idx) * isz, len(r_idx)], 'PPPi'))
-                    link.kernels[(mode, copy)] = (packs, unpacks, len(s_idx) * n_grids, len(r_idx) * n_grids)
-            self._links[nid] = link
+        """The halo scheme of this subdomain: links, device buffers, pack / unpack kernels or face buffers."""
+        self._halo = halo.make(self)
 
-    # -- 1-D decompositions along x: dense face buffers written / read by the sweep itself (xface.py)
-    _xface = None
-
-    def _x_faces_only(self):
-        """Every subdomain of the simulation is connected through its x faces only, and the model can use the
-        x-face buffers (same answer in every runner of the simulation)."""
-        if not getattr(self.config, 'hip_xface', True) or self.has_macro_exchange or self.dim != 3 or \
-                not getattr(self.backend, 'supports_xface', False):
-            return False
-        if not xface.supported(self._sim.grid, self._desc, self.indirect) or len(self._sim.grids) != 1:
-            return False
-        return self._x_slabs_line_up()
-
-    def _x_slabs_line_up(self):
-        """A 1-D decomposition along x whose slabs share their y / z extent (same answer in every runner)."""
-        local = self._local_periodic()
-        if any(local[a] and not self._fused[a] for a in range(self.dim)):
-            # periodic images made by the ghost-layer kernels live in the arrays, not in the face buffers
-            return False
-        ref = self._all_specs[0]
-        for spec in self._all_specs:
-            if tuple(spec.location[1:]) != tuple(ref.location[1:]) or tuple(spec.size[1:]) != tuple(ref.size[1:]):
-                return False        # faces that only partly overlap: rows of the two sides do not line up
-            faces = set(face for face, _ in spec.connecting_subdomains())
-            if not faces or not faces <= set((spec.X_LOW, spec.X_HIGH)):
-                return False
-            if spec.size[0] > 1024 or spec.size[0] < 2:
-                return False
-        return True
-
-    def _init_xface_halo(self):
-        """Per neighbour and step parity one send and one receive buffer: [what leaves through my low face | through my
-        high face] (the faces that lead to this neighbour); it arrives as [its high-face input | its low-face input] on
-        the other side.  The sweep is cut into z-chunks and the planes a chunk completes travel at once
-        (xface.ChunkPlan)."""
-        spec = self._spec
-        n = xface.face_count(self._desc)
-        isz = np.dtype(self.float).itemsize
-        by_neighbour = {}
-        for face, nid in sorted(spec.connecting_subdomains()):
-            by_neighbour.setdefault(nid, []).append(xface.LOW if face == spec.X_LOW else xface.HIGH)
-        send, recv = [[0, 0], [0, 0]], [[0, 0], [0, 0]]
-        self._xface_routes = []          # (neighbour id, my face, parity -> send address, parity -> receive address)
-        zc = getattr(self._connector, 'zero_copy', False)
-        for nid in sorted(by_neighbour):
-            faces = sorted(by_neighbour[nid])
-            link = subdomain_connection.HaloLink(nid)
-            link.faces = faces
-            if zc:
-                link.recv_bufs = [self._connector.alloc_recv(self, 'dist', nid, par, n * len(faces), self.float) for par in (0, 1)]
-            else:
-                link.send_bufs = [self._connector.alloc_buffer(self, n * len(faces), self.float) for _ in (0, 1)]
-                link.recv_bufs = [self._connector.alloc_buffer(self, n * len(faces), self.float) for _ in (0, 1)]
-            self._links[nid] = link
-        if zc:
-            # my send planes ARE the neighbours' receive planes: [through my low face | through my high face] on this side
-            # is [its high-face input | its low-face input] on the other, the layout of its receive buffer
-            self._connector.resolve(self)
-            for nid, link in self._links.items():
-                link.send_bufs = [self._connector.send_addr(self, 'dist', nid, par) for par in (0, 1)]
-        for nid in sorted(by_neighbour):
-            link, faces = self._links[nid], self._links[nid].faces
-            link.send_buf, link.recv_buf = link.send_bufs[0], link.recv_bufs[0]
-            for par in (0, 1):
-                for k, face in enumerate(faces):                       # my send order: low, high
-                    send[par][face] = link.send_bufs[par] + k * n * isz
-                for k, face in enumerate(reversed(faces)):             # the neighbour's send order seen from here
-                    recv[par][face] = link.recv_bufs[par] + k * n * isz
-            for face in faces:            # pieces are posted in this order on both sides: my low <-> its high first
-                self._xface_routes.append((nid, face))
-            link.kernels = {}
-            for mode in ('push', 'pull'):
-                for copy in (0, 1):
-                    link.kernels[(mode, copy)] = ([], [], n * len(faces), n * len(faces))
-        self._xface = xface.XFaceHalo(self.backend, self.module, self._sim.grid, self._desc, send, recv, shared=zc)
-        lat = list(reversed(self._lat_size))
-        # several launches per step pay off where the transfer is slow (another process / GPU: a connector that can be
-        # called in the middle of a step); runners stepped in lock-step by one Python process are bound by that process
-        # instead: one chunk (profiles/r03/xface_overlap_schemes.jsonl)
-        self._xchunks = xface.ChunkPlan(lat[2] - 2, self._fused[2],
-                                        None if getattr(self._connector, 'mid_step', False) else 1)
+    _links = property(lambda self: self._halo.links)                  # populations: {neighbour id: Link}
+    _macro_links = property(lambda self: self._halo.macro_links)      # fields of the non-local models
+    _xface = property(lambda self: self._halo.xface)                  # xface.XFaceHalo of a FaceBufferHalo, else None
+    _nnx = property(lambda self: self._halo.nnx)                      # xface.NNPlanes of a PlaneHalo, else None
+    _xface_routes = property(lambda self: self._halo.routes)
+    _xchunks = property(lambda self: self._halo.chunks)
 
     def xface_pieces(self, pos):
-        """[(neighbour id, send address, receive address, elements)] of batch `pos` of the step just enqueued: for every
-        connected face (send side: my faces low, high; the receive side of the same neighbour takes them as its high, low)
-        the runs of z-planes the chunks swept so far have completed."""
-        x, isz = self._xface, np.dtype(self.float).itemsize
-        par = self._xface_parity
-        out = []
-        # sends in my face order; receives of one neighbour in the order IT sends: its low face (= my high) first
-        by_n = {}
-        for nid, face in self._xface_routes:
-            by_n.setdefault(nid, []).append(face)
-        for nid in sorted(by_n):
-            s_faces = sorted(by_n[nid])
-            r_faces = list(reversed(s_faces))
-            for sf, rf in zip(s_faces, r_faces):
-                for p0, p1 in self._xchunks.batches[self._xface_kind][pos]:
-                    off, cnt = p0 * x.plane * isz, (p1 - p0) * x.plane
-                    out.append((nid, x.send[par][sf] + off, x.recv[par][rf] + off, cnt))
-        return out
-
-    def _reset_xface(self):
-        """Whatever state was just set up from the host (initial conditions, a checkpoint, a debug write): the arrays
-        count, nothing that crossed the x faces before does."""
-        if self._xface is not None:
-            self.backend.sync_stream(*self._all_streams())
-            self._connector.quiesce(self)       # peer transport: the neighbours write into these buffers themselves
-            self._xface.reset(self._calc_stream)
-            it = self._sim.iteration
-            if self.config.access_pattern == 'AA' and (it & 1):
-                # the next step pulls, and the edge lanes of the fluid-only row kernel take what enters through a
-                # connected x face from the receive buffers alone (slf_row.hip: no pull out of the ghost column): prime
-                # them from the ghost columns of the state just written (a checkpoint taken at an odd iteration)
-                self._xface.prime_pull(self.gpu_dist(0, 0), self._calc_stream, parity=1 - (it & 1))
-            self.backend.sync_stream(self._calc_stream)
-            self._connector.quiesce(self)
-            self.__dict__.pop('_halo_mode', None)
-    
-    def _materialise_halo(self):
-        """x-face buffers: the arrays are stale at the connected faces until the received values are written into
-        them (before anything reads the arrays on the host)."""
-        if self._xface is None or not hasattr(self, '_halo_mode'):
-            return
-        self.backend.sync_stream(*self._all_streams())
-        self._xface.materialise(self.gpu_dist(0, self._halo_copy), self._halo_mode == 'push', self._calc_stream,
-                                parity=self._xface_parity)
-        self.backend.sync_stream(self._calc_stream)
+        """The transfers of batch `pos` of the step just enqueued (halo.FaceBufferHalo.pieces)."""
+        return self._halo.pieces(pos, self._step_parity, self._xface_kind)
 
     def halo_messages(self, kind='dist'):
         """[(neighbour id, send buffer, #send, receive buffer, #recv)] of the exchange that is due now,
         ordered by neighbour id: 'dist' = populations of the step just computed, 'macro' = fields read
         by non-local models."""
-        out = []
-        if kind == 'dist':
-            for nid in sorted(self._links):
-                link = self._links[nid]
-                k = link.kernels[(self._halo_mode, self._halo_copy)]
-                out.append((nid, link.send_buf, k[2], link.recv_buf, k[3]))
-        else:
-            for nid in sorted(self._macro_links):
-                link = self._macro_links[nid]
-                out.append((nid, link.send_buf, link.n_send, link.recv_buf, link.n_recv))
-        return out
+        return self._halo.messages(kind, self._step_parity)
 
     # ------------------------------------------------------------------ kernels
     def _prepare_compute_kernels(self):
@@ -666,15 +468,13 @@ class SubdomainRunner(object):
             if plan is not None:
                 self._set_step_state(it)
                 plan.run(it)
-                if self._xface is not None:
-                    self._xface._bound = None       # the plan set the module's face buffers itself
+                self._halo.unbind()         # the plan set the module's face buffers itself
                 self._sim.iteration += 1
                 b.set_iteration(self._sim.iteration)
                 return
         b.set_iteration(it)
         self._program(DirectQueue(b), it, sync_req)
-        if self._xface is not None:
-            self._xface._bound = None
+        self._halo.unbind()
         self._sim.iteration += 1
         b.set_iteration(self._sim.iteration)
 
@@ -729,14 +529,16 @@ class SubdomainRunner(object):
         kernels = self._kernels_full if sync_req else self._kernels_none
         return kernels.primary if (it & 1) == 0 else kernels.secondary
 
+    _step_parity = None       # of the step last enqueued; None: none since the state was written from the host
+
     def _set_step_state(self, it):
         """What the rest of the runner reads about the step being enqueued (halo_messages, xface_pieces, materialise)."""
-        aa = self.config.access_pattern == 'AA'
-        self._halo_mode = 'pull' if (aa and (it & 1) == 0) else 'push'
-        self._halo_copy = 0 if aa else 1 - (it & 1)
-        if self._xface is not None:
-            self._xface_parity = it & 1
-            self._xface_kind = 'own' if (aa and (it & 1) == 0) else 'push'
+        self._step_parity = it & 1
+
+    # in place the even steps pull, every other step pushes; the copy of the arrays the step writes; its z-chunk batches
+    _step_pulls = property(lambda self: self.config.access_pattern == 'AA' and self._step_parity == 0)
+    _step_copy = property(lambda self: 0 if self.config.access_pattern == 'AA' else 1 - self._step_parity)
+    _xface_kind = property(lambda self: 'own' if self._step_pulls else 'push')
 
     def _program(self, q, it, sync_req):
         """One step of a runner that owns its process (reference subdomain_runner.py:960-1058): macro pass of the
@@ -748,7 +550,7 @@ class SubdomainRunner(object):
 
     def _neighbour_events(self, group, name, parity):
         """Events `name` of parity `parity` of the runners this one exchanges halos with (same-process groups)."""
-        ids = set(self._links) | set(getattr(self, '_macro_links', {}))
+        ids = set(self._links) | set(self._macro_links)
         return [group.by_id[nid]._pev[parity][name] for nid in sorted(ids) if nid in group.by_id]
 
     def _program_macro(self, q, it, group=None, sync_req=False):
@@ -833,9 +635,7 @@ class SubdomainRunner(object):
         if timed:
             prof.record_gpu_start(tp, sh)
         for nid in sorted(links):
-            link = links[nid]
-            packs = link.kernels[(self._halo_mode, self._halo_copy)][0] if kind == 'dist' else link.packs[it & 1]
-            for pack in packs:
+            for pack in links[nid].packs[it & 1]:
                 q.launch(pack, None, sh)
         if timed:
             prof.record_gpu_end(tp, sh)
@@ -855,7 +655,7 @@ class SubdomainRunner(object):
         if timed:
             prof.record_gpu_start(TimeProfile.DISTRIB, sh)
         for nid in sorted(self._links):
-            for unpack in self._links[nid].kernels[(self._halo_mode, self._halo_copy)][1]:
+            for unpack in self._links[nid].unpacks[it & 1]:
                 q.launch(unpack, None, sh)
         if timed:
             prof.record_gpu_end(TimeProfile.DISTRIB, sh)
@@ -948,7 +748,7 @@ class SubdomainRunner(object):
         """Distributions as [Q, (nz,) ny, arr_nx] (reference subdomain_runner.py:1363-1381); with indirect
         addressing the slots are scattered back to their nodes (inactive nodes: 0)."""
         self.backend.sync_stream(*self._all_streams())
-        self._materialise_halo()
+        self._halo.materialise()
         if copy is None:
             copy = 0 if not self._gpu_grids_secondary else (self._sim.iteration & 1)
         raw = np.zeros((self._sim.grid.Q, self._dist_stride), dtype=self.float)
@@ -975,7 +775,7 @@ class SubdomainRunner(object):
         self.backend.to_buf(self.gpu_dist(grid_num, copy), raw)
         if isinstance(getattr(self, '_resident', None), dict):
             self._resident['equalised'] = False      # the scratch copies of the resident launches no longer agree with the arrays
-        self._reset_xface()
+        self._halo.reset()
 
     def _debug_global_idx_to_tuple(self, gi):
         dist_num = gi // self._get_nodes()
@@ -1063,7 +863,7 @@ class SubdomainRunner(object):
             self.restore_checkpoint(fname)
         if getattr(cfg, 'debug_dump_node_type_map', False) and self._output is not None:
             self._output.dump_node_type(self._subdomain._type_vis_map)
-        self._reset_xface()
+        self._halo.reset()
         self._sim.before_main_loop(self)
         self.backend.sync_stream(self._calc_stream)
         self.num_fluid_nodes = self._subdomain.num_fluid_nodes
@@ -1335,7 +1135,7 @@ class SubdomainRunner(object):
         (sim.rho, sim.v) stay valid."""
         self.backend.sync_stream(*self._all_streams())
         self._kernels_full = self._kernels_none = self._pbc_kernels = None
-        self._links, self._macro_links = {}, {}
+        self._halo = halo.Halo()
         if self._connector is not None:
             self._connector.release(self)
         self.backend.close()
@@ -1379,199 +1179,15 @@ class NNSubdomainRunner(SubdomainRunner):
         ShanChenPrepareMacroFields -> ApplyMacroPeriodicBoundaryConditions (rho, phi)
         -> ShanChenCollideAndPropagate0, 1 -> ApplyPeriodicBoundaryConditions (both lattices)
 
-    Axes wrapped inside the kernels need no ghost fill.  Exchange of the macroscopic fields between
-    *different* subdomains (reference _send_macro/_recv_macro) is not implemented yet: one subdomain."""
+    Axes wrapped inside the kernels need no ghost fill.  Between subdomains the fields travel like the populations,
+    in an exchange of their own in front of the sweep (reference _send_macro/_recv_macro; sailfish_amd/halo.py)."""
 
     has_macro_exchange = True
-
-    # -- 1-D decompositions along x of the binary model: the populations of both lattices and the densities cross the
-    # -- faces through dense planes the two kernels of a step write / read themselves (xface.NNPlanes)
-    _nnx = None
-
-    def _nn_x_faces_only(self):
-        if not getattr(self.config, 'hip_xface', True) or self.dim != 3 or len(self._sim.grids) not in (1, 2) or \
-                not getattr(self.backend, 'supports_xface_planes', False):
-            return False
-        if not xface.supported_nn(self._sim.grid, self._desc, self.indirect):
-            return False
-        # (An edge node in a row next to a y / z face that is not wrapped inside the kernels reads ghost-row entries of the
-        # density planes.  They hold what prime() found in the neighbour's ghost row -- the +inf every field is created
-        # with outside the lattice, make_scalar_field -- which is what the ghost COLUMN of such a row holds as well: no
-        # node owns that position, so build_macro_links never delivers anything there.  A node that computes a force must
-        # not sit there in either scheme; a wall does not care.)
-        return self._x_slabs_line_up()
-
-    def _init_nn_planes(self):
-        """Per neighbour, kind ('dist': both lattices, 'macro': rho and phi) and step parity one send and one receive
-        buffer, [through my low face | through my high face] as in _init_xface_halo.  The links carry no pack / unpack
-        kernels -- the sweeps fill and read the planes -- so the step program of the general case (pack -> exchange ->
-        unpack, per kind) moves them as it stands."""
-        spec = self._spec
-        nnx = xface.NNPlanes(self.backend, self.module, self._sim.grid, self._desc, n_lat=len(self._sim.grids))
-        by_neighbour = {}
-        for face, nid in sorted(spec.connecting_subdomains()):
-            by_neighbour.setdefault(nid, []).append(xface.LOW if face == spec.X_LOW else xface.HIGH)
-        zc = getattr(self._connector, 'zero_copy', False)
-        all_links = {'dist': self._links, 'macro': self._macro_links}
-        for kind in ('dist', 'macro'):
-            n, links = nnx.count[kind], all_links[kind]
-            for nid in sorted(by_neighbour):
-                link = subdomain_connection.HaloLink(nid)
-                link.faces = sorted(by_neighbour[nid])
-                link.n_send = link.n_recv = n * len(link.faces)
-                if zc:
-                    link.recv_bufs = [self._connector.alloc_recv(self, kind, nid, par, link.n_recv, self.float) for par in (0, 1)]
-                else:
-                    link.send_bufs = [self._connector.alloc_buffer(self, link.n_send, self.float) for _ in (0, 1)]
-                    link.recv_bufs = [self._connector.alloc_buffer(self, link.n_recv, self.float) for _ in (0, 1)]
-                links[nid] = link
-            if zc:
-                self._connector.resolve(self)        # collective: once per kind, in this order, on every rank
-                for nid, link in links.items():
-                    link.send_bufs = [self._connector.send_addr(self, kind, nid, par) for par in (0, 1)]
-            for nid, link in links.items():
-                link.send_buf, link.recv_buf = link.send_bufs[0], link.recv_bufs[0]
-                if kind == 'dist':
-                    link.kernels = dict(((mode, copy), ([], [], link.n_send, link.n_recv))
-                                        for mode in ('push', 'pull') for copy in (0, 1))
-                else:
-                    link.packs, link.unpacks = [[], []], [[], []]
-        self._nnx = nnx
-        nnx.shared = bool(zc)
-        self.config.logger.debug('subdomain %d: Shan-Chen model over x-face planes (%s)' % (
-            spec.id, 'the neighbours\' memory mapped here' if zc else type(self._connector).__name__))
-        for kind in all_links:
-            for nid in all_links[kind]:
-                self._nnx_place(kind, nid)
-        nnx.reset()
-
-    def _nnx_place(self, kind, nid):
-        """The face addresses inside the buffers of the link to `nid` (again after a buffer of the link was replaced)."""
-        nnx = self._nnx
-        link = (self._links if kind == 'dist' else self._macro_links)[nid]
-        step = nnx.count[kind] * nnx.isz
-        for par in (0, 1):
-            for k, face in enumerate(link.faces):                     # my send order: low, high
-                nnx.send[kind][par][face] = link.send_bufs[par] + k * step
-            for k, face in enumerate(reversed(link.faces)):           # the neighbour's send order seen from here
-                nnx.recv[kind][par][face] = link.recv_bufs[par] + k * step
 
     def _nnx_serial(self, group):
         """Stepped by a group that runs every sweep of its subdomains on ONE stream, planes shared with the neighbours: the
         order of that stream is all the order the planes need (controller.LocalGroup._serialise_sweeps)."""
         return self._nnx is not None and group is not None and getattr(group, 'single_calc_stream', False) and self._nnx.shared
-
-    def halo_messages(self, kind='dist'):
-        if self._nnx is None:
-            return SubdomainRunner.halo_messages(self, kind)
-        par = self._nnx_parity
-        links = self._links if kind == 'dist' else self._macro_links
-        return [(nid, links[nid].send_bufs[par], links[nid].n_send, links[nid].recv_bufs[par], links[nid].n_recv)
-                for nid in sorted(links)]
-
-    def _set_step_state(self, it):
-        SubdomainRunner._set_step_state(self, it)
-        self._nnx_parity = it & 1
-
-    def _reset_xface(self):
-        if self._nnx is None:
-            return SubdomainRunner._reset_xface(self)
-        self.backend.sync_stream(*self._all_streams())
-        self._connector.quiesce(self)       # zero-copy transports: the neighbours write into these planes themselves
-        self._nnx.reset(self._calc_stream)
-        self.backend.sync_stream(self._calc_stream)
-        self._connector.quiesce(self)       # ... and I into theirs: everybody has cleared before anybody fills
-        self._nnx_prime()
-        group = getattr(self, '_group', None)
-        if group is not None and self._nnx.shared:
-            # subdomains of one process reset one at a time: what the neighbours had filled in my planes went with the
-            # clearing above
-            for r in group.runners:
-                if r is not self and getattr(r, '_nnx', None) is not None:
-                    r._nnx_prime()
-        self._connector.quiesce(self)
-        self.__dict__.pop('_halo_mode', None)
-
-    def _nnx_prime(self):
-        """The density planes I send, from the fields as they are on the device now (xface.NNPlanes.prime)."""
-        fields = [self.gpu_field(fp.buffer) for fp in self._sim._scalar_fields if fp.abstract.need_nn]
-        self._nnx.prime(fields, self._calc_stream)
-        if self.config.access_pattern == 'AA':
-            self._nnx.prime_own([self.gpu_dist(g, 0) for g in range(self._nnx.n_lat)], self._calc_stream)
-        self.backend.sync_stream(self._calc_stream)
-
-    def _materialise_halo(self):
-        if self._nnx is None:
-            return SubdomainRunner._materialise_halo(self)
-        if not hasattr(self, '_halo_mode'):
-            return
-        self.backend.sync_stream(*self._all_streams())
-        self._nnx.materialise([self.gpu_dist(g, self._halo_copy) for g in range(self._nnx.n_lat)], self._halo_mode == 'push', self._calc_stream,
-                              self._nnx_parity)
-        self.backend.sync_stream(self._calc_stream)
-
-    def _init_halo(self):
-        """Population halo as in the base class (all lattices), plus the exchange of the macroscopic
-        fields the non-local force reads at neighbouring nodes (reference _init_interblock_kernels /
-        _send_macro / _recv_macro, subdomain_runner.py:1907-2100)."""
-        if self._all_specs is not None and len(self._all_specs) >= 2 and self._nn_x_faces_only():
-            self._links, self._macro_links, self._ev_halo = {}, {}, None
-            if self._connector is None:
-                from sailfish_amd.connector import LocalConnector
-                self._connector = LocalConnector()
-            return self._init_nn_planes()
-        SubdomainRunner._init_halo(self)
-        if self._all_specs is None or len(self._all_specs) < 2:
-            return
-        cfg = self.config
-        arr = list(reversed(self._physical_size))
-        dim = self.dim
-
-        def fused_of(spec):
-            return [int(bool(spec._periodicity[a]) and getattr(cfg, 'hip_fused_periodic', True)) for a in range(dim)]
-
-        links = subdomain_connection.build_macro_links(self._spec, self._all_specs, self._global_size,
-                                                       self._global_periodic, arr, fused_of)
-        b = self.backend
-        fields = [self.gpu_field(fp.buffer) for fp in self._sim._scalar_fields if fp.abstract.need_nn]
-        isz = np.dtype(self.float).itemsize
-        zc = getattr(self._connector, 'zero_copy', False)
-        todo = []
-        for nid in sorted(links):
-            link = links[nid]
-            ns, nr = len(link.send), len(link.recv)
-            if ns == 0 and nr == 0:
-                continue
-            link.n_send, link.n_recv = ns * len(fields), nr * len(fields)
-            if zc:          # the neighbour's receive buffers mapped here, two sets by step parity (connector.PeerConnector)
-                link.recv_bufs = [self._connector.alloc_recv(self, 'macro', nid, par, link.n_recv, self.float) for par in (0, 1)]
-            else:
-                link.send_buf = self._connector.alloc_buffer(self, link.n_send, self.float)
-                link.recv_buf = self._connector.alloc_buffer(self, link.n_recv, self.float)
-                link.send_bufs, link.recv_bufs = [link.send_buf] * 2, [link.recv_buf] * 2
-            todo.append((nid, link, ns, nr))
-        if zc:
-            self._connector.resolve(self)
-        for nid, link, ns, nr in todo:
-            if zc:
-                link.send_bufs = [self._connector.send_addr(self, 'macro', nid, par) for par in (0, 1)]
-                link.send_buf, link.recv_buf = link.send_bufs[0], link.recv_bufs[0]
-            g_s = b.alloc_buf(like=link.send) if ns else 0
-            g_r = b.alloc_buf(like=link.recv) if nr else 0
-            # [parity of the step] -> kernels
-            link.packs = [[self.get_kernel('CollectSparseData', [g_s, f, link.send_bufs[par] + i * ns * isz, ns], 'PPPi')
-                           for i, f in enumerate(fields)] if ns else [] for par in (0, 1)]
-            link.unpacks = [[self.get_kernel('DistributeSparseData', [g_r, f, link.recv_bufs[par] + i * nr * isz, nr], 'PPPi')
-                             for i, f in enumerate(fields)] if nr else [] for par in (0, 1)]
-            self._macro_links[nid] = link
-
-    def _prepare_compute_kernels(self):
-        self._kernels_full = self._sim.get_compute_kernels(self, True, True)
-        self._kernels_none = self._sim.get_compute_kernels(self, False, True)
-        self._pbc_kernels = self._sim.get_pbc_kernels(self)
-        self._pbc_axes = [a for a in range(self.dim) if self._local_periodic()[a] and not self._fused[a]]
-        self._regions = self._make_regions()
-        self._kernels_prepared = True
 
     def _enqueue_plain_step(self, it):
         b = self.backend
@@ -1654,6 +1270,3 @@ class NNSubdomainRunner(SubdomainRunner):
         if self._nnx_serial(getattr(self, '_group', None)):
             return
         SubdomainRunner._program_back(self, q, it)
-
-    def _debug_get_dist(self, output=True, grid_num=0, copy=None):
-        return SubdomainRunner._debug_get_dist(self, output, grid_num, copy)

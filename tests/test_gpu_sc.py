@@ -258,7 +258,9 @@ def test_sc_x_slabs_through_planes(size, nsub, precision, potential, pattern, mo
     tol = dict(rtol=0, atol=0) if potential == 'linear' else dict(rtol=2e-6, atol=1e-7)      # expf: the device's own
     for r, o in zip(ctrl.runners, og.subs):
         assert r._nnx is not None and r._nnx.shared == (mode != 'copies')
-        assert not r._links[sorted(r._links)[0]].kernels[('push', 0)][0]        # nothing is packed
+        assert r._links and r._macro_links
+        for link in list(r._links.values()) + list(r._macro_links.values()):       # nothing is packed or unpacked
+            assert link.packs == [[], []] and link.unpacks == [[], []]
         if potential == 'linear':
             assert np.array_equal(r._sim.rho, o.real(o.rho)) and np.array_equal(r._sim.phi, o.real(o.phi))
         else:
