@@ -37,7 +37,8 @@ typedef struct slf_kernel slf_kernel;
 enum { SLF_OK = 0, SLF_ERR_INVALID = 1, SLF_ERR_HIP = 2, SLF_ERR_UNSUPPORTED = 3, SLF_ERR_NOT_FOUND = 4 };
 
 enum { SLF_D2Q9 = 0, SLF_D3Q19 = 1 };
-enum { SLF_BGK = 0, SLF_MRT = 1 };
+/* SLF_ELBM: the entropic collision (--model=elbm; reference templates/entropic.mako, relaxation.mako:56-97). */
+enum { SLF_BGK = 0, SLF_MRT = 1, SLF_ELBM = 2 };
 enum { SLF_AB = 0, SLF_AA = 1 };
 /* density model = the value of slf_module_desc::incompressible (reference sym.py:573-661, sym_equilibrium.py:100-118):
  * compressible (rho0 = rho), --incompressible (rho0 = 1), --minimize_roundoff (the arrays hold f_i - w_i, the density
@@ -101,7 +102,7 @@ enum {
 typedef struct slf_module_desc {
   uint32_t struct_size;        /* sizeof(slf_module_desc), ABI check */
   int32_t lattice;             /* SLF_D2Q9 | SLF_D3Q19            (--grid) */
-  int32_t model;               /* SLF_BGK | SLF_MRT               (--model) */
+  int32_t model;               /* SLF_BGK | SLF_MRT | SLF_ELBM    (--model) */
   int32_t precision;           /* 4 (single) | 8 (double)          (--precision) */
   int32_t access_pattern;      /* SLF_AB | SLF_AA                  (--access_pattern) */
   int32_t lat_nx, lat_ny, lat_nz; /* logical size incl. the ghost envelope; lat_nz = 1 in 2-D */
@@ -154,6 +155,18 @@ typedef struct slf_module_desc {
   int32_t regularized;
   int32_t subgrid;
   double smagorinsky_const;
+  /* model = SLF_ELBM (reference lb_single.py:31-69): f_i += alpha beta (feq_i - f_i) with beta = 1 / (2 visc / cs^2 + 1)
+   * and alpha from the entropy equality H(f + alpha (feq - f)) = H(f): 2 where max_i |feq_i / f_i - 1| < 1e-6, the
+   * series of PRL 97, 010201 below 0.01, Newton's method otherwise.  entropic_equilibrium (--entropic_equilibrium): the
+   * collision's feq is the product form (sym_equilibrium.elbm_equilibrium / elbm_d3q19_equilibrium at order 8) instead of
+   * the BGK polynomial; boundary conditions, initial conditions and output keep the polynomial, as in the reference.
+   * entropy_tolerance (> 0; the reference's defaults are 1e-6 single, 1e-10 double) and alpha_tolerance (1e-10) end the
+   * Newton iteration.  Single-fluid modules, compressible density model (incompressible with the polynomial equilibrium
+   * only), no body force, no regularized / subgrid; served by the per-node kernels.  A node whose iteration does not
+   * converge (the reference's die()) keeps its populations and raises the word slf_module_poll_invalid() reads. */
+  int32_t entropic_equilibrium;
+  double entropy_tolerance;
+  double alpha_tolerance;
 } slf_module_desc;
 
 /* Region of the lattice a sweep launch covers (replaces the reference's
@@ -365,6 +378,10 @@ int slf_module_classify_rows(slf_module* m, const void* map_dptr, slf_stream* st
  * 'i' arguments, base < 2^32; at most 12 directions per launch -- the mask travels to the kernel as an ordered list
  * of 5-bit entries; a face of D3Q19 carries 5, more is SLF_ERR_INVALID), plus "ComputeMacroFields"
  * (rho / v of the current state, arguments as CollideAndPropagate).
+ * In a SLF_ELBM module CollideAndPropagate takes one optional TRAILING pointer, the alpha field (dense, like rho;
+ * reference LBEntropicFluidSim, lb_single.py:129-133: after the options word): the Newton start value of every node is
+ * read from it and the alpha of every wet node is stored into it at every step; without it (or with NULL) the iteration
+ * starts from 2 and nothing is stored.  Fill it with 2 before the first step.
  * The reference's own face kernels are served under their names AND argument lists as well (a host that binds the
  * reference's _init_collect_kernels / _init_distrib_kernels, subdomain_runner.py:1160-1290, needs no special case):
  * "CollectContinuousData" / "DistributeContinuousData" / "CollectContinuousDataWithSwap" /

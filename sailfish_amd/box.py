@@ -22,7 +22,8 @@ def padded_nx(lat_nx, alignment=32):
 def make_box_desc(grid, size, model='bgk', precision='single', access_pattern='AA', visc=1.0 / 6.0,
                   periodic_fused=(0, 0, 0), fluid_only=True, accel=None, incompressible=False,
                   relaxation_enabled=True, type_kind=None, node_params=None, nt_bits=None, use_link_tags=True,
-                  alignment=32, dist_pad=None, regularized=False, subgrid=None, smagorinsky_const=0.1):
+                  alignment=32, dist_pad=None, regularized=False, subgrid=None, smagorinsky_const=0.1,
+                  entropic_equilibrium=False, entropy_tolerance=0.0, alpha_tolerance=1e-10):
     """size = (nx, ny[, nz]) real nodes; a ghost envelope of 1 is added."""
     dim = grid.dim
     assert len(size) == dim
@@ -53,13 +54,21 @@ def make_box_desc(grid, size, model='bgk', precision='single', access_pattern='A
     if regularized or subgrid:
         kw.update(regularized=int(bool(regularized)), smagorinsky_const=float(smagorinsky_const),
                   subgrid=hipabi.SLF_SUBGRID_LES_SMAGORINSKY if subgrid else hipabi.SLF_SUBGRID_NONE)
+    if model == 'elbm':
+        from sailfish_amd.lb_single import LBFluidSim
+        kw.update(LBFluidSim.elbm_desc(grid, visc, precision, entropic_equilibrium, entropy_tolerance, alpha_tolerance))
+    elif entropic_equilibrium:
+        kw['entropic_equilibrium'] = 1        # (refused by the library: it belongs to model = elbm)
     return hipabi.make_desc(**kw)
 
 
 class BoxSim(object):
     """One subdomain, no neighbours, on one GPU through the backend interface."""
 
-    def __init__(self, backend, desc, periodic=(False, False, False), node_map=None, tune_placement=False):
+    def __init__(self, backend, desc, periodic=(False, False, False), node_map=None, tune_placement=False,
+                 alpha_field=None):
+        """alpha_field (entropic modules): True = the alpha array exists (filled with 2) and is the trailing argument of
+        CollideAndPropagate; None = as the module's model says; False = no array (every Newton iteration starts from 2)."""
         self.backend = backend
         self.desc = desc
         self.dim = 2 if desc.lattice == hipabi.SLF_D2Q9 else 3
@@ -106,6 +115,10 @@ class BoxSim(object):
         foff = b.dist_align_offset(self.dtype().itemsize)      # x = 1 of every field row on a 128-byte line as well
         self.gpu_rho = b.alloc_buf(like=self.rho, align_offset=foff)
         self.gpu_v = [b.alloc_buf(like=a, align_offset=foff) for a in self.v]
+        self.alpha = self.gpu_alpha = None
+        if alpha_field or (alpha_field is None and desc.model == hipabi.SLF_ELBM):
+            self.alpha = np.full(self.shape, 2.0, dtype=self.dtype)
+            self.gpu_alpha = b.alloc_buf(like=self.alpha, align_offset=foff)
         self.gpu_map = 0
         self.node_map = None
         if node_map is not None:
@@ -132,7 +145,11 @@ class BoxSim(object):
             pairs = [(0, 0)] if self.aa else [(0, 1), (1, 0)]
             for i, o in pairs:
                 args = [self.gpu_map, self.gpu_dist[i], self.gpu_dist[o], self.gpu_rho] + self.gpu_v + [save]
-                ks.append(b.get_kernel(m, 'CollideAndPropagate', (64,), args, sig, needs_iteration=self.aa))
+                csig = sig
+                if self.gpu_alpha is not None:
+                    args.append(self.gpu_alpha)
+                    csig += 'P'
+                ks.append(b.get_kernel(m, 'CollideAndPropagate', (64,), args, csig, needs_iteration=self.aa))
             self.k_sweep[save] = ks
         self.k_init = []
         for dbuf in self.gpu_dist:
@@ -190,7 +207,8 @@ class BoxSim(object):
         """Frees the device memory of this simulation."""
         self.sync()
         b = self.backend
-        for addr in list(self.gpu_dist) + [self.gpu_rho] + list(self.gpu_v) + ([self.gpu_map] if self.gpu_map else []):
+        for addr in list(self.gpu_dist) + [self.gpu_rho] + list(self.gpu_v) + ([self.gpu_map] if self.gpu_map else []) + \
+                ([self.gpu_alpha] if self.gpu_alpha is not None else []):
             b.free_buf(addr)
         self.gpu_dist = []
         # drop the kernel objects: the backend's registry of iteration-dependent kernels holds them weakly
@@ -204,6 +222,16 @@ class BoxSim(object):
         for g in self.gpu_v:
             self.backend.from_buf(g)
         return self.rho, self.v
+
+    def fetch_alpha(self):
+        self.sync()
+        self.backend.from_buf(self.gpu_alpha)
+        return self.alpha
+
+    def set_alpha(self, alpha):
+        """alpha over the real nodes (or a scalar)."""
+        self.real_view(self.alpha)[...] = alpha
+        self.backend.to_buf(self.gpu_alpha)
 
     def current_dist_index(self):
         return 0 if self.aa else (self.iteration & 1)

@@ -112,6 +112,7 @@ struct slf_kernel {
   uint32_t iteration;
   bool bound;
   bool sc_local_velocity;   // ShanChenPrepareDensities / ShanChenCollideAndPropagateFusedV
+  bool alpha_arg = false;   // CollideAndPropagate of an entropic module: the last pointer is the alpha field
 };
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
@@ -949,7 +950,8 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
   if (!ctx || !d || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   if (d->struct_size != sizeof(slf_module_desc)) return fail(SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
   if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19) return fail(SLF_ERR_UNSUPPORTED, "unsupported lattice");
-  if (d->model != SLF_BGK && d->model != SLF_MRT) return fail(SLF_ERR_UNSUPPORTED, "unsupported collision model");
+  if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
+    return fail(SLF_ERR_UNSUPPORTED, "unsupported collision model");
   if (d->precision != 4 && d->precision != 8) return fail(SLF_ERR_UNSUPPORTED, "precision must be 4 or 8");
   if (d->access_pattern != SLF_AB && d->access_pattern != SLF_AA)
     return fail(SLF_ERR_UNSUPPORTED, "unsupported access pattern");
@@ -1080,6 +1082,32 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
       return fail(SLF_ERR_INVALID, "subgrid = les-smagorinsky needs smagorinsky_const > 0");
     }
     g.variant = 0;       // per-node kernels: the tuned / whole-row ones implement the plain collision
+  }
+  ph.entropic_equilibrium = d->entropic_equilibrium != 0;
+  ph.entropy_tolerance = d->entropy_tolerance;
+  ph.alpha_tolerance = d->alpha_tolerance;
+  if (ph.entropic_equilibrium && d->model != SLF_ELBM) {
+    delete m;
+    return fail(SLF_ERR_INVALID, "entropic_equilibrium needs model = SLF_ELBM");
+  }
+  if (d->model == SLF_ELBM) {
+    // what ELBM_relaxate (relaxation.mako:56-97) was written for, and what this library has fixtures for (regularized /
+    // subgrid, the options of the BGK preamble it never runs, were refused above)
+    const char* why = nullptr;
+    bool rates = false;            // a host that filled in MRT relaxation rates expects them to act
+    for (int i = 0; i < 27; i++) rates = rates || d->mrt_rates[i] != 0.0;
+    if (rates) why = "elbm: MRT relaxation rates are set (mrt_rates must be all zero: the entropic collision has one rate)";
+    else if (d->simtype != SLF_SIM_LBM) why = "elbm: single-fluid modules only (the Shan-Chen models use the BGK collision)";
+    else if (d->incompressible == SLF_DENSITY_ROUNDOFF) why = "elbm: minimize_roundoff stores f_i - w_i, the entropy needs the populations themselves";
+    else if (d->incompressible == SLF_DENSITY_INCOMPRESSIBLE && ph.entropic_equilibrium)
+      why = "elbm: the product-form equilibrium (entropic_equilibrium) is compressible; not with the incompressible density model";
+    else if (d->has_force) why = "elbm: body forces under the entropic collision are not served";
+    else if (!(d->entropy_tolerance > 0.0) || !(d->alpha_tolerance >= 0.0)) why = "elbm: entropy_tolerance must be > 0 and alpha_tolerance >= 0";
+    if (why) {
+      delete m;
+      return fail(SLF_ERR_UNSUPPORTED, why);
+    }
+    g.variant = 0;       // per-node kernels only
   }
   if (d->incompressible == SLF_DENSITY_ROUNDOFF) {
     // --minimize_roundoff: "BGK-like models" in the reference (lb_base.py:72-76); here BGK, single fluid, fluid and
@@ -1438,7 +1466,7 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
     // density formulation, node kinds whose code touches nothing but the node's own populations
     const slf::Geometry& g = m->geo;
     if (g.dim != 2 || m->sc.enabled || g.indirect || m->phys.incompressible == SLF_DENSITY_ROUNDOFF || m->phys.regularized ||
-        m->phys.subgrid)
+        m->phys.subgrid || m->sel.model == SLF_ELBM)
       return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: 2-D single-fluid modules with direct addressing and the "
                                        "standard density formulation only");
     if (g.axis_mode[0] == 1 || g.axis_mode[1] == 1)
@@ -1499,7 +1527,7 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
   size_t want_p = 0, want_i = 0;
   switch (k->kind) {
     case KK_COLLIDE_AND_PROPAGATE:
-    case KK_COMPUTE_MACRO: want_p = 4 + dim; want_i = 1; break;   // map, dist_in, dist_out, rho, v.., options
+    case KK_COMPUTE_MACRO: want_p = 4 + dim; want_i = 1; break;   // map, dist_in, dist_out, rho, v.., options [, alpha]
     case KK_SET_INITIAL_CONDITIONS: want_p = 3 + dim; want_i = 0; break;  // dist, v.., rho, map
     case KK_PBC:
     case KK_PBC_SWAP:
@@ -1564,12 +1592,20 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
                                k->kind == KK_SC_SWEEP0 || k->kind == KK_SC_SWEEP1 || k->kind == KK_SC_INIT ||
                                k->kind == KK_SCS_MACRO || k->kind == KK_SCS_SWEEP))
     want_p += 1;   // leading `nodes` table (reference _add_indirect_args, subdomain_runner.py:1153-1157)
+  k->alpha_arg = false;
+  if (k->kind == KK_COLLIDE_AND_PROPAGATE && k->mod->sel.model == SLF_ELBM && k->ptrs.size() == want_p + 1 &&
+      fmt[argc - 1] == 'P') {
+    // entropic modules: the alpha field, the LAST argument (reference lb_single.py:129-133: behind the options word)
+    want_p += 1;
+    k->alpha_arg = true;
+  }
   if (k->ptrs.size() != want_p || k->ints.size() != want_i)
     return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature");
   k->needs_iteration = needs_iteration;
   k->bound = true;
   if (k->kind == KK_COLLIDE_AND_PROPAGATE && k->mod->geo.indirect && !k->ptrs.empty() &&
-      k->mod->phys.incompressible != SLF_DENSITY_ROUNDOFF && !k->mod->phys.regularized && !k->mod->phys.subgrid) {
+      k->mod->phys.incompressible != SLF_DENSITY_ROUNDOFF && !k->mod->phys.regularized && !k->mod->phys.subgrid &&
+      k->mod->sel.model != SLF_ELBM) {
     // indirect addressing: the sweep is launched over the slots (slot_sweep_kernel); the slot -> node table of this
     // `nodes` argument is built here, once (a launch may be recorded into a graph, where nothing can be allocated)
     SLF_HIP(hipSetDevice(k->mod->ctx->device));
@@ -1609,6 +1645,7 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       a.node_params = m->node_params;
       a.status = m->status;
       a.options = (uint32_t)k->ints[0];
+      a.alpha = k->alpha_arg ? (void*)k->ptrs.back() : nullptr;
       for (int f = 0; f < 2; f++) {
         a.xsend[f] = m->xsend[f];
         a.xrecv[f] = m->xrecv[f];

@@ -50,6 +50,9 @@ struct Physics {
   // --regularized / --subgrid=les-smagorinsky (slf_module_desc; relaxation_common.mako:166-237): per-node kernels only
   int regularized, subgrid;
   double smagorinsky_const;
+  // --model=elbm (slf_module_desc; templates/entropic.mako): per-node kernels only
+  int entropic_equilibrium;
+  double entropy_tolerance, alpha_tolerance;
 };
 
 struct ShanChen {
@@ -93,6 +96,7 @@ struct SweepArgs {
   const void* xrecv2[2];
   void* msend[2];
   const void* mrecv[2];
+  void* alpha;         // entropic modules: the alpha field (dense, like rho) or NULL
 };
 
 // What slf_module_classify_rows() found in a node map, per 64-node x-segment (= one wavefront of a whole-row

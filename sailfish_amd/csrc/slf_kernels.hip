@@ -24,8 +24,9 @@ namespace slf {
 
 // TURB (--regularized / --subgrid): workgroups of at most 512 threads, i.e. 256 VGPRs -- the non-equilibrium flux tensor on
 // top of the collision does not fit the 128 of a 1024-thread workgroup (76-152 bytes of scratch per lane in the odd step).
+// MODEL = 2 (--model=elbm): the same bound -- f and fneq stay live across the Newton solve.
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false>
-__global__ void __launch_bounds__(TURB ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
+__global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const int gy = p.y0 + (int)blockIdx.y;
   const int gz = (L::dim == 3) ? p.z0 + (int)blockIdx.z : 0;
@@ -358,6 +359,16 @@ static hipError_t launch_sweep4(bool general, const Geometry& g, const Physics& 
   dim3 block(block_x, 1, 1);
   dim3 grid((g.lat_nx - 2 + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
   if (grid.y == 0 || grid.z == 0) return hipSuccess;
+  if constexpr (MODEL == 2) {                 // --model=elbm: per-node kernels only, at most 512 threads per workgroup
+    if (block.x > 512) {
+      block.x = 512;
+      grid.x = (g.lat_nx - 2 + 511) / 512;
+    }
+    if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true>), grid, block, 0, s, p);
+    else if (general) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, false>), grid, block, 0, s, p);
+    return hipGetLastError();
+  }
   if constexpr (MODEL == 0) {
     if (ph.incompressible == SLF_DENSITY_ROUNDOFF) {       // --minimize_roundoff (BGK only; checked at module creation)
       if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true, true>), grid, block, 0, s, p);
@@ -402,6 +413,7 @@ template <class L, class R>
 static hipError_t launch_sweep2(int model, Prop prop, bool general, const Geometry& g, const Physics& ph,
                                 const SweepArgs& a, int y0, int y1, int z0, int z1, int bx, hipStream_t s) {
   if (model == 0) return launch_sweep3<L, R, 0>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
+  if (model == 2) return launch_sweep3<L, R, 2>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
   return launch_sweep3<L, R, 1>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
 }
 

@@ -654,6 +654,186 @@ SLF_D void bgk_relax_turb(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L,
   }
 }
 
+// ---- entropic collision (--model=elbm; reference templates/entropic.mako, relaxation.mako:56-97 ELBM_relaxate) ----
+// f_i += alpha beta (feq_i - f_i), beta = 1 / (2 tau0 + 1), tau0 = visc / cs^2; alpha is the non-trivial root of
+// H(f + alpha fneq) = H(f), H(f) = sum_i f_i (ln f_i - ln w_i) (the entropic weights of D2Q9 and D3Q19 are the lattice
+// weights, sym.py:329, 951-1024).  Three regimes by dev = max_i |fneq_i / f_i| (EntropicRelaxationParam):
+//   dev < 1e-6   alpha = 2 (plain BGK);
+//   dev < 0.01   the series of PRL 97, 010201 (2006) Eq. 12 in a1..a4 (ComputeACoeff, sym.alpha_series);
+//   otherwise    Newton's method on the entropy equality (EstimateAlphaFromEntropy), started from the node's previous
+//                alpha where the module has an alpha array.
+// dev and a1..a4 come out of ONE pass over the populations (a reciprocal and nine operations per direction, no
+// logarithm), so the first two regimes are straight-line code and a wave enters the Newton branch -- the only place
+// that evaluates logarithms and reads the alpha array -- only when one of its lanes needs it.
+template <class R>
+struct ElbmParams {
+  R beta;              // 1 / (2 tau0 + 1)
+  R entropy_tol;       // |H(f + alpha fneq) - H(f)| below this ends the iteration
+  R alpha_tol;         // as does a step of alpha below this
+  int entropic_eq;     // product-form equilibrium (--entropic_equilibrium) instead of the BGK polynomial
+};
+
+SLF_D float slf_log(float x) { return logf(x); }
+SLF_D double slf_log(double x) { return log(x); }
+SLF_D float slf_abs(float x) { return __builtin_fabsf(x); }
+SLF_D double slf_abs(double x) { return __builtin_fabs(x); }
+template <class L, class R>
+struct EntropicWeights {
+  // -ln w_i, rounded once to R (the reference prints the constant into the kernel: entropic.mako:53, 68)
+  static constexpr double ln(double x) {           // constexpr natural logarithm of a weight in (0, 1): atanh series
+    int k = 0;
+    while (x < 0.75) { x *= 2.0; k++; }
+    const double y = (x - 1.0) / (x + 1.0), y2 = y * y;
+    double s = 0.0, t = y;
+    for (int n = 1; n < 60; n += 2) { s += t / n; t *= y2; }
+    return 2.0 * s - k * 0.6931471805599453094;
+  }
+  static constexpr R neg_ln_w(int i) { return (R)(-ln((double)L::wnum(i) / (double)L::wden(i))); }
+};
+
+// fneq_i = feq_i - f_i.  ENTROPIC_EQ = false: the BGK polynomial (feq above); true: the product form --
+// D2Q9: sym_equilibrium.elbm_equilibrium (Europhys. Lett. 63, 798 (2003)): with s_c = sqrt(1 + 3 v_c^2),
+//   feq_i = rho prod_c (2 - s_c) w_i prod_c ((2 v_c + s_c) / (1 - v_c))^e_ic;
+// D3Q19: sym_equilibrium.elbm_d3q19_equilibrium at order 8: feq_i = chi w_i prod_c zeta_c^e_ic.
+template <class L, class R, bool ENTROPIC_EQ>
+SLF_D void elbm_fneq(const R (&f)[L::Q], R rho, bool incompressible, const R (&v)[3], R (&fneq)[L::Q]) {
+  if constexpr (!ENTROPIC_EQ) {
+    const R rho0 = incompressible ? (R)1 : rho;
+    const R u15 = usq15<L, R>(v);
+    static_for<0, L::Q>([&](auto I) { fneq[I] = feq<L, R, I>(rho, rho0, v, u15) - f[I]; });
+  } else {
+    R pref, c[3], ic[3];
+    c[2] = ic[2] = (R)1;
+    if constexpr (L::dim == 2) {
+      pref = rho;
+      static_for<0, 2>([&](auto D) {
+        const R s = slf_sqrt((R)1 + (R)3 * (v[D] * v[D]));
+        pref = pref * ((R)2 - s);
+        c[D] = ((R)2 * v[D] + s) / ((R)1 - v[D]);
+        ic[D] = (R)1 / c[D];
+      });
+    } else {
+      const R x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2];
+      const R q[3] = {x2, y2, z2};
+      const R x4 = x2 * x2, y4 = y2 * y2, z4 = z2 * z2;
+      const R vsq = (x2 + y2) + z2;
+      const R yz = y2 + z2, y2z2 = y2 * z2, y4z4 = y4 + z4;
+      const R o6 = ((x4 * x2 + x4 * yz) + yz * y4z4) + x2 * ((y4 + (R)12 * y2z2) + z4);
+      const R o8 = (((((((R)5 * (x4 * x4) + (R)5 * (y4 * y4)) + (R)4 * (y4 * y2) * z2) + (R)2 * y4 * z4) +
+                      (R)4 * y2 * (z4 * z2)) + (R)5 * (z4 * z4)) + (R)4 * (x4 * x2) * yz) +
+                   ((R)4 * x2 * yz * ((y4 + (R)17 * y2z2) + z4) + (R)2 * x4 * ((y4 + (R)36 * y2z2) + z4));
+      pref = rho * (((((R)1 - (R)1.5 * vsq) + (R)1.125 * (vsq * vsq)) - (R)1.6875 * o6) + (R)0.6328125 * o8);
+      static_for<0, 3>([&](auto D) {
+        constexpr int X = D, Y = (D + 1) % 3, Z = (D + 2) % 3;      // cyclic permutation
+        const R a = v[X], a2 = q[X], b2c2 = q[Y] * q[Z], bpc = q[Y] + q[Z];
+        const R a3 = a2 * a, a4 = a2 * a2, a6 = a4 * a2;
+        R t = ((((R)1 + (R)3 * a) + (R)4.5 * a2) + (R)4.5 * a3) + (R)3.375 * a4;
+        t = t + (R)3.375 * (a4 * a + (R)2 * a * b2c2);
+        t = t + (R)5.0625 * (a6 + (R)4 * a2 * b2c2);
+        t = t + (R)5.0625 * (a * ((a6 + (R)4 * a2 * b2c2) - b2c2 * bpc));
+        t = t + (R)1.8984375 * (a2 * (a6 - (R)8 * b2c2 * bpc));
+        c[D] = t;
+        ic[D] = (R)1 / t;
+      });
+    }
+    static_for<0, L::Q>([&](auto I) {
+      R t = pref * Weights<L, R>::w(I);
+      static_for<0, L::dim>([&](auto D) {
+        constexpr int e = e_comp<L>(I, D);
+        if constexpr (e > 0) t = t * c[D];
+        if constexpr (e < 0) t = t * ic[D];
+      });
+      fneq[I] = t - f[I];
+    });
+  }
+}
+
+// Newton's method on H(f + alpha fneq) = H(f) (EstimateAlphaFromEntropy, entropic.mako:90-143).  false: the reference
+// would die() here (more than 1000 steps, or a final alpha below 1 or not finite).  Every evaluation at an alpha other
+// than 1.1 that is not a number restarts at 1.1 without counting as a step, and the evaluation at 1.1 never restarts, so
+// the loop makes at most 2002 evaluations; one that restarts into 1.1 and steps to a NaN from there would repeat just
+// that until the count runs out, and gives up at once.
+template <class L, class R>
+SLF_D bool elbm_newton(const R (&f)[L::Q], const R (&fneq)[L::Q], const ElbmParams<R>& ep, R& alpha) {
+  R ent = (R)0;
+  static_for<0, L::Q>([&](auto I) {
+    constexpr R nlw = EntropicWeights<L, R>::neg_ln_w(I);
+    ent = ent + f[I] * (slf_log(f[I]) + nlw);
+  });
+  R max_alpha = (R)1000;           // FindMaxAlpha: the largest alpha that keeps every population positive
+  static_for<0, L::Q>([&](auto I) {
+    if (f[I] < (R)0 || fneq[I] < (R)0) {
+      const R m = ((R)0 - f[I]) / fneq[I];
+      max_alpha = m < max_alpha ? m : max_alpha;       // min(): a NaN (0 / 0) leaves max_alpha as it is
+    }
+  });
+  int steps = 0;
+  for (int evals = 0; evals < 2002; evals++) {
+    R ent_ineq = (R)0, dent = (R)0;
+    static_for<0, L::Q>([&](auto I) {
+      const R t = f[I] + alpha * fneq[I];
+      constexpr R nlw = EntropicWeights<L, R>::neg_ln_w(I);
+      const R h = slf_log(t) + nlw;
+      ent_ineq = ent_ineq + t * h;
+      dent = dent + fneq[I] * (h + (R)1);
+    });
+    if (ent_ineq != ent_ineq && alpha != (R)1.1) {
+      alpha = (R)1.1;
+      continue;
+    }
+    const R ent_increase = ent_ineq - ent;
+    if (slf_abs(ent_increase) < ep.entropy_tol) break;
+    R new_alpha = alpha - ent_increase / dent;
+    if (new_alpha > max_alpha) new_alpha = (R)0.5 * (alpha + max_alpha);
+    if (slf_abs(new_alpha - alpha) < ep.alpha_tol) break;
+    if (new_alpha != new_alpha && alpha == (R)1.1) return false;
+    alpha = new_alpha;
+    steps++;
+    if (steps > 1000) return false;
+  }
+  return !(alpha < (R)1) && __builtin_isfinite(alpha);
+}
+
+// alpha_node: the node's entry of the alpha array, or NULL (no array: Newton starts from 2, nothing is stored).
+// false: the solver gave up; the populations are as they came in and nothing was stored.
+template <class L, class R>
+SLF_D bool elbm_relax(R (&f)[L::Q], R rho, const R (&v)[3], bool incompressible, const ElbmParams<R>& ep, R* alpha_node) {
+  R fneq[L::Q];
+  if (ep.entropic_eq) elbm_fneq<L, R, true>(f, rho, incompressible, v, fneq);
+  else elbm_fneq<L, R, false>(f, rho, incompressible, v, fneq);
+  // SmallEquilibriumDeviation + ComputeACoeff in one pass
+  R dev = (R)0, a1 = (R)0, a2 = (R)0, a3 = (R)0, a4 = (R)0;
+  static_for<0, L::Q>([&](auto I) {
+    const R inv = (R)1 / f[I];
+    const R t = fneq[I] * inv;
+    R p = fneq[I] * fneq[I] * inv;
+    const R at = slf_abs(t);
+    dev = at > dev ? at : dev;            // max(): as the reference's, a NaN ratio does not raise dev
+    a1 = a1 + p;
+    p = p * t;
+    a2 = a2 + p;
+    p = p * t;
+    a3 = a3 + p;
+    p = p * t;
+    a4 = a4 + p;
+  });
+  R alpha = (R)2;
+  if (dev >= (R)0.01) {
+    if (alpha_node) alpha = *alpha_node;
+    if (!elbm_newton<L, R>(f, fneq, ep, alpha)) return false;
+  } else if (dev >= (R)1e-6) {
+    // sym.alpha_series() in x_k = a_k / a1 with the factors of ComputeACoeff (1/2, -1/6, 1/12, -1/20)
+    const R i1 = (R)1 / ((R)0.5 * a1);
+    const R x2 = ((R)(-1.0 / 6.0) * a2) * i1, x3 = ((R)(1.0 / 12.0) * a3) * i1, x4 = ((R)(-1.0 / 20.0) * a4) * i1;
+    alpha = ((((((R)2 - (R)4 * x2) + (R)16 * (x2 * x2)) - (R)8 * x3) + (R)80 * (x2 * x3)) - (R)80 * (x2 * x2 * x2)) -
+            (R)16 * x4;
+  }
+  if (alpha_node) *alpha_node = alpha;
+  const R ab = alpha * ep.beta;
+  static_for<0, L::Q>([&](auto I) { f[I] = f[I] + ab * fneq[I]; });
+  return true;
+}
+
 // Number of unknown populations, other than the one along the normal n, with a component along axis d.
 template <class L>
 constexpr int zouhe_count(int n, int d) {

@@ -46,6 +46,10 @@ struct SweepParams {
   // --regularized (bit 0) / --subgrid=les-smagorinsky (bit 1): read by the TURB instantiations of the per-node kernels only
   int turb_flags;
   R turb_visc, turb_c2x36;      // viscosity and 36 C^2 of the subgrid model
+  // --model=elbm: read by the MODEL = 2 instantiations of the per-node kernels only.  alpha: dense field like rho, the
+  // Newton start value of a node and the alpha it ended with; NULL: no alpha array (start from 2, nothing stored)
+  R* alpha;
+  ElbmParams<R> elbm;
 };
 
 
@@ -294,7 +298,22 @@ __device__ __forceinline__ void check_invalid(uint32_t* status, uint32_t options
   }
 }
 
+// The entropic collision of a wet node.  Where the solver gives up (the reference's die(), entropic.mako:123-141) the
+// populations stay unrelaxed and the module's invalid-value word is raised with the node's position -- whatever the
+// options say: the host's next status check ends the run (slf_module_poll_invalid).
+template <class L, class R>
+__device__ __forceinline__ void elbm_collide(const SweepParams<L, R>& p, R (&f)[L::Q], R rho, const R (&v)[3], uint32_t gi) {
+  if (!elbm_relax<L, R>(f, rho, v, p.cp.incompressible != 0, p.elbm, p.alpha ? p.alpha + gi : nullptr)) {
+    if (atomicOr(p.status, 1u) == 0u) {
+      p.status[1] = gi % (uint32_t)p.g.arr_nx;
+      p.status[2] = (gi / (uint32_t)p.g.arr_nx) % (uint32_t)p.g.arr_ny;
+      p.status[3] = gi / (uint32_t)p.g.arr_nxy;
+    }
+  }
+}
+
 // gi: dense node index; si: the node's slot in the distribution arrays (= gi unless INDIRECT).
+// MODEL: 0 BGK, 1 MRT, 2 entropic (slf_node.h elbm_relax; the per-node kernels only).
 // BCL: the module's Geometry::bc_level the instantiation is for (2 = everything; the outflow, do-nothing and full-slip nodes
 // exist at level 2 only, so that the level-1 kernels of the usual wall / inlet / outlet conditions do not carry their code).
 // ROUNDOFF: the --minimize_roundoff formulation (slf_node.h: macro_roundoff, bgk_relax_roundoff): BGK; fluid, full-way
@@ -483,7 +502,9 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     }
     // ---- collision (relaxate, relaxation.mako:196-202: wet nodes only)
     if (wet && p.relaxation_enabled) {
-      if constexpr (MODEL == 0 && TURB) {
+      if constexpr (MODEL == 2) {
+        elbm_collide<L, R>(p, f, rho, v, gi);
+      } else if constexpr (MODEL == 0 && TURB) {
         bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
       } else if constexpr (MODEL == 0) {
         bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
@@ -519,7 +540,8 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
   } else {
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (p.relaxation_enabled) {
-      if constexpr (MODEL == 0 && TURB) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
+      if constexpr (MODEL == 2) elbm_collide<L, R>(p, f, rho, v, gi);
+      else if constexpr (MODEL == 0 && TURB) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
       else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
       else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
     }
@@ -570,6 +592,11 @@ inline SweepParams<L, R> make_params(const Geometry& g, const Physics& ph, const
   p.turb_flags = (ph.regularized ? 1 : 0) | (ph.subgrid ? 2 : 0);
   p.turb_visc = (R)ph.visc;
   p.turb_c2x36 = (R)(36.0 * ph.smagorinsky_const * ph.smagorinsky_const);
+  p.alpha = (R*)a.alpha;
+  p.elbm.beta = (R)1 / ((R)2 * (R)(3.0 * ph.visc) + (R)1);       // tau0 = visc / cs^2 (reference lb_single.py:54-55)
+  p.elbm.entropy_tol = (R)ph.entropy_tolerance;
+  p.elbm.alpha_tol = (R)ph.alpha_tolerance;
+  p.elbm.entropic_eq = ph.entropic_equilibrium;
   p.g = g;
   p.cp.omega = (R)(1.0 / ph.tau);
   for (int k = 0; k < L::Q; k++) p.cp.mrt_s[k] = (R)ph.mrt_rates[k];

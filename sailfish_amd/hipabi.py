@@ -12,7 +12,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 SLF_MAX_NODE_TYPES = 16
 SLF_MAX_Q = 27
 SLF_D2Q9, SLF_D3Q19 = 0, 1
-SLF_BGK, SLF_MRT = 0, 1
+SLF_BGK, SLF_MRT, SLF_ELBM = 0, 1, 2
 SLF_AB, SLF_AA = 0, 1
 SLF_SIM_LBM, SLF_SIM_SHAN_CHEN_BINARY, SLF_SIM_SHAN_CHEN_SINGLE = 0, 1, 2
 (SLF_NK_FLUID, SLF_NK_GHOST, SLF_NK_UNUSED, SLF_NK_PROPAGATION_ONLY, SLF_NK_FULL_BB, SLF_NK_HALF_BB,
@@ -59,6 +59,9 @@ class SlfModuleDesc(Structure):
         ('regularized', c_int32),
         ('subgrid', c_int32),
         ('smagorinsky_const', c_double),
+        ('entropic_equilibrium', c_int32),
+        ('entropy_tolerance', c_double),
+        ('alpha_tolerance', c_double),
     ]
 
 

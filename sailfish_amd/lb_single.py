@@ -10,14 +10,23 @@ from sailfish_amd.lb_base import KernelPair, LBForcedSim, LBSim, ScalarField, Ve
 class LBFluidSim(LBSim):
     """Simulates a single fluid."""
     subdomain_runner = subdomain_runner.SubdomainRunner
+    alpha_output = False
 
     @classmethod
     def add_options(cls, group, dim):
         group.add_argument('--visc', type=float, default=1.0, help='numerical viscosity')
         group.add_argument('--incompressible', action='store_true', default=False,
                            help='use the incompressible model of Luo and He')
-        group.add_argument('--model', help='LB collision model to use', type=str, choices=['bgk', 'mrt'],
+        group.add_argument('--model', help='LB collision model to use', type=str, choices=['bgk', 'mrt', 'elbm'],
                            default='bgk')
+        # the entropic collision (reference lb_single.py:31-50; templates/entropic.mako)
+        group.add_argument('--entropic_equilibrium', action='store_true', default=False,
+                           help='Use the equilibrium in product form instead of the standard LBGK equilibrium.')
+        group.add_argument('--entropy_tolerance', type=float, default=0.0,
+                           help='Entropy changes below this level will be treated as constant. If 0.0, a default value '
+                                'depending on the precision of the simulation is used (1e-6 single, 1e-10 double).')
+        group.add_argument('--alpha_tolerance', type=float, default=1e-10,
+                           help='Alpha value tolerance used to end Newton-Raphson iterations.')
         # the two options of the reference's BGK relaxation preamble (lb_single.py:27-30, 38-42; relaxation_common.mako:166-237)
         group.add_argument('--regularized', action='store_true', default=False,
                            help='Apply the regularization procedure prior to the collision step.')
@@ -35,10 +44,15 @@ class LBFluidSim(LBSim):
         if not self.grid.model_supported(cfg.model):
             raise ValueError('model %s not supported on grid %s' % (cfg.model, self.grid.__name__))
         kw.update(lattice=self.grid.slf_id,
-                  model=hipabi.SLF_MRT if cfg.model == 'mrt' else hipabi.SLF_BGK,
+                  model={'mrt': hipabi.SLF_MRT, 'elbm': hipabi.SLF_ELBM}.get(cfg.model, hipabi.SLF_BGK),
                   tau=sym.relaxation_time(cfg.visc), visc=cfg.visc,
                   mrt_rates=sym.mrt_rates(self.grid, cfg.visc),
                   incompressible=self.density_model(cfg))
+        if getattr(cfg, 'entropic_equilibrium', False) and cfg.model != 'elbm':
+            raise ValueError('--entropic_equilibrium is the equilibrium of the entropic collision: it needs --model=elbm')
+        if cfg.model == 'elbm':
+            kw.update(self.elbm_desc(self.grid, cfg.visc, cfg.precision, getattr(cfg, 'entropic_equilibrium', False),
+                                     getattr(cfg, 'entropy_tolerance', 0.0), getattr(cfg, 'alpha_tolerance', 1e-10)))
         if getattr(cfg, 'regularized', False) or getattr(cfg, 'subgrid', 'none') != 'none':
             if cfg.model != 'bgk':
                 # the reference's MRT relaxation never calls the preamble that implements them: it would ignore both silently
@@ -47,6 +61,21 @@ class LBFluidSim(LBSim):
                       subgrid=hipabi.SLF_SUBGRID_LES_SMAGORINSKY if getattr(cfg, 'subgrid', 'none') == 'les-smagorinsky'
                       else hipabi.SLF_SUBGRID_NONE,
                       smagorinsky_const=float(getattr(cfg, 'smagorinsky_const', 0.1)))
+
+    @staticmethod
+    def elbm_tau0(grid, visc):
+        """The relaxation time of the entropic collision, visc / cs^2 (reference lb_single.py:54-55); the populations
+        relax by alpha beta with beta = 1 / (2 tau0 + 1)."""
+        return visc / float(grid.cssq)
+
+    @staticmethod
+    def elbm_desc(grid, visc, precision, entropic_equilibrium=False, entropy_tolerance=0.0, alpha_tolerance=1e-10):
+        """The slf_module_desc fields of an entropic module: the collision has one rate (no MRT rates), and an
+        entropy_tolerance of 0 means the default of the precision (reference lb_single.py:63-67)."""
+        if not entropy_tolerance > 0.0:
+            entropy_tolerance = 1e-6 if precision == 'single' else 1e-10
+        return dict(model=hipabi.SLF_ELBM, mrt_rates=[0.0] * grid.Q, entropic_equilibrium=int(bool(entropic_equilibrium)),
+                    entropy_tolerance=float(entropy_tolerance), alpha_tolerance=float(alpha_tolerance))
 
     @staticmethod
     def density_model(cfg):
@@ -74,6 +103,24 @@ class LBFluidSim(LBSim):
                 raise NotImplementedError('--minimize_roundoff: fluid, bounce-back and equilibrium density / velocity nodes '
                                           'only (node kinds %s are not covered: the reference\'s own regularized / Zou-He '
                                           'expressions are inconsistent under the option, DESIGN.md)' % sorted(set(bad)))
+        if kw.get('entropic_equilibrium') and kw.get('model') != hipabi.SLF_ELBM:
+            raise NotImplementedError('entropic_equilibrium needs model = elbm')
+        if kw.get('model') == hipabi.SLF_ELBM:
+            # what ELBM_relaxate (relaxation.mako:56-97) covers and this backend has fixtures for
+            if any(float(x) != 0.0 for x in kw.get('mrt_rates', [])):
+                raise NotImplementedError('--model=elbm: MRT relaxation rates are set; the entropic collision has one rate')
+            if kw.get('regularized') or kw.get('subgrid'):
+                raise NotImplementedError('--model=elbm: --regularized / --subgrid belong to the BGK relaxation preamble, which '
+                                          'the entropic collision never runs')
+            if kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
+                raise NotImplementedError('--model=elbm: single-fluid simulations only (the Shan-Chen models use BGK)')
+            if kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
+                raise NotImplementedError('--model=elbm: --minimize_roundoff stores f - w; the entropy needs the populations')
+            if kw.get('incompressible') == hipabi.SLF_DENSITY_INCOMPRESSIBLE and kw.get('entropic_equilibrium'):
+                raise NotImplementedError('--model=elbm: --entropic_equilibrium (compressible product form) does not go with '
+                                          '--incompressible')
+            if kw.get('has_force'):
+                raise NotImplementedError('--model=elbm: body forces under the entropic collision are not supported')
 
     def initial_conditions(self, runner):
         """f = feq(rho, v) on every copy of the distributions (reference lb_single.py:72-94)."""
@@ -107,6 +154,11 @@ class LBFluidSim(LBSim):
         signature = 'P' * (len(args1) - 1) + 'i'
         args1, sig1 = runner.add_indirect_args(args1, signature)
         args2, _ = runner.add_indirect_args(args2, signature)
+        if self.alpha_output:
+            # the alpha field of the entropic collision: the LAST argument (reference lb_single.py:129-133)
+            args1.append(runner.gpu_field(self.alpha))
+            args2.append(runner.gpu_field(self.alpha))
+            sig1 += 'P'
         return sig1, args1, args2
 
     def get_compute_kernels(self, runner, full_output, bulk):
@@ -154,6 +206,26 @@ class LBFluidSim(LBSim):
         for i in range(0, self.dim):
             kernels[1][i] = [runner.get_kernel(kernel, [gpu_dist, np.uint32(i)], 'Pi')]
         return kernels
+
+
+class LBEntropicFluidSim(LBFluidSim):
+    """LBFluidSim with alpha field tracking (reference lb_single.py:202-218).
+
+    The alpha field is 2.0 in areas where the fluid dynamics is fully resolved.  alpha < 2.0 means that the flow field is
+    smoothened, while alpha > 2.0 indicates enhancement of flow perturbation.  The field is the last argument of
+    CollideAndPropagate: the Newton iteration of a node starts from its previous alpha, and the alpha of every wet node
+    is stored at every step.  It is written to the output like rho and travels with checkpoints (checkpoint_fields), so
+    that a restored run resumes with the stored start values."""
+    alpha_output = True
+    checkpoint_fields = ('alpha',)
+
+    @classmethod
+    def modify_config(cls, config):
+        config.model = 'elbm'
+
+    @classmethod
+    def fields(cls):
+        return [ScalarField('rho'), VectorField('v'), ScalarField('alpha', init=2.0)]
 
 
 class LBSingleFluidShanChen(LBFluidSim, LBForcedSim):

@@ -797,6 +797,12 @@ class SubdomainRunner(object):
             data['dist%da' % n] = self._debug_get_dist(grid_num=n, copy=cur)
             if self._gpu_grids_secondary:
                 data['dist%db' % n] = self._debug_get_dist(grid_num=n, copy=1 - cur)
+        # fields that are STATE, not output derived from the populations (LBSim.checkpoint_fields: the alpha field of
+        # the entropic collision, whose entries are the Newton start values of the next step)
+        for name in getattr(self._sim, 'checkpoint_fields', ()):
+            host = getattr(self._sim, name)
+            self.backend.from_buf(self.gpu_field(host))
+            data['field_' + name] = np.array(host)
         np.savez(fname, **data)
 
     def restore_checkpoint(self, fname):
@@ -822,6 +828,11 @@ class SubdomainRunner(object):
             if n >= len(self._gpu_grids_primary) or (not is_a and not self._gpu_grids_secondary):
                 continue
             self._debug_set_dist(cpoint[key], grid_num=n, copy=cur if is_a else 1 - cur)
+        for name in getattr(self._sim, 'checkpoint_fields', ()):
+            if 'field_' + name in cpoint.files:
+                host = getattr(self._sim, name)
+                host[...] = cpoint['field_' + name]
+                self.backend.to_buf(self.gpu_field(host))
         self.backend.set_iteration(self._sim.iteration)
 
     # ------------------------------------------------------------------ life cycle
@@ -886,14 +897,17 @@ class SubdomainRunner(object):
     def check_gpu_invalid(self):
         """On-GPU invalid value check (reference --check_invalid_results_gpu): the sweeps flag wet nodes with
         a non-finite density; polled whenever the host synchronises with the device anyway."""
-        if not getattr(self.config, 'check_invalid_results_gpu', False):
+        # (the entropic collision raises the same word where its Newton iteration gives up, whatever the option says)
+        if not getattr(self.config, 'check_invalid_results_gpu', False) and getattr(self.config, 'model', '') != 'elbm':
             return
         pos = self.backend.poll_invalid(self.module, self._calc_stream)
         if pos is not None:
             gpos = [int(p) - 1 + o for p, o in zip(pos, self._spec.location)]
             raise self.backend.FatalError(
-                'Invalid value (inf / nan) detected on the GPU: subdomain %d, node %s (global position %s), '
-                'before iteration %d' % (self._spec.id, tuple(pos[:self.dim]), tuple(gpos), self._sim.iteration))
+                'Invalid value (inf / nan%s) detected on the GPU: subdomain %d, node %s (global position %s), '
+                'before iteration %d' % (', or an entropic collision whose alpha iteration did not converge'
+                                         if getattr(self.config, 'model', '') == 'elbm' else '',
+                                         self._spec.id, tuple(pos[:self.dim]), tuple(gpos), self._sim.iteration))
 
     def post_step(self, sync_req, output_req):
         cfg = self.config

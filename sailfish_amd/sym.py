@@ -32,6 +32,8 @@ class DxQy(object):
     def model_supported(cls, model):
         if model == 'mrt':
             return hasattr(cls, 'mrt_matrix')
+        if model == 'elbm':
+            return hasattr(cls, 'entropic_weights')
         return model == 'bgk'
 
 
@@ -149,6 +151,14 @@ def _prepare_grids():
         grid.mrt_matrix = np.array(_gram_schmidt_int(grid._mrt_basis()), dtype=np.int64)
         grid.mrt_norms = (grid.mrt_matrix * grid.mrt_matrix).sum(axis=1)
         grid.weights_float = np.array([float(w) for w in grid.weights])
+        # weights of the entropy function H = sum_i f_i ln(f_i / w_i) of the entropic model: products of the D1Q3 weights
+        # {-1: 1/6, 0: 2/3, 1: 1/6} unless the lattice defines its own (reference sym.py:951-1024) -- D2Q9 is a product
+        # lattice; D3Q19, which is not, uses its lattice weights (reference sym.py:329)
+        if grid.Q == 3 ** grid.dim:
+            d1q3 = {-1: Fraction(1, 6), 0: Fraction(2, 3), 1: Fraction(1, 6)}
+            grid.entropic_weights = [d1q3[v[0]] * d1q3[v[1]] * (d1q3[v[2]] if grid.dim == 3 else 1) for v in grid.basis]
+        else:
+            grid.entropic_weights = list(grid.weights)
         grid.basis_array = np.array(grid.basis, dtype=np.int64)
 
 

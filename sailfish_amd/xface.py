@@ -40,6 +40,8 @@ def supported(grid, desc, indirect=False, simtype=0):
     from sailfish_amd import hipabi
     if int(desc.incompressible) == hipabi.SLF_DENSITY_ROUNDOFF or int(desc.regularized) or int(desc.subgrid):
         return False
+    if int(desc.model) == hipabi.SLF_ELBM:      # per-node kernels as well
+        return False
     variant = os.environ.get('SLF_VARIANT')
     if variant is not None and not (int(variant) & 8):
         return False

@@ -141,7 +141,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 4x4,8x4,5x3 x-slabs of one process)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -323,6 +323,24 @@ def main():
         res.append(run('9b: examples/sphere_3d.py D3Q19 BGK 512x256x256 (AA)', SphereSim, LBGeometry3D,
                        dict(lat_nx=512, lat_ny=256, lat_nz=256, access_pattern='AA', max_iters=int(1500 * it),
                             benchmark_sample_from=int(500 * it)), 152))
+    # the entropic collision (--model=elbm, LBEntropicFluidSim: per-node kernels, the alpha field stored every step: 4 more
+    # bytes per update) on the 256^3 lid-driven cavity at Re = 1000, with the polynomial and the product-form equilibrium.
+    # Like-for-like baseline: 10c, the same cavity with BGK -- under SLF_VARIANT=0 through the per-node kernels as well.
+    from sailfish.lb_single import LBEntropicFluidSim
+
+    class EntropicCavity3D(LBEntropicFluidSim):
+        subdomain = Cavity3D.subdomain
+
+    cavity256 = dict(lat_nx=256, lat_ny=256, lat_nz=256, grid='D3Q19', visc=0.0128, access_pattern='AA',
+                     max_iters=int(1500 * it), benchmark_sample_from=int(500 * it))
+    if '10a' in only:
+        res.append(run('10a: D3Q19 ELBM lid-driven cavity 256^3 (AA)', EntropicCavity3D, LBGeometry3D,
+                       dict(cavity256, model='elbm'), 156))
+    if '10b' in only:
+        res.append(run('10b: D3Q19 ELBM lid-driven cavity 256^3, --entropic_equilibrium (AA)', EntropicCavity3D, LBGeometry3D,
+                       dict(cavity256, model='elbm', entropic_equilibrium=True), 156))
+    if '10c' in only:
+        res.append(run('10c: D3Q19 BGK lid-driven cavity 256^3 (AA)', Cavity3D, LBGeometry3D, dict(cavity256, model='bgk'), 152))
     # ---- several x-slabs of ONE process on this GPU (controller.LocalGroup; round 6): the Shan-Chen models over the x-face
     # planes, the force-driven pipe with its cuts on 128-byte lines
     if '4x4' in only:
