@@ -1620,6 +1620,44 @@ int slf_kernel_set_iteration(slf_kernel* k, uint32_t iteration) {
   return SLF_OK;
 }
 
+namespace {
+
+// What the four sweep cases of slf_kernel_launch share.  Each returns SLF_OK or the failure it has recorded.
+
+// the propagation step of this launch, from the module's access pattern and the kernel's iteration
+int step_prop(const slf_kernel* k, slf::Prop* prop) {
+  *prop = slf::PROP_AB;
+  if (k->mod->access_pattern == SLF_AA) {
+    if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
+    *prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
+  }
+  return SLF_OK;
+}
+
+// the rows [y0, y1) x [z0, z1) to sweep: the region, or all real nodes
+int sweep_region(const slf::Geometry& g, const slf_region* region, int* y0, int* y1, int* z0, int* z1) {
+  *y0 = 1; *y1 = g.lat_ny - 1; *z0 = 1; *z1 = g.lat_nz - 1;
+  if (g.dim == 2) { *z0 = 0; *z1 = 1; }
+  if (region) {
+    *y0 = region->y0; *y1 = region->y1;
+    if (g.dim == 3) { *z0 = region->z0; *z1 = region->z1; }
+    if (*y0 < 1 || *y1 > g.lat_ny - 1 || *y0 > *y1 || (g.dim == 3 && (*z0 < 1 || *z1 > g.lat_nz - 1 || *z0 > *z1)))
+      return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
+  }
+  return SLF_OK;
+}
+
+// the module's tables and the options word (first integer argument) into the launch arguments; a.map is set by now
+int sweep_common(const slf_kernel* k, slf::SweepArgs& a) {
+  a.node_params = k->mod->node_params;
+  a.status = k->mod->status;
+  a.options = (uint32_t)k->ints[0];
+  if (k->mod->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+  return SLF_OK;
+}
+
+}  // namespace
+
 int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* stream) {
   if (!k) return fail(SLF_ERR_INVALID, "kernel is NULL");
   if (!k->bound) return fail(SLF_ERR_INVALID, "kernel arguments not set");
@@ -1642,36 +1680,24 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       a.v[0] = (void*)k->ptrs[b0 + 4];
       a.v[1] = (void*)k->ptrs[b0 + 5];
       a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 6] : nullptr;
-      a.node_params = m->node_params;
-      a.status = m->status;
-      a.options = (uint32_t)k->ints[0];
       a.alpha = k->alpha_arg ? (void*)k->ptrs.back() : nullptr;
       for (int f = 0; f < 2; f++) {
         a.xsend[f] = m->xsend[f];
         a.xrecv[f] = m->xrecv[f];
       }
       a.rows = m->rows.map ? &m->rows : nullptr;
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+      if (int rc = sweep_common(k, a)) return rc;
       if (g.indirect && !a.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
       // (the slot table is built when the arguments are bound, slf_kernel_set_args: a launch may be part of a graph capture)
       if (g.indirect && k->kind == KK_COLLIDE_AND_PROPAGATE && m->slots.nodes == a.nodes) a.slots = &m->slots;
-      slf::Prop prop = slf::PROP_AB;
-      if (m->access_pattern == SLF_AA) {
-        if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-        prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
-      }
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
       if (k->kind == KK_COMPUTE_MACRO) {
         e = slf::launch_macro(m->sel, prop, g, m->phys, a, s);
         break;
       }
-      int y0 = 1, y1 = g.lat_ny - 1, z0 = 1, z1 = g.lat_nz - 1;
-      if (g.dim == 2) { z0 = 0; z1 = 1; }
-      if (region) {
-        y0 = region->y0; y1 = region->y1;
-        if (g.dim == 3) { z0 = region->z0; z1 = region->z1; }
-        if (y0 < 1 || y1 > g.lat_ny - 1 || y0 > y1 || (g.dim == 3 && (z0 < 1 || z1 > g.lat_nz - 1 || z0 > z1)))
-          return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
-      }
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
       e = slf::launch_sweep(m->sel, prop, g, m->phys, a, y0, y1, z0, z1, m->block_x, s);
       break;
     }
@@ -1690,25 +1716,13 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       a.v[0] = (void*)k->ptrs[b0 + 5];
       a.v[1] = (void*)k->ptrs[b0 + 6];
       a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 7] : nullptr;
-      a.node_params = m->node_params;
-      a.status = m->status;
-      a.options = (uint32_t)k->ints[0];
       a.sc_local_velocity = k->sc_local_velocity;
       sc_planes_of(m, a);
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-      slf::Prop prop = slf::PROP_AB;
-      if (m->access_pattern == SLF_AA) {
-        if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-        prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
-      }
-      int y0 = 1, y1 = g.lat_ny - 1, z0 = 1, z1 = g.lat_nz - 1;
-      if (g.dim == 2) { z0 = 0; z1 = 1; }
-      if (region) {
-        y0 = region->y0; y1 = region->y1;
-        if (g.dim == 3) { z0 = region->z0; z1 = region->z1; }
-        if (y0 < 1 || y1 > g.lat_ny - 1 || y0 > y1 || (g.dim == 3 && (z0 < 1 || z1 > g.lat_nz - 1 || z0 > z1)))
-          return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
-      }
+      if (int rc = sweep_common(k, a)) return rc;
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
       if (k->kind == KK_SC_MACRO) e = slf::launch_sc_macro(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, s);
       else e = slf::launch_sc_sweep(m->sel, k->kind == KK_SC_SWEEP0 ? 0 : 1, prop, g, m->phys, m->sc, a, y0, y1, z0, z1,
                                     m->block_x, s);
@@ -1726,25 +1740,13 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       a.v[0] = (void*)k->ptrs[7];
       a.v[1] = (void*)k->ptrs[8];
       a.v[2] = g.dim == 3 ? (void*)k->ptrs[9] : nullptr;
-      a.node_params = m->node_params;
-      a.status = m->status;
-      a.options = (uint32_t)k->ints[0];
       a.sc_local_velocity = k->sc_local_velocity;
       sc_planes_of(m, a);
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-      slf::Prop prop = slf::PROP_AB;
-      if (m->access_pattern == SLF_AA) {
-        if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-        prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
-      }
-      int y0 = 1, y1 = g.lat_ny - 1, z0 = 1, z1 = g.lat_nz - 1;
-      if (g.dim == 2) { z0 = 0; z1 = 1; }
-      if (region) {
-        y0 = region->y0; y1 = region->y1;
-        if (g.dim == 3) { z0 = region->z0; z1 = region->z1; }
-        if (y0 < 1 || y1 > g.lat_ny - 1 || y0 > y1 || (g.dim == 3 && (z0 < 1 || z1 > g.lat_nz - 1 || z0 > z1)))
-          return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
-      }
+      if (int rc = sweep_common(k, a)) return rc;
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
       e = slf::launch_sc_fused(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, m->block_x, s);
       break;
     }
@@ -1770,9 +1772,6 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       a.map = (const void*)k->ptrs[b0 + 0];
       a.dist_in = (void*)k->ptrs[b0 + 1];
       a.phi = nullptr;
-      a.node_params = m->node_params;
-      a.status = m->status;
-      a.options = (uint32_t)k->ints[0];
       if (k->kind == KK_SCS_MACRO) {
         a.dist_out = nullptr;
         a.rho = (void*)k->ptrs[b0 + 2];
@@ -1785,24 +1784,15 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
         a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 6] : nullptr;
       }
       sc_planes_of(m, a);
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-      slf::Prop prop = slf::PROP_AB;
-      if (m->access_pattern == SLF_AA) {
-        if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-        prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
-      }
+      if (int rc = sweep_common(k, a)) return rc;
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
       if (k->kind == KK_SCS_MACRO) {
         e = slf::launch_scs_macro(m->sel, prop, g, m->phys, m->sc, a, s);
         break;
       }
-      int y0 = 1, y1 = g.lat_ny - 1, z0 = 1, z1 = g.lat_nz - 1;
-      if (g.dim == 2) { z0 = 0; z1 = 1; }
-      if (region) {
-        y0 = region->y0; y1 = region->y1;
-        if (g.dim == 3) { z0 = region->z0; z1 = region->z1; }
-        if (y0 < 1 || y1 > g.lat_ny - 1 || y0 > y1 || (g.dim == 3 && (z0 < 1 || z1 > g.lat_nz - 1 || z0 > z1)))
-          return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
-      }
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
       e = slf::launch_scs_sweep(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, m->block_x, s);
       break;
     }

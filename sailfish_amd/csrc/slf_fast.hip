@@ -9,6 +9,7 @@
 //       (the even step touches only the node's own slots -> every access is aligned)
 //   8   x-streaming steps (odd AA, AB) use the whole-row kernel with aligned accesses
 // Populations are streamed exactly once per step: every access carries the non-temporal hint (NT).
+#include "slf_dispatch.h"
 #include "slf_rowpush.h"
 
 namespace slf {
@@ -328,24 +329,16 @@ static bool launch_fast_model(Prop prop, const Geometry& g, const SweepParams<D3
   if ((variant & 8) && prop != PROP_AA_EVEN) {
     if (nx > 1024) return false;                 // long rows: segmented row kernel (slf_row.hip)
     dim3 grid(1, ny, nz);
-    if (nx > 512) {                              // two nodes per thread
-      dim3 block((((nx + 1) / 2 + 63) / 64) * 64, 1, 1);
-      if (prop == PROP_AB) hipLaunchKernelGGL((fast_row_kernel<MODEL, PROP_AB, FORCE, 2>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((fast_row_kernel<MODEL, PROP_AA_ODD, FORCE, 2>), grid, block, 0, s, p);
-      return true;
-    }
-    dim3 block(((nx + 63) / 64) * 64, 1, 1);
-    if (prop == PROP_AB) hipLaunchKernelGGL((fast_row_kernel<MODEL, PROP_AB, FORCE, 1>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((fast_row_kernel<MODEL, PROP_AA_ODD, FORCE, 1>), grid, block, 0, s, p);
+    const int per_thread = nx > 512 ? 2 : 1;     // two nodes per thread
+    dim3 block((((nx + per_thread - 1) / per_thread + 63) / 64) * 64, 1, 1);
+    pick<int, PROP_AB, PROP_AA_ODD>(prop, [&](auto P) { pick<int, 1, 2>(per_thread, [&](auto N) {
+      hipLaunchKernelGGL((fast_row_kernel<MODEL, P, FORCE, N>), grid, block, 0, s, p);
+    }); });
     return true;
   }
   dim3 block(block_x, 1, 1);
   dim3 grid((nx + block_x - 1) / block_x, ny, nz);
-  switch (prop) {
-    case PROP_AB: hipLaunchKernelGGL((fast_scalar_kernel<MODEL, PROP_AB, FORCE>), grid, block, 0, s, p); break;
-    case PROP_AA_EVEN: hipLaunchKernelGGL((fast_scalar_kernel<MODEL, PROP_AA_EVEN, FORCE>), grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((fast_scalar_kernel<MODEL, PROP_AA_ODD, FORCE>), grid, block, 0, s, p); break;
-  }
+  pick_prop(prop, [&](auto P) { hipLaunchKernelGGL((fast_scalar_kernel<MODEL, P, FORCE>), grid, block, 0, s, p); });
   return true;
 }
 
@@ -359,14 +352,11 @@ bool launch_sweep_fast(const KernelSelector& sel, Prop prop, const Geometry& g, 
   if (y1 <= y0 || z1 <= z0) return false;
   const SweepParams<D3Q19, float> p = make_params<D3Q19, float>(g, ph, a, y0, z0);
   const int ny = y1 - y0, nz = z1 - z0;
-  bool done;
-  if (ph.has_force) {
-    done = sel.model == 0 ? launch_fast_model<0, true>(prop, g, p, ny, nz, block_x, s)
-                          : launch_fast_model<1, true>(prop, g, p, ny, nz, block_x, s);
-  } else {   // no body force: straight-line collision, half the registers, twice the resident waves
-    done = sel.model == 0 ? launch_fast_model<0, false>(prop, g, p, ny, nz, block_x, s)
-                          : launch_fast_model<1, false>(prop, g, p, ny, nz, block_x, s);
-  }
+  bool done = false;
+  // no body force: straight-line collision, half the registers, twice the resident waves
+  pick<int, 0, 1>(sel.model == 0 ? 0 : 1, [&](auto MODEL) { pick_bool(ph.has_force != 0, [&](auto FORCE) {
+    done = launch_fast_model<MODEL, FORCE>(prop, g, p, ny, nz, block_x, s);
+  }); });
   if (done) *err = hipGetLastError();
   return done;
 }

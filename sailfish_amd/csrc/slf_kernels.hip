@@ -16,6 +16,7 @@
 // "push" for AB and the odd AA step, in-place opposite-slot for the even AA step
 // (reference propagation.mako:170-174, 384-421; geo_helpers.mako:248-276).
 #include "../../include/sailfish_hip.h"
+#include "slf_dispatch.h"
 #include "slf_kernels.h"
 #include "slf_node.h"
 #include "slf_sweep.h"
@@ -291,14 +292,14 @@ hipError_t launch_box(const KernelSelector& sel, const Geometry& g, bool collect
   dim3 grid((ncols + 255) / 256, nrows, nd);
   const size_t dq = g.dist_size;
   const int all = deliver_all ? 1 : 0;
-  if (sel.precision == 4) {
-    if (collect) hipLaunchKernelGGL((box_kernel<float, true>), grid, block, 0, s, (float*)dist, (float*)buffer, dq, dirlist, base, col_stride, ncols, row_stride, nrows, buf_k_stride, buf_row_stride, all);
-    else hipLaunchKernelGGL((box_kernel<float, false>), grid, block, 0, s, (float*)dist, (float*)buffer, dq, dirlist, base, col_stride, ncols, row_stride, nrows, buf_k_stride, buf_row_stride, all);
-  } else {
-    if (collect) hipLaunchKernelGGL((box_kernel<double, true>), grid, block, 0, s, (double*)dist, (double*)buffer, dq, dirlist, base, col_stride, ncols, row_stride, nrows, buf_k_stride, buf_row_stride, all);
-    else hipLaunchKernelGGL((box_kernel<double, false>), grid, block, 0, s, (double*)dist, (double*)buffer, dq, dirlist, base, col_stride, ncols, row_stride, nrows, buf_k_stride, buf_row_stride, all);
-  }
-  return hipGetLastError();
+  return pick_real(sel, [&](auto r) {
+    using R = decltype(r);
+    pick_bool(collect, [&](auto COLLECT) {
+      hipLaunchKernelGGL((box_kernel<R, COLLECT>), grid, block, 0, s, (R*)dist, (R*)buffer, dq, dirlist, base, col_stride,
+                         ncols, row_stride, nrows, buf_k_stride, buf_row_stride, all);
+    });
+    return hipGetLastError();
+  });
 }
 
 // PrepareMacroFields-style pass: density/velocity of every wet node without
@@ -352,81 +353,43 @@ __global__ void __launch_bounds__(1024) macro_kernel(const SweepParams<L, R> p) 
 // host-side dispatch
 // ---------------------------------------------------------------------------
 
-template <class L, class R, int MODEL, int PROP>
-static hipError_t launch_sweep4(bool general, const Geometry& g, const Physics& ph, const SweepArgs& a, int y0, int y1,
-                                int z0, int z1, int block_x, hipStream_t s) {
+template <class L, class R>
+static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, const Geometry& g, const Physics& ph,
+                                const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
   const SweepParams<L, R> p = make_params<L, R>(g, ph, a, y0, z0);
   dim3 block(block_x, 1, 1);
   dim3 grid((g.lat_nx - 2 + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
   if (grid.y == 0 || grid.z == 0) return hipSuccess;
-  if constexpr (MODEL == 2) {                 // --model=elbm: per-node kernels only, at most 512 threads per workgroup
-    if (block.x > 512) {
-      block.x = 512;
-      grid.x = (g.lat_nx - 2 + 511) / 512;
-    }
-    if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true>), grid, block, 0, s, p);
-    else if (general) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, false>), grid, block, 0, s, p);
-    return hipGetLastError();
+  if (model != 0 && model != 2) model = 1;
+  // BGK only (checked at module creation): --minimize_roundoff; --regularized / --subgrid=les-smagorinsky
+  const bool roundoff = model == 0 && ph.incompressible == SLF_DENSITY_ROUNDOFF;
+  const bool turb = model == 0 && !roundoff && (ph.regularized || ph.subgrid);
+  if ((turb || model == 2) && block.x > 512) {      // these instantiations: at most 512 threads per workgroup (launch bounds)
+    block.x = 512;
+    grid.x = (g.lat_nx - 2 + 511) / 512;
   }
-  if constexpr (MODEL == 0) {
-    if (ph.incompressible == SLF_DENSITY_ROUNDOFF) {       // --minimize_roundoff (BGK only; checked at module creation)
-      if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true, true>), grid, block, 0, s, p);
-      else if (general) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, false, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, false, false, true>), grid, block, 0, s, p);
-      return hipGetLastError();
-    }
-    if (ph.regularized || ph.subgrid) {       // --regularized / --subgrid=les-smagorinsky (BGK only; checked at module creation)
-      if (block.x > 512) {                    // these instantiations: at most 512 threads per workgroup (launch bounds)
-        block.x = 512;
-        grid.x = (g.lat_nx - 2 + 511) / 512;
-      }
-      if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true, false, true>), grid, block, 0, s, p);
-      else if (general) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, false, false, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, false, false, false, true>), grid, block, 0, s, p);
-      return hipGetLastError();
-    }
-  }
-  if (g.indirect && p.slot_gi) {       // one thread per slot (slot_sweep_kernel)
+  if (!roundoff && !turb && model != 2 && g.indirect && p.slot_gi) {       // one thread per slot (slot_sweep_kernel)
     SweepParams<L, R> q = p;
     q.y1 = y1;
     q.z1 = (L::dim == 3) ? z1 : 1;
-    return launch_slot_sweep<L, R>(MODEL, PROP, g.bc_level, q, s);      // slf_slots.hip
+    return launch_slot_sweep<L, R>(model, prop, g.bc_level, q, s);      // slf_slots.hip
   }
-  if (g.indirect) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true, true>), grid, block, 0, s, p);
-  else if (general) hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, true>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, PROP, false>), grid, block, 0, s, p);
-  return hipGetLastError();
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
+  pick<int, 0, 1, 2>(model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
+    pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
+      pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) {
+        // indirect addressing: the node map is always read; --minimize_roundoff and --regularized / --subgrid exclude
+        // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only
+        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0)) return;
+        else {
+          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB>), grid, block, 0, s, p);
+          e = hipGetLastError();
+        }
+      }); });
+    }); });
+  }); });
+  return e;
 }
-
-template <class L, class R, int MODEL>
-static hipError_t launch_sweep3(Prop prop, bool general, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                                int y0, int y1, int z0, int z1, int bx, hipStream_t s) {
-  switch (prop) {
-    case PROP_AB: return launch_sweep4<L, R, MODEL, PROP_AB>(general, g, ph, a, y0, y1, z0, z1, bx, s);
-    case PROP_AA_EVEN: return launch_sweep4<L, R, MODEL, PROP_AA_EVEN>(general, g, ph, a, y0, y1, z0, z1, bx, s);
-    default: return launch_sweep4<L, R, MODEL, PROP_AA_ODD>(general, g, ph, a, y0, y1, z0, z1, bx, s);
-  }
-}
-
-template <class L, class R>
-static hipError_t launch_sweep2(int model, Prop prop, bool general, const Geometry& g, const Physics& ph,
-                                const SweepArgs& a, int y0, int y1, int z0, int z1, int bx, hipStream_t s) {
-  if (model == 0) return launch_sweep3<L, R, 0>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
-  if (model == 2) return launch_sweep3<L, R, 2>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
-  return launch_sweep3<L, R, 1>(prop, general, g, ph, a, y0, y1, z0, z1, bx, s);
-}
-
-#define SLF_DISPATCH_LR(sel, CALL)                                   \
-  do {                                                               \
-    if ((sel).lattice == 0) {                                        \
-      if ((sel).precision == 4) { using L = D2Q9; using R = float; CALL; }  \
-      else { using L = D2Q9; using R = double; CALL; }               \
-    } else {                                                         \
-      if ((sel).precision == 4) { using L = D3Q19; using R = float; CALL; } \
-      else { using L = D3Q19; using R = double; CALL; }              \
-    }                                                                \
-  } while (0)
 
 hipError_t launch_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                         const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
@@ -435,13 +398,14 @@ hipError_t launch_sweep(const KernelSelector& sel, Prop prop, const Geometry& g,
     if (launch_sweep_fast(sel, prop, g, ph, a, y0, y1, z0, z1, block_x, s, &fe)) return fe;
     if (launch_sweep_row(sel, prop, g, ph, a, y0, y1, z0, z1, s, &fe)) return fe;
   }
-  SLF_DISPATCH_LR(sel, return (launch_sweep2<L, R>(sel.model, prop, sel.general, g, ph, a, y0, y1, z0, z1, block_x, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) {
+    return launch_sweep2(lr, sel.model, prop, sel.general, g, ph, a, y0, y1, z0, z1, block_x, s);
+  });
 }
 
 template <class L, class R>
-static hipError_t launch_init2(const Geometry& g, const Physics& ph, void* dist, const void* rho, const void* const v[3],
-                               const void* nodes, hipStream_t s) {
+static hipError_t launch_init2(LR<L, R>, const Geometry& g, const Physics& ph, void* dist, const void* rho,
+                               const void* const v[3], const void* nodes, hipStream_t s) {
   dim3 block(256, 1, 1);
   dim3 grid((g.lat_nx + 255) / 256, g.lat_ny, g.lat_nz);
   hipLaunchKernelGGL((init_kernel<L, R>), grid, block, 0, s, (R*)dist, (const R*)rho, (const R*)v[0], (const R*)v[1],
@@ -451,27 +415,24 @@ static hipError_t launch_init2(const Geometry& g, const Physics& ph, void* dist,
 
 hipError_t launch_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist, const void* rho,
                        const void* const v[3], const void* nodes, hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (launch_init2<L, R>(g, ph, dist, rho, v, nodes, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return launch_init2(lr, g, ph, dist, rho, v, nodes, s); });
 }
 
 template <class L, class R>
-static hipError_t launch_pbc2(const Geometry& g, void* dist, int axis, bool with_swap, hipStream_t s) {
+static hipError_t launch_pbc2(LR<L, R>, const Geometry& g, void* dist, int axis, bool with_swap, hipStream_t s) {
   const int lat[3] = {g.lat_nx, g.lat_ny, g.lat_nz};
   int b_ax = (axis == 0) ? 1 : 0;
   int c_ax = (axis == 2) ? 1 : 2;
   dim3 block(256, 1, 1);
   dim3 grid((lat[b_ax] + 255) / 256, L::dim == 3 ? lat[c_ax] : 1, 1);
-  if (with_swap) hipLaunchKernelGGL((pbc_kernel<L, R, true>), grid, block, 0, s, (R*)dist, g, axis);
-  else hipLaunchKernelGGL((pbc_kernel<L, R, false>), grid, block, 0, s, (R*)dist, g, axis);
+  pick_bool(with_swap, [&](auto SWAP) { hipLaunchKernelGGL((pbc_kernel<L, R, SWAP>), grid, block, 0, s, (R*)dist, g, axis); });
   return hipGetLastError();
 }
 
 hipError_t launch_pbc(const KernelSelector& sel, const Geometry& g, void* dist, int axis, bool with_swap,
                       hipStream_t s) {
   if (axis < 0 || axis >= g.dim) return hipErrorInvalidValue;
-  SLF_DISPATCH_LR(sel, return (launch_pbc2<L, R>(g, dist, axis, with_swap, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return launch_pbc2(lr, g, dist, axis, with_swap, s); });
 }
 
 hipError_t launch_macro_pbc(const KernelSelector& sel, const Geometry& g, void* field, int axis, hipStream_t s) {
@@ -481,9 +442,10 @@ hipError_t launch_macro_pbc(const KernelSelector& sel, const Geometry& g, void* 
   int c_ax = (axis == 2) ? 1 : 2;
   dim3 block(256, 1, 1);
   dim3 grid((lat[b_ax] + 255) / 256, lat[c_ax], 1);
-  if (sel.precision == 4) hipLaunchKernelGGL((macro_pbc_kernel<float>), grid, block, 0, s, (float*)field, g, axis);
-  else hipLaunchKernelGGL((macro_pbc_kernel<double>), grid, block, 0, s, (double*)field, g, axis);
-  return hipGetLastError();
+  return pick_real(sel, [&](auto r) {
+    hipLaunchKernelGGL((macro_pbc_kernel<decltype(r)>), grid, block, 0, s, (decltype(r)*)field, g, axis);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_sparse(const KernelSelector& sel, bool collect, const unsigned long long* idx, void* dist,
@@ -491,37 +453,32 @@ hipError_t launch_sparse(const KernelSelector& sel, bool collect, const unsigned
   if (n <= 0) return hipSuccess;
   dim3 block(256, 1, 1);
   dim3 grid((n + 255) / 256, 1, 1);
-  if (sel.precision == 4) {
-    if (collect) hipLaunchKernelGGL((sparse_kernel<float, true>), grid, block, 0, s, idx, (float*)dist, (float*)buffer, n);
-    else hipLaunchKernelGGL((sparse_kernel<float, false>), grid, block, 0, s, idx, (float*)dist, (float*)buffer, n);
-  } else {
-    if (collect) hipLaunchKernelGGL((sparse_kernel<double, true>), grid, block, 0, s, idx, (double*)dist, (double*)buffer, n);
-    else hipLaunchKernelGGL((sparse_kernel<double, false>), grid, block, 0, s, idx, (double*)dist, (double*)buffer, n);
-  }
-  return hipGetLastError();
+  return pick_real(sel, [&](auto r) {
+    using R = decltype(r);
+    pick_bool(collect, [&](auto COLLECT) {
+      hipLaunchKernelGGL((sparse_kernel<R, COLLECT>), grid, block, 0, s, idx, (R*)dist, (R*)buffer, n);
+    });
+    return hipGetLastError();
+  });
 }
 
 template <class L, class R>
-static hipError_t launch_macro2(Prop prop, bool general, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                                hipStream_t s) {
+static hipError_t launch_macro2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph,
+                                const SweepArgs& a, hipStream_t s) {
   const SweepParams<L, R> p = make_params<L, R>(g, ph, a, 1, L::dim == 3 ? 1 : 0);
   const int bx = 256;
   dim3 block(bx, 1, 1);
   dim3 grid((g.lat_nx - 2 + bx - 1) / bx, g.lat_ny - 2, L::dim == 3 ? g.lat_nz - 2 : 1);
-  if (prop == PROP_AA_ODD) {
-    if (general) hipLaunchKernelGGL((macro_kernel<L, R, PROP_AA_ODD, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((macro_kernel<L, R, PROP_AA_ODD, false>), grid, block, 0, s, p);
-  } else {
-    if (general) hipLaunchKernelGGL((macro_kernel<L, R, PROP_AB, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((macro_kernel<L, R, PROP_AB, false>), grid, block, 0, s, p);
-  }
+  // two-copy and the even in-place step: the node's own slots
+  pick<int, PROP_AB, PROP_AA_ODD>(prop == PROP_AA_ODD ? PROP_AA_ODD : PROP_AB, [&](auto P) {
+    pick_bool(general, [&](auto G) { hipLaunchKernelGGL((macro_kernel<L, R, P, G>), grid, block, 0, s, p); });
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                         const SweepArgs& a, hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (launch_macro2<L, R>(prop, sel.general, g, ph, a, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return launch_macro2(lr, prop, sel.general, g, ph, a, s); });
 }
 
 }  // namespace slf

@@ -23,6 +23,7 @@
 // Not served (refused by slf_kernel_set_args / the host falls back to stepping): half-way bounce-back and outflow
 // nodes (their node code writes / reads memory directly), indirect addressing, --minimize_roundoff, Shan-Chen models.
 #include "../../include/sailfish_hip.h"
+#include "slf_dispatch.h"
 #include "slf_kernels.h"
 #include "slf_node.h"
 #include "slf_sweep.h"
@@ -282,19 +283,6 @@ size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y) {
   return nw * (size_t)q * (size_t)precision * 2 + nw * 8;
 }
 
-template <class L, class R, int MODEL, bool AA>
-static hipError_t launch_resident3(bool general, const ResidentParams<L, R>& rp, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024) {
-    // beyond the default 64 KiB of dynamic LDS a kernel has to ask for it (160 KiB per workgroup on gfx950)
-    const void* fn = general ? (const void*)resident_kernel<L, R, MODEL, AA, true> : (const void*)resident_kernel<L, R, MODEL, AA, false>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  if (general) hipLaunchKernelGGL((resident_kernel<L, R, MODEL, AA, true>), grid, block, lds, s, rp);
-  else hipLaunchKernelGGL((resident_kernel<L, R, MODEL, AA, false>), grid, block, lds, s, rp);
-  return hipGetLastError();
-}
-
 template <class L, class R>
 static hipError_t launch_resident2(const KernelSelector& sel, bool aa, const Geometry& g, const Physics& ph, const SweepArgs& a,
                                    const void* const src[2], void* const dst[2], int it0, int steps, int tile_x, int tile_y,
@@ -323,20 +311,26 @@ static hipError_t launch_resident2(const KernelSelector& sel, bool aa, const Geo
   dim3 block(threads, 1, 1);
   dim3 grid((rp.ext[0] + tile_x - 1) / tile_x, (rp.ext[1] + tile_y - 1) / tile_y, 1);
   const size_t lds = resident_lds_bytes(L::Q, (int)sizeof(R), aa, rp.win[0], rp.win[1]);
-  if (sel.model == 0) {
-    if (aa) return launch_resident3<L, R, 0, true>(sel.general, rp, grid, block, lds, s);
-    return launch_resident3<L, R, 0, false>(sel.general, rp, grid, block, lds, s);
-  }
-  if (aa) return launch_resident3<L, R, 1, true>(sel.general, rp, grid, block, lds, s);
-  return launch_resident3<L, R, 1, false>(sel.general, rp, grid, block, lds, s);
+  hipError_t e = hipSuccess;
+  pick<int, 0, 1>(sel.model == 0 ? 0 : 1, [&](auto MODEL) { pick_bool(aa, [&](auto AA) { pick_bool(sel.general, [&](auto G) {
+    // beyond the default 64 KiB of dynamic LDS a kernel has to ask for it (160 KiB per workgroup on gfx950)
+    if (lds > 64 * 1024) {
+      e = hipFuncSetAttribute((const void*)resident_kernel<L, R, MODEL, AA, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return;
+    }
+    hipLaunchKernelGGL((resident_kernel<L, R, MODEL, AA, G>), grid, block, lds, s, rp);
+    e = hipGetLastError();
+  }); }); });
+  return e;
 }
 
 hipError_t launch_resident(const KernelSelector& sel, bool aa, const Geometry& g, const Physics& ph, const SweepArgs& a,
                            const void* const src[2], void* const dst[2], int it0, int steps, int tile_x, int tile_y, int halo,
                            hipStream_t s) {
   if (sel.lattice != 0) return hipErrorInvalidValue;
-  if (sel.precision == 4) return launch_resident2<D2Q9, float>(sel, aa, g, ph, a, src, dst, it0, steps, tile_x, tile_y, halo, s);
-  return launch_resident2<D2Q9, double>(sel, aa, g, ph, a, src, dst, it0, steps, tile_x, tile_y, halo, s);
+  return pick_real(sel, [&](auto r) {
+    return launch_resident2<D2Q9, decltype(r)>(sel, aa, g, ph, a, src, dst, it0, steps, tile_x, tile_y, halo, s);
+  });
 }
 
 }  // namespace slf

@@ -19,6 +19,7 @@
 // Arithmetic is node_update() of slf_sweep.h, shared with the per-node kernel in slf_kernels.hip: the
 // results are bit-identical.  Replaces the reference's shared-memory propagation
 // (templates/propagation.mako:180-288) on MI355X.
+#include "slf_dispatch.h"
 #include "slf_rowpush.h"
 
 namespace slf {
@@ -280,23 +281,13 @@ static void launch_row5(Prop prop, SweepParams<L, R> p, int nx, int ny, int nz, 
   launch_level<L, R, MODEL, GENERAL, FORCE, 2>(prop, p, grid, block, s);
 }
 
-template <class L, class R, int MODEL, bool GENERAL>
-static void launch_row4(Prop prop, const SweepParams<L, R>& p, int nx, int ny, int nz, const RowClasses* rc, hipStream_t s) {
-  // compile-time "body force or not" instantiations: see bgk_relax, slf_node.h
-  if (p.cp.has_force != 0) launch_row5<L, R, MODEL, GENERAL, true>(prop, p, nx, ny, nz, rc, s);
-  else launch_row5<L, R, MODEL, GENERAL, false>(prop, p, nx, ny, nz, rc, s);
-}
-
 template <class L, class R>
 static void launch_row2(const KernelSelector& sel, Prop prop, const SweepParams<L, R>& p, int nx, int ny, int nz,
                         const RowClasses* rc, hipStream_t s) {
-  if (sel.model == 0) {
-    if (sel.general) launch_row4<L, R, 0, true>(prop, p, nx, ny, nz, rc, s);
-    else launch_row4<L, R, 0, false>(prop, p, nx, ny, nz, rc, s);
-  } else {
-    if (sel.general) launch_row4<L, R, 1, true>(prop, p, nx, ny, nz, rc, s);
-    else launch_row4<L, R, 1, false>(prop, p, nx, ny, nz, rc, s);
-  }
+  // compile-time "body force or not" instantiations: see bgk_relax, slf_node.h
+  pick<int, 0, 1>(sel.model == 0 ? 0 : 1, [&](auto MODEL) { pick_bool(sel.general, [&](auto GENERAL) {
+    pick_bool(p.cp.has_force != 0, [&](auto FORCE) { launch_row5<L, R, MODEL, GENERAL, FORCE>(prop, p, nx, ny, nz, rc, s); });
+  }); });
 }
 
 bool launch_sweep_row(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
@@ -308,8 +299,7 @@ bool launch_sweep_row(const KernelSelector& sel, Prop prop, const Geometry& g, c
   const int ny = y1 - y0, nz = (g.dim == 3) ? z1 - z0 : 1;
   if (ny <= 0 || nz <= 0) return false;
   const RowClasses* rc = (sel.general && a.rows && a.rows->map == a.map) ? a.rows : nullptr;
-  if (sel.precision == 4) launch_row2<D3Q19, float>(sel, prop, make_params<D3Q19, float>(g, ph, a, y0, z0), nx, ny, nz, rc, s);
-  else launch_row2<D3Q19, double>(sel, prop, make_params<D3Q19, double>(g, ph, a, y0, z0), nx, ny, nz, rc, s);
+  pick_real(sel, [&](auto r) { launch_row2(sel, prop, make_params<D3Q19, decltype(r)>(g, ph, a, y0, z0), nx, ny, nz, rc, s); });
   *err = hipGetLastError();
   return true;
 }

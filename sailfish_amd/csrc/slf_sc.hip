@@ -14,6 +14,7 @@
 // reads the 18 neighbour densities of the *other* field through the cache hierarchy (each value is
 // reused by 18 nodes; rows of a workgroup are contiguous), the acceleration F_k / rho_k enters the BGK
 // collision through Guo forcing exactly like a body force (relaxation_common.mako:56-64,110-149).
+#include "slf_dispatch.h"
 #include "slf_rowpush.h"
 
 namespace slf {
@@ -953,294 +954,223 @@ static inline bool sc_row_pull_ok(const Geometry& g) {
   return SLF_SC_ROW_PULL && g.wrap[0] && g.lat_nx - 2 <= 1024 && (g.variant & 8) && !g.indirect;
 }
 
+// Block width of the pass kernels (densities, velocity): the whole row in one workgroup where it fits
+static inline int sc_pass_block_x(int nx) {
+  const int bx = ((nx + 63) / 64) * 64;
+  return bx > 1024 ? 256 : bx;
+}
+
+// Launch shape of all four launchers.  row: whole-row workgroups + aligned stores for the x-streaming steps in 3-D (as
+// slf_row.hip), where the caller's kernels have that form (row_ok); block_x is then the row's, not the caller's.
+struct ScShape {
+  dim3 grid, block;
+  bool row, empty;
+  int xcd_shift;      // the force stencil's rho / phi rows: neighbouring rows on one XCD
+};
+
+template <class L>
+static ScShape sc_shape(const Geometry& g, bool row_ok, Prop prop, int y0, int y1, int z0, int z1, int block_x) {
+  const int nx = g.lat_nx - 2;
+  ScShape sh;
+  sh.row = row_ok && L::dim == 3 && (g.variant & 8) && prop != PROP_AA_EVEN;
+  if (sh.row) block_x = row_block_x(nx);
+  sh.block = dim3(block_x, 1, 1);
+  sh.grid = dim3((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
+  sh.empty = sh.grid.y == 0 || sh.grid.z == 0;
+  sh.xcd_shift = xcd_shift_for(sh.grid.y, sh.grid.x);
+  return sh;
+}
+
 template <class L, class R>
-static hipError_t sc_macro2(Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
+static hipError_t sc_macro2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
                             const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s) {
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
-  const int nx = g.lat_nx - 2;
-  int bx = ((nx + 63) / 64) * 64;
-  if (bx > 1024) bx = 256;
-  dim3 block(bx, 1, 1);
-  dim3 grid((nx + bx - 1) / bx, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-  if (grid.y == 0 || grid.z == 0) return hipSuccess;
+  const ScShape sh = sc_shape<L>(g, false, prop, y0, y1, z0, z1, sc_pass_block_x(g.lat_nx - 2));
+  if (sh.empty) return hipSuccess;
   // the densities-only form: indirect addressing keeps the reference's pass
   const bool vout = !a.sc_local_velocity || (a.options & 1u) || g.indirect;
-  if (sc_xface_in_use(a)) {
-    // connected x faces through planes: edge lanes take the entering populations from the receive planes and store their
-    // densities for the neighbours (the module was checked when the planes were set: slf_module_set_xface_planes)
-    if constexpr (L::dim == 3) {
-      if (g.indirect) return hipErrorInvalidValue;
-      p.xcd_shift = xcd_shift_for(grid.y, grid.x);        // 32 consecutive rows write one line of a plane: one XCD
-#define SLF_SCM_XF(P, G)                                                                                            \
-  do {                                                                                                               \
-    if (vout) hipLaunchKernelGGL((sc_macro_kernel<L, R, P, G, false, true, true>), grid, block, 0, s, p);            \
-    else hipLaunchKernelGGL((sc_macro_kernel<L, R, P, G, false, false, true>), grid, block, 0, s, p);                \
-  } while (0)
-      if (prop == PROP_AA_ODD) {
-        if (general) SLF_SCM_XF(PROP_AA_ODD, true); else SLF_SCM_XF(PROP_AA_ODD, false);
-      } else {          // two-copy and the even in-place step: the node's own slots
-        if (general) SLF_SCM_XF(PROP_AB, true); else SLF_SCM_XF(PROP_AB, false);
-      }
-#undef SLF_SCM_XF
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
+  // connected x faces through planes: edge lanes take the entering populations from the receive planes and store their
+  // densities for the neighbours (the module was checked when the planes were set: slf_module_set_xface_planes)
+  const bool xf = sc_xface_in_use(a);
+  if (xf && (L::dim != 3 || g.indirect)) return hipErrorInvalidValue;
+  if (xf) p.xcd_shift = sh.xcd_shift;        // 32 consecutive rows write one line of a plane: one XCD
   if constexpr (L::dim == 3) {
-    if (!vout && !general && prop == PROP_AA_ODD && sc_row_pull_ok(g)) {
-      hipLaunchKernelGGL((sc_density_pull_kernel<L, R>), grid, block, 0, s, p);
+    if (!xf && !vout && !general && prop == PROP_AA_ODD && sc_row_pull_ok(g)) {
+      hipLaunchKernelGGL((sc_density_pull_kernel<L, R>), sh.grid, sh.block, 0, s, p);
       return hipGetLastError();
     }
   }
-#define SLF_SCM(P)                                                                        \
-  do {                                                                                    \
-    if (g.indirect) hipLaunchKernelGGL((sc_macro_kernel<L, R, P, true, true>), grid, block, 0, s, p); \
-    else if (general && vout) hipLaunchKernelGGL((sc_macro_kernel<L, R, P, true>), grid, block, 0, s, p); \
-    else if (general) hipLaunchKernelGGL((sc_macro_kernel<L, R, P, true, false, false>), grid, block, 0, s, p); \
-    else if (vout) hipLaunchKernelGGL((sc_macro_kernel<L, R, P, false>), grid, block, 0, s, p);        \
-    else hipLaunchKernelGGL((sc_macro_kernel<L, R, P, false, false, false>), grid, block, 0, s, p);        \
-  } while (0)
-  if (prop == PROP_AA_ODD) SLF_SCM(PROP_AA_ODD);
-  else SLF_SCM(PROP_AB);
-#undef SLF_SCM
-  return hipGetLastError();
-}
-
-template <class L, class R, int K>
-static hipError_t sc_sweep3(Prop prop, bool general, bool row, const ScParams<L, R>& p, dim3 grid, dim3 block,
-                            hipStream_t s) {
-  if (p.g.indirect) {      // active-node slots: per-node kernels with translated neighbours
-    if (prop == PROP_AB) hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, PROP_AB, true, false, true>), grid, block, 0, s, p);
-    else if (prop == PROP_AA_EVEN) hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, PROP_AA_EVEN, true, false, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, PROP_AA_ODD, true, false, true>), grid, block, 0, s, p);
-    return hipGetLastError();
-  }
-#define SLF_SCS(P)                                                                           \
-  do {                                                                                       \
-    if (general) hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, P, true>), grid, block, 0, s, p); \
-    else hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, P, false>), grid, block, 0, s, p);        \
-  } while (0)
-#define SLF_SCS_ROW(P)                                                                             \
-  do {                                                                                               \
-    if (general) hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, P, true, true>), grid, block, 0, s, p);   \
-    else hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, P, false, true>), grid, block, 0, s, p);          \
-  } while (0)
-  if constexpr (L::dim == 3) {
-    if (row && prop == PROP_AB) { SLF_SCS_ROW(PROP_AB); return hipGetLastError(); }
-    if (row && prop == PROP_AA_ODD) { SLF_SCS_ROW(PROP_AA_ODD); return hipGetLastError(); }
-  }
-  if (prop == PROP_AB) SLF_SCS(PROP_AB);
-  else if (prop == PROP_AA_EVEN) SLF_SCS(PROP_AA_EVEN);
-  else SLF_SCS(PROP_AA_ODD);
-#undef SLF_SCS
-#undef SLF_SCS_ROW
-  return hipGetLastError();
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
+  // two-copy and the even in-place step: the node's own slots
+  pick<int, PROP_AB, PROP_AA_ODD>(prop == PROP_AA_ODD ? PROP_AA_ODD : PROP_AB, [&](auto P) {
+    pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
+      pick_bool(vout, [&](auto VOUT) { pick_bool(xf, [&](auto XF) {
+        // IND && !G: indirect addressing always reads the node map
+        // IND && !VOUT: indirect addressing keeps the reference's pass, which writes the velocity
+        // IND && XF: no planes with indirect addressing (refused above)
+        // XF && dim != 3: planes are 3-D only (refused above)
+        if constexpr ((IND && (!G || !VOUT || XF)) || (XF && L::dim != 3)) return;
+        else {
+          hipLaunchKernelGGL((sc_macro_kernel<L, R, P, G, IND, VOUT, XF>), sh.grid, sh.block, 0, s, p);
+          e = hipGetLastError();
+        }
+      }); });
+    }); });
+  });
+  return e;
 }
 
 template <class L, class R>
-static hipError_t sc_sweep2(int grid_idx, Prop prop, bool general, const Geometry& g, const Physics& ph,
+static hipError_t sc_sweep2(LR<L, R>, int grid_idx, Prop prop, bool general, const Geometry& g, const Physics& ph,
                             const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
                             hipStream_t s) {
   if (sc_xface_in_use(a)) return hipErrorInvalidValue;       // planes: the fused sweep only
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, grid_idx, y0, z0);
-  const int nx = g.lat_nx - 2;
-  // whole-row workgroups + aligned stores for the x-streaming steps in 3-D (as slf_row.hip)
-  const bool row = L::dim == 3 && (g.variant & 8) && prop != PROP_AA_EVEN && !g.indirect;
-  if (row) block_x = row_block_x(nx);
-  dim3 block(block_x, 1, 1);
-  dim3 grid((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-  if (grid.y == 0 || grid.z == 0) return hipSuccess;
-  p.xcd_shift = xcd_shift_for(grid.y, grid.x);      // the force stencil's rho / phi rows: neighbouring rows on one XCD
-  if (grid_idx == 0) return sc_sweep3<L, R, 0>(prop, general, row, p, grid, block, s);
-  return sc_sweep3<L, R, 1>(prop, general, row, p, grid, block, s);
+  const ScShape sh = sc_shape<L>(g, !g.indirect, prop, y0, y1, z0, z1, block_x);
+  if (sh.empty) return hipSuccess;
+  p.xcd_shift = sh.xcd_shift;
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
+  pick<int, 0, 1>(grid_idx == 0 ? 0 : 1, [&](auto K) { pick_prop(prop, [&](auto P) {
+    pick_bool(general || g.indirect, [&](auto G) { pick_bool(sh.row, [&](auto ROW) { pick_bool(g.indirect, [&](auto IND) {
+      // IND && !G: indirect addressing (active-node slots) always reads the node map
+      // IND && ROW: indirect addressing has per-node kernels with translated neighbours, no whole rows
+      // ROW && (dim != 3 || AA_EVEN): whole rows serve the x-streaming steps in 3-D; the even step does not stream
+      if constexpr ((IND && (!G || ROW)) || (ROW && (L::dim != 3 || P == PROP_AA_EVEN))) return;
+      else {
+        hipLaunchKernelGGL((sc_sweep_kernel<L, R, K, P, G, ROW, IND>), sh.grid, sh.block, 0, s, p);
+        e = hipGetLastError();
+      }
+    }); }); });
+  }); });
+  return e;
 }
-
-#define SLF_DISPATCH_LR(sel, CALL)                                   \
-  do {                                                               \
-    if ((sel).lattice == 0) {                                        \
-      if ((sel).precision == 4) { using L = D2Q9; using R = float; CALL; }  \
-      else { using L = D2Q9; using R = double; CALL; }               \
-    } else {                                                         \
-      if ((sel).precision == 4) { using L = D3Q19; using R = float; CALL; } \
-      else { using L = D3Q19; using R = double; CALL; }              \
-    }                                                                \
-  } while (0)
 
 hipError_t launch_sc_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                            const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (sc_macro2<L, R>(prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return sc_macro2(lr, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, s); });
 }
 
 hipError_t launch_sc_sweep(const KernelSelector& sel, int grid_idx, Prop prop, const Geometry& g, const Physics& ph,
                            const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
                            hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (sc_sweep2<L, R>(grid_idx, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) {
+    return sc_sweep2(lr, grid_idx, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
+  });
 }
 
 template <class L, class R>
-static hipError_t sc_fused2(Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
+static hipError_t sc_fused2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
                             const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
-  const int nx = g.lat_nx - 2;
-  const bool row = L::dim == 3 && (g.variant & 8) && prop != PROP_AA_EVEN;
-  if (row) block_x = row_block_x(nx);
-  dim3 block(block_x, 1, 1);
-  dim3 grid((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-  if (grid.y == 0 || grid.z == 0) return hipSuccess;
-  p.xcd_shift = xcd_shift_for(grid.y, grid.x);      // the force stencil's rho / phi rows: neighbouring rows on one XCD
-  const size_t park = (SLF_SC_PARK && sizeof(R) == 4 && L::Q == 19) ? (size_t)block_x * 5 * 16 : 0;   // lattice 1 parked in LDS
-#define SLF_SCF(P, ROW)                                                                            \
-  do {                                                                                             \
-    if (a.sc_local_velocity) {                                                                     \
-      if (general) hipLaunchKernelGGL((sc_fused_kernel<L, R, P, true, ROW, true>), grid, block, park, s, p);   \
-      else hipLaunchKernelGGL((sc_fused_kernel<L, R, P, false, ROW, true>), grid, block, park, s, p);          \
-    } else {                                                                                       \
-      if (general) hipLaunchKernelGGL((sc_fused_kernel<L, R, P, true, ROW>), grid, block, 0, s, p);   \
-      else hipLaunchKernelGGL((sc_fused_kernel<L, R, P, false, ROW>), grid, block, 0, s, p);          \
-    }                                                                                              \
-  } while (0)
-  if (sc_xface_in_use(a)) {
-    if constexpr (L::dim == 3) {
-      if (!a.sc_local_velocity) return hipErrorInvalidValue;
-#define SLF_SCF_XF(P, ROW)                                                                                                   \
-  do {                                                                                                                        \
-    if (general) hipLaunchKernelGGL((sc_fused_kernel<L, R, P, true, ROW, true, false, true>), grid, block, park, s, p);       \
-    else hipLaunchKernelGGL((sc_fused_kernel<L, R, P, false, ROW, true, false, true>), grid, block, park, s, p);              \
-  } while (0)
-      if (prop == PROP_AA_EVEN) {
-        SLF_SCF_XF(PROP_AA_EVEN, false);
-        return hipGetLastError();
+  const ScShape sh = sc_shape<L>(g, true, prop, y0, y1, z0, z1, block_x);
+  if (sh.empty) return hipSuccess;
+  p.xcd_shift = sh.xcd_shift;
+  const bool ownv = a.sc_local_velocity, xf = sc_xface_in_use(a);
+  // planes: 3-D, the own-velocity sweep, and an x-streaming step is one whole-row workgroup
+  if (xf && (L::dim != 3 || !ownv)) return hipErrorInvalidValue;
+  if (xf && prop != PROP_AA_EVEN && (!sh.row || sh.grid.x != 1)) return hipErrorInvalidValue;
+  const bool pull = !xf && sh.row && prop == PROP_AA_ODD && ownv && sc_row_pull_ok(g) && sh.grid.x == 1;
+  // lattice 1 parked in LDS (own-velocity kernels)
+  const size_t park = (SLF_SC_PARK && ownv && sizeof(R) == 4 && L::Q == 19) ? (size_t)sh.block.x * 5 * 16 : 0;
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
+  pick_prop(prop, [&](auto P) { pick_bool(general, [&](auto G) { pick_bool(sh.row, [&](auto ROW) {
+    pick_bool(ownv, [&](auto OWNV) { pick_bool(pull, [&](auto PULL) { pick_bool(xf, [&](auto XF) {
+      // ROW && (dim != 3 || AA_EVEN): whole rows serve the x-streaming steps in 3-D; the even step does not stream
+      // PULL && !(ROW && OWNV && AA_ODD): aligned loads (sc_pull_rows) exist for the odd step of the whole-row
+      //   own-velocity sweep only
+      // XF && (dim != 3 || !OWNV): planes are 3-D and need the own-velocity sweep (refused above)
+      // XF && PULL: the aligned loads wrap x inside the kernel, planes connect it outside (pull has !xf)
+      // XF && ROW != (P != AA_EVEN): under planes an x-streaming step is always one whole-row workgroup (refused above
+      //   otherwise), and the even step never is (sc_shape)
+      if constexpr ((ROW && (L::dim != 3 || P == PROP_AA_EVEN)) || (PULL && !(ROW && OWNV && P == PROP_AA_ODD)) ||
+                    (XF && (L::dim != 3 || !OWNV || PULL || ROW != (P != PROP_AA_EVEN)))) return;
+      else {
+        hipLaunchKernelGGL((sc_fused_kernel<L, R, P, G, ROW, OWNV, PULL, XF>), sh.grid, sh.block, park, s, p);
+        e = hipGetLastError();
       }
-      if (!row || grid.x != 1) return hipErrorInvalidValue;
-      if (prop == PROP_AB) SLF_SCF_XF(PROP_AB, true);
-      else SLF_SCF_XF(PROP_AA_ODD, true);
-#undef SLF_SCF_XF
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
-  if constexpr (L::dim == 3) {
-    if (row && prop == PROP_AB) { SLF_SCF(PROP_AB, true); return hipGetLastError(); }
-    if (row && prop == PROP_AA_ODD && a.sc_local_velocity && sc_row_pull_ok(g) && grid.x == 1) {
-      if (general) hipLaunchKernelGGL((sc_fused_kernel<L, R, PROP_AA_ODD, true, true, true, true>), grid, block, park, s, p);
-      else hipLaunchKernelGGL((sc_fused_kernel<L, R, PROP_AA_ODD, false, true, true, true>), grid, block, park, s, p);
-      return hipGetLastError();
-    }
-    if (row && prop == PROP_AA_ODD) { SLF_SCF(PROP_AA_ODD, true); return hipGetLastError(); }
-  }
-  if (prop == PROP_AB) SLF_SCF(PROP_AB, false);
-  else if (prop == PROP_AA_EVEN) SLF_SCF(PROP_AA_EVEN, false);
-  else SLF_SCF(PROP_AA_ODD, false);
-#undef SLF_SCF
-  return hipGetLastError();
+    }); }); });
+  }); }); });
+  return e;
 }
 
 hipError_t launch_sc_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen& sc,
                            const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (sc_fused2<L, R>(prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return sc_fused2(lr, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s); });
 }
 
 template <class L, class R>
-static hipError_t scs_launch2(bool macro, Prop prop, bool general, const Geometry& g, const Physics& ph,
+static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, const Geometry& g, const Physics& ph,
                               const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
                               hipStream_t s) {
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
   p.G[0] = (R)sc.G[0];
   p.G[1] = (R)0;
-  const int nx = g.lat_nx - 2;
-  const bool row = !macro && L::dim == 3 && (g.variant & 8) && prop != PROP_AA_EVEN && !g.indirect;
-  if (row) block_x = row_block_x(nx);
-  dim3 block(block_x, 1, 1);
-  dim3 grid((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-  if (grid.y == 0 || grid.z == 0) return hipSuccess;
-  p.xcd_shift = xcd_shift_for(grid.y, grid.x);      // the force stencil's rho / phi rows: neighbouring rows on one XCD
-  if (sc_xface_in_use(a)) {
-    // connected x faces through planes (slf_module_set_xface_planes: sets 0 and 2 of the binary model's three)
-    if constexpr (L::dim == 3) {
-      if (g.indirect) return hipErrorInvalidValue;
-#define SLF_SCS_XF(KERN, P, ...)                                                                             \
-  do {                                                                                                        \
-    if (general) hipLaunchKernelGGL((KERN<L, R, P, true, __VA_ARGS__>), grid, block, 0, s, p);                \
-    else hipLaunchKernelGGL((KERN<L, R, P, false, __VA_ARGS__>), grid, block, 0, s, p);                       \
-  } while (0)
-      if (macro) {
-        if (prop == PROP_AA_ODD) SLF_SCS_XF(scs_macro_kernel, PROP_AA_ODD, false, true);
-        else SLF_SCS_XF(scs_macro_kernel, PROP_AB, false, true);
-        return hipGetLastError();
-      }
-      if (prop == PROP_AA_EVEN) {
-        SLF_SCS_XF(scs_sweep_kernel, PROP_AA_EVEN, false, false, true);
-        return hipGetLastError();
-      }
-      if (!row || grid.x != 1) return hipErrorInvalidValue;
-      if (prop == PROP_AB) SLF_SCS_XF(scs_sweep_kernel, PROP_AB, true, false, true);
-      else SLF_SCS_XF(scs_sweep_kernel, PROP_AA_ODD, true, false, true);
-#undef SLF_SCS_XF
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
-  if (g.indirect) {      // active-node slots: per-node kernels with translated neighbours (the node map is always read)
-    if (macro) {
-      if (prop == PROP_AA_ODD) hipLaunchKernelGGL((scs_macro_kernel<L, R, PROP_AA_ODD, true, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((scs_macro_kernel<L, R, PROP_AB, true, true>), grid, block, 0, s, p);
-    } else {
-      if (prop == PROP_AB) hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AB, true, false, true>), grid, block, 0, s, p);
-      else if (prop == PROP_AA_EVEN) hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AA_EVEN, true, false, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AA_ODD, true, false, true>), grid, block, 0, s, p);
-    }
-    return hipGetLastError();
-  }
-  if constexpr (L::dim == 3) {
-    if (row) {
-      if (prop == PROP_AB) {
-        if (general) hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AB, true, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AB, false, true>), grid, block, 0, s, p);
-      } else {
-        if (general) hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AA_ODD, true, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((scs_sweep_kernel<L, R, PROP_AA_ODD, false, true>), grid, block, 0, s, p);
-      }
-      return hipGetLastError();
-    }
-  }
-#define SLF_SCS1(KERN, P)                                                       \
-  do {                                                                          \
-    if (general) hipLaunchKernelGGL((KERN<L, R, P, true>), grid, block, 0, s, p);  \
-    else hipLaunchKernelGGL((KERN<L, R, P, false>), grid, block, 0, s, p);         \
-  } while (0)
+  const ScShape sh = sc_shape<L>(g, !macro && !g.indirect, prop, y0, y1, z0, z1, block_x);
+  if (sh.empty) return hipSuccess;
+  p.xcd_shift = sh.xcd_shift;
+  // connected x faces through planes (slf_module_set_xface_planes: sets 0 and 2 of the binary model's three): 3-D,
+  // direct addressing, and an x-streaming step of the sweep is one whole-row workgroup
+  const bool xf = sc_xface_in_use(a);
+  if (xf && (L::dim != 3 || g.indirect)) return hipErrorInvalidValue;
+  if (xf && !macro && prop != PROP_AA_EVEN && (!sh.row || sh.grid.x != 1)) return hipErrorInvalidValue;
+  // indirect addressing (active-node slots): per-node kernels with translated neighbours, the node map is always read
+  const bool gen = general || g.indirect;
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
   if (macro) {
-    if (prop == PROP_AA_ODD) SLF_SCS1(scs_macro_kernel, PROP_AA_ODD);
-    else SLF_SCS1(scs_macro_kernel, PROP_AB);
-  } else {
-    if (prop == PROP_AB) SLF_SCS1(scs_sweep_kernel, PROP_AB);
-    else if (prop == PROP_AA_EVEN) SLF_SCS1(scs_sweep_kernel, PROP_AA_EVEN);
-    else SLF_SCS1(scs_sweep_kernel, PROP_AA_ODD);
+    // two-copy and the even in-place step: the node's own slots
+    pick<int, PROP_AB, PROP_AA_ODD>(prop == PROP_AA_ODD ? PROP_AA_ODD : PROP_AB, [&](auto P) {
+      pick_bool(gen, [&](auto G) { pick_bool(g.indirect, [&](auto IND) { pick_bool(xf, [&](auto XF) {
+        // IND && !G: indirect addressing always reads the node map (gen)
+        // IND && XF: no planes with indirect addressing (refused above)
+        // XF && dim != 3: planes are 3-D only (refused above)
+        if constexpr ((IND && (!G || XF)) || (XF && L::dim != 3)) return;
+        else {
+          hipLaunchKernelGGL((scs_macro_kernel<L, R, P, G, IND, XF>), sh.grid, sh.block, 0, s, p);
+          e = hipGetLastError();
+        }
+      }); }); });
+    });
+    return e;
   }
-#undef SLF_SCS1
-  return hipGetLastError();
+  pick_prop(prop, [&](auto P) { pick_bool(gen, [&](auto G) { pick_bool(sh.row, [&](auto ROW) {
+    pick_bool(g.indirect, [&](auto IND) { pick_bool(xf, [&](auto XF) {
+      // IND && !G: indirect addressing always reads the node map (gen)
+      // IND && XF: no planes with indirect addressing (refused above)
+      // XF && dim != 3: planes are 3-D only (refused above)
+      // ROW && (dim != 3 || AA_EVEN): whole rows serve the x-streaming steps in 3-D; the even step does not stream
+      // ROW && IND: indirect addressing has per-node kernels with translated neighbours, no whole rows
+      // XF && ROW != (P != AA_EVEN): under planes an x-streaming step is always one whole-row workgroup (refused above
+      //   otherwise), and the even step never is (sc_shape)
+      if constexpr ((IND && (!G || XF)) || (XF && L::dim != 3) || (ROW && (L::dim != 3 || P == PROP_AA_EVEN || IND)) ||
+                    (XF && ROW != (P != PROP_AA_EVEN))) return;
+      else {
+        hipLaunchKernelGGL((scs_sweep_kernel<L, R, P, G, ROW, IND, XF>), sh.grid, sh.block, 0, s, p);
+        e = hipGetLastError();
+      }
+    }); });
+  }); }); });
+  return e;
 }
 
 hipError_t launch_scs_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                             const ShanChen& sc, const SweepArgs& a, hipStream_t s) {
   const int z0 = g.dim == 3 ? 1 : 0, z1 = g.dim == 3 ? g.lat_nz - 1 : 1;
-  int bx = ((g.lat_nx - 2 + 63) / 64) * 64;
-  if (bx > 1024) bx = 256;
-  SLF_DISPATCH_LR(sel, return (scs_launch2<L, R>(true, prop, sel.general, g, ph, sc, a, 1, g.lat_ny - 1, z0, z1, bx, s)));
-  return hipErrorInvalidValue;
+  const int bx = sc_pass_block_x(g.lat_nx - 2);
+  return pick_lr(sel, [&](auto lr) {
+    return scs_launch2(lr, true, prop, sel.general, g, ph, sc, a, 1, g.lat_ny - 1, z0, z1, bx, s);
+  });
 }
 
 hipError_t launch_scs_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                             const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
                             hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (scs_launch2<L, R>(false, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) {
+    return scs_launch2(lr, false, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
+  });
 }
 
 template <class L, class R>
-static hipError_t sc_init2(const Geometry& g, void* d1, void* d2, const void* rho, const void* phi,
+static hipError_t sc_init2(LR<L, R>, const Geometry& g, void* d1, void* d2, const void* rho, const void* phi,
                            const void* const v[3], const void* nodes, hipStream_t s) {
   dim3 block(256, 1, 1);
   dim3 grid((g.lat_nx + 255) / 256, g.lat_ny, g.lat_nz);
@@ -1251,8 +1181,7 @@ static hipError_t sc_init2(const Geometry& g, void* d1, void* d2, const void* rh
 
 hipError_t launch_sc_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist1, void* dist2,
                           const void* rho, const void* phi, const void* const v[3], const void* nodes, hipStream_t s) {
-  SLF_DISPATCH_LR(sel, return (sc_init2<L, R>(g, dist1, dist2, rho, phi, v, nodes, s)));
-  return hipErrorInvalidValue;
+  return pick_lr(sel, [&](auto lr) { return sc_init2(lr, g, dist1, dist2, rho, phi, v, nodes, s); });
 }
 
 }  // namespace slf

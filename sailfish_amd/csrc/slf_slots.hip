@@ -3,6 +3,7 @@
 // code compile as long as everything else of slf_kernels.hip together, and the library's sources are compiled in parallel
 // (sailfish_amd/build.py).
 #include "../../include/sailfish_hip.h"
+#include "slf_dispatch.h"
 #include "slf_kernels.h"
 #include "slf_node.h"
 #include "slf_sweep.h"
@@ -96,34 +97,23 @@ hipError_t launch_build_slot_table(const Geometry& g, const void* nodes, uint32_
   return hipGetLastError();
 }
 
-template <class L, class R, int MODEL, int PROP>
-static hipError_t slot_sweep3(int bc_level, const SweepParams<L, R>& q, hipStream_t s) {
-  const dim3 sgrid((q.n_slots + 255) / 256, 1, 1), sblock(256, 1, 1);
-  // (single-precision BGK, odd in-place step: the level-0 instantiation comes out of the register allocator with 28 bytes
-  // of scratch at 128 VGPRs where level 1 has none at 124 -- profiles/r06/kernels_resources.txt -- so level 1 serves both)
-  constexpr bool skip0 = sizeof(R) == 4 && MODEL == 0 && PROP == PROP_AA_ODD && L::Q > 9;
-  if constexpr (!skip0) {
-    if (bc_level == 0) {
-      hipLaunchKernelGGL((slot_sweep_kernel<L, R, MODEL, PROP, 0>), sgrid, sblock, 0, s, q);
-      return hipGetLastError();
-    }
-  }
-  if (bc_level <= 1) hipLaunchKernelGGL((slot_sweep_kernel<L, R, MODEL, PROP, 1>), sgrid, sblock, 0, s, q);
-  else hipLaunchKernelGGL((slot_sweep_kernel<L, R, MODEL, PROP, 2>), sgrid, sblock, 0, s, q);
-  return hipGetLastError();
-}
-
-template <class L, class R, int MODEL>
-static hipError_t slot_sweep2(int prop, int bc_level, const SweepParams<L, R>& q, hipStream_t s) {
-  if (prop == PROP_AB) return slot_sweep3<L, R, MODEL, PROP_AB>(bc_level, q, s);
-  if (prop == PROP_AA_EVEN) return slot_sweep3<L, R, MODEL, PROP_AA_EVEN>(bc_level, q, s);
-  return slot_sweep3<L, R, MODEL, PROP_AA_ODD>(bc_level, q, s);
-}
-
 template <class L, class R>
 hipError_t launch_slot_sweep(int model, int prop, int bc_level, const SweepParams<L, R>& q, hipStream_t s) {
-  if (model == 0) return slot_sweep2<L, R, 0>(prop, bc_level, q, s);
-  return slot_sweep2<L, R, 1>(prop, bc_level, q, s);
+  const dim3 sgrid((q.n_slots + 255) / 256, 1, 1), sblock(256, 1, 1);
+  hipError_t e = hipErrorInvalidValue;      // stays if prop is none of the three steps
+  pick<int, 0, 1>(model == 0 ? 0 : 1, [&](auto MODEL) { pick_prop((Prop)prop, [&](auto P) {
+    // (single-precision BGK, odd in-place step: the level-0 instantiation comes out of the register allocator with 28 bytes
+    // of scratch at 128 VGPRs where level 1 has none at 124 -- profiles/r06/kernels_resources.txt -- so level 1 serves both)
+    constexpr bool skip0 = sizeof(R) == 4 && MODEL == 0 && P == PROP_AA_ODD && L::Q > 9;
+    pick<int, 0, 1, 2>(bc_level == 0 && !skip0 ? 0 : (bc_level <= 1 ? 1 : 2), [&](auto BCL) {
+      if constexpr (skip0 && BCL == 0) return;
+      else {
+        hipLaunchKernelGGL((slot_sweep_kernel<L, R, MODEL, P, BCL>), sgrid, sblock, 0, s, q);
+        e = hipGetLastError();
+      }
+    });
+  }); });
+  return e;
 }
 
 template hipError_t launch_slot_sweep<D2Q9, float>(int, int, int, const SweepParams<D2Q9, float>&, hipStream_t);
