@@ -493,6 +493,43 @@ int slf_module_set_x_ghost_unused(slf_module* m, int low, int high);
 /* number of x-threads per workgroup the sweep uses for this module (diagnostics) */
 int slf_module_block_size(slf_module* m, int* threads);
 
+/* ---- flow statistics on the device: the reference's sailfish/stats.py (KineticEnergyEnstrophyMixIn: kernel
+ *      ComputeSquareVelocityAndVorticity, templates/data_processing.mako:35-109, + two GPUArray sums; ReynoldsStatsMixIn:
+ *      the ReduceComputeMoments / ReduceComputeCorrelations ...64 kernels of templates/reynolds_statistics.mako, five
+ *      passes per sample).  Entry points, not slf_kernel_get names: a call is a pass over the fields plus a small launch
+ *      that adds the partial sums the pass left in `workspace`.  3-D modules of either precision; the fields are the
+ *      module's dense arrays real[arr_nz][arr_ny][arr_nx] (ghost layer: any value, it is never read into a result --
+ *      the runner keeps +inf there).  Every sum is double and is formed without floating-point atomics, in an order
+ *      that depends on the lattice size alone: the same fields give the same bits, call after call.  Outputs are
+ *      device pointers; everything is enqueued on `stream`; one workspace serves one call at a time.
+ *        slf_stats_workspace_bytes  size of the workspace of a call (what = SLF_STATS_*).
+ *        slf_stats_ke_enstrophy     out2 = {sum v_sq, sum vort_sq} over the real nodes whose kind in `map` is not
+ *                                   excluded (ghost, unused, propagation-only; map NULL: every real node counts), with
+ *                                   v_sq = (vx vx + vy vy) + vz vz and vort_sq = (wx wx + wy wy) + wz wz of w = curl v,
+ *                                   all in the module's precision; a derivative is (f[+1] - f[-1]) 0.5 where both
+ *                                   neighbours are real nodes of this subdomain and f[+1] - f resp. f - f[-1] on the first
+ *                                   resp. last real layer of the axis (numpy.gradient's first-order edges) -- periodic
+ *                                   axes and faces connected to other subdomains included, and across excluded nodes, as in
+ *                                   the reference.  The sums add the rounded per-node values, so they do not depend on
+ *                                   whether v_sq / vort_sq (both or neither; the reference's fields) are stored; stored,
+ *                                   ghost and excluded entries are 0.  Extents of at least 2 (an extent of 1 is
+ *                                   SLF_ERR_INVALID: its one-sided difference would read the ghost layer).
+ *        slf_stats_profiles         out[k * out_stride + offset + p] = sum over the two other axes of statistic k at
+ *                                   position p = 0 .. n - 1 along `axis` (0 x, 1 y, 2 z): k = 4 i + (m - 1) the m-th power
+ *                                   (m = 1 .. 4, multiplied left to right) of field i of (ux, uy, uz, rho), k = 16 .. 21
+ *                                   ux uy, ux uz, uy uz, ux rho, uy rho, uz rho; the field values are converted to double
+ *                                   first.  EVERY real node enters, the node map is not consulted (reference
+ *                                   reynolds_statistics.mako).  With out_stride = ring size x n and offset = snapshot x n,
+ *                                   `out` is the reference's ring of snapshots, one [ring][n] array per statistic;
+ *                                   offset + n <= out_stride; nothing else of `out` is written. ---- */
+enum { SLF_STATS_KE_ENSTROPHY = 0, SLF_STATS_PROFILES_X = 1, SLF_STATS_PROFILES_Y = 2, SLF_STATS_PROFILES_Z = 3 };
+enum { SLF_STATS_PROFILE_COUNT = 22 };
+int slf_stats_workspace_bytes(slf_module* m, int what, size_t* bytes);
+int slf_stats_ke_enstrophy(slf_module* m, const void* map, const void* vx, const void* vy, const void* vz, void* v_sq,
+                           void* vort_sq, void* workspace, double* out2, slf_stream* stream);
+int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, const void* vz, const void* rho,
+                       void* workspace, double* out, size_t out_stride, size_t offset, slf_stream* stream);
+
 /* ---- step plans (extension): the launch list of ONE time step, built once, enqueued with one call.
  *      The reference enqueues every kernel, event and copy of a step from Python (SubdomainRunner.step(),
  *      subdomain_runner.py:960-974; the boundary / bulk overlap with its event chain, :1028-1058; _send_dists /

@@ -621,6 +621,36 @@ class HIPBackend(placement.VmmMixin):
         _check(self._lib, self._lib.slf_module_set_x_ghost_unused(module.handle, int(bool(low)), int(bool(high))),
                'slf_module_set_x_ghost_unused')
 
+    # -- flow statistics (C ABI slf_stats_*; sailfish_amd/stats.py) ---------------
+    supports_flow_stats = True
+
+    def stats_workspace(self, module, what):
+        """Device workspace of one statistics call: what = hipabi.SLF_STATS_KE_ENSTROPHY | SLF_STATS_PROFILES_X / _Y / _Z."""
+        n = ctypes.c_size_t()
+        _check(self._lib, self._lib.slf_stats_workspace_bytes(module.handle, int(what), ctypes.byref(n)),
+               'slf_stats_workspace_bytes')
+        return self.alloc_buf(size=max(8, n.value))
+
+    def stats_ke_enstrophy(self, module, gpu_map, gpu_v, workspace, out2, gpu_v_sq=0, gpu_vort_sq=0, stream=None):
+        """Enqueues: out2 (device, two doubles) = sum of v^2 and of |curl v|^2 over the nodes `gpu_map` does not exclude
+        (0 / None: over every real node); the two fields are stored as well where both addresses are given."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_stats_ke_enstrophy(module.handle, P(gpu_map or None), P(gpu_v[0]), P(gpu_v[1]),
+                                                           P(gpu_v[2] if len(gpu_v) > 2 else None), P(gpu_v_sq or None),
+                                                           P(gpu_vort_sq or None), P(workspace), P(out2),
+                                                           stream.handle if stream else None), 'slf_stats_ke_enstrophy')
+
+    def stats_profiles(self, module, axis, gpu_v, gpu_rho, workspace, out, out_stride, offset, stream=None):
+        """Enqueues: out[k * out_stride + offset + p] (device doubles) = statistic k = 0 .. 21 summed over the two other
+        axes at position p along `axis` (0, 1, 2 or 'x', 'y', 'z')."""
+        P = ctypes.c_void_p
+        if isinstance(axis, str):
+            axis = 'xyz'.index(axis)
+        _check(self._lib, self._lib.slf_stats_profiles(module.handle, int(axis), P(gpu_v[0]), P(gpu_v[1]),
+                                                       P(gpu_v[2] if len(gpu_v) > 2 else None), P(gpu_rho), P(workspace),
+                                                       P(out), int(out_stride), int(offset),
+                                                       stream.handle if stream else None), 'slf_stats_profiles')
+
     @staticmethod
     def supports_row_classes(desc):
         """Modules the row classes exist for: D3Q19 single-fluid with a node map, direct addressing."""

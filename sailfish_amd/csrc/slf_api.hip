@@ -1434,6 +1434,56 @@ int slf_module_block_size(slf_module* m, int* threads) {
   return SLF_OK;
 }
 
+// ---- flow statistics (slf_stats.hip) ----------------------------------------------------------------------------
+static int check_stats_module(const slf_module* m, const char* what) {
+  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  if (m->geo.dim != 3) return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": 3-D modules only (the statistics read vx, vy and vz)");
+  return SLF_OK;
+}
+
+int slf_stats_workspace_bytes(slf_module* m, int what, size_t* bytes) {
+  if (int e = check_stats_module(m, "slf_stats_workspace_bytes")) return e;
+  if (!bytes) return fail(SLF_ERR_INVALID, "bytes is NULL");
+  if (what < SLF_STATS_KE_ENSTROPHY || what > SLF_STATS_PROFILES_Z)
+    return fail(SLF_ERR_INVALID, "slf_stats_workspace_bytes: what = SLF_STATS_KE_ENSTROPHY | SLF_STATS_PROFILES_X / _Y / _Z");
+  const slf::StatsShape sh = what == SLF_STATS_KE_ENSTROPHY ? slf::stats_ke_shape(m->geo)
+                                                            : slf::stats_profiles_shape(m->geo, what - SLF_STATS_PROFILES_X);
+  *bytes = sh.workspace_doubles * sizeof(double);
+  return SLF_OK;
+}
+
+int slf_stats_ke_enstrophy(slf_module* m, const void* map, const void* vx, const void* vy, const void* vz, void* v_sq,
+                           void* vort_sq, void* workspace, double* out2, slf_stream* stream) {
+  if (int e = check_stats_module(m, "slf_stats_ke_enstrophy")) return e;
+  if (!vx || !vy || !vz) return fail(SLF_ERR_INVALID, "slf_stats_ke_enstrophy: a velocity field is NULL");
+  if (!workspace || !out2) return fail(SLF_ERR_INVALID, "slf_stats_ke_enstrophy: workspace / out2 is NULL");
+  if ((v_sq == nullptr) != (vort_sq == nullptr))
+    return fail(SLF_ERR_INVALID, "slf_stats_ke_enstrophy: v_sq and vort_sq are stored together or not at all");
+  const slf::Geometry& g = m->geo;
+  if (g.lat_nx < 4 || g.lat_ny < 4 || g.lat_nz < 4)
+    return fail(SLF_ERR_INVALID, "slf_stats_ke_enstrophy: an extent of 1 leaves the one-sided difference nothing but the ghost layer");
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  const void* v[3] = {vx, vy, vz};
+  SLF_HIP(slf::launch_stats_ke_enstrophy(m->sel, g, map, v, v_sq, vort_sq, (double*)workspace, out2, native(stream)));
+  return SLF_OK;
+}
+
+int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, const void* vz, const void* rho,
+                       void* workspace, double* out, size_t out_stride, size_t offset, slf_stream* stream) {
+  if (int e = check_stats_module(m, "slf_stats_profiles")) return e;
+  if (axis < 0 || axis > 2) return fail(SLF_ERR_INVALID, "slf_stats_profiles: axis = 0 (x) | 1 (y) | 2 (z)");
+  if (!vx || !vy || !vz || !rho) return fail(SLF_ERR_INVALID, "slf_stats_profiles: a field is NULL");
+  if (!workspace || !out) return fail(SLF_ERR_INVALID, "slf_stats_profiles: workspace / out is NULL");
+  const slf::Geometry& g = m->geo;
+  const int n = (axis == 0 ? g.lat_nx : axis == 1 ? g.lat_ny : g.lat_nz) - 2;
+  if (offset + (size_t)n > out_stride)
+    return fail(SLF_ERR_INVALID, "slf_stats_profiles: offset + positions exceeds out_stride (the snapshot would run into the next statistic)");
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  const void* v[3] = {vx, vy, vz};
+  SLF_HIP(slf::launch_stats_profiles(m->sel, g, axis, v, rho, (double*)workspace, out, out_stride, offset, native(stream)));
+  return SLF_OK;
+}
+
 int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   if (!m || !name || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   KernelKind kk;

@@ -189,4 +189,23 @@ hipError_t launch_resident(const KernelSelector& sel, bool aa, const Geometry& g
 int resident_halo(bool aa, int it0, int steps);
 size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y);
 
+// ---- flow statistics (slf_stats.hip): 3-D lattices, fields in the module's dense layout ----
+// Launch shape of a statistics pass: a function of the lattice size alone, so the order of every addition is too.
+constexpr int STATS_PROFILE_COUNT = 22;   // f, f^2, f^3, f^4 of ux, uy, uz, rho; ux uy, ux uz, uy uz, ux rho, uy rho, uz rho
+struct StatsShape {
+  int block, grid_x;
+  int chunks, per_chunk;       // profiles: workgroups that share one position (one x block), rows / planes each takes
+  size_t workspace_doubles;    // partial sums the pass leaves for its finalize launch
+};
+StatsShape stats_ke_shape(const Geometry& g);
+StatsShape stats_profiles_shape(const Geometry& g, int axis);
+// Sum of v^2 and of |curl v|^2 over the real, non-excluded nodes -> out2[2] (device); map NULL: no node is excluded;
+// v_sq / vort_sq: both NULL or both fields to store (0 on ghost and excluded nodes)
+hipError_t launch_stats_ke_enstrophy(const KernelSelector& sel, const Geometry& g, const void* map, const void* const v[3],
+                                     void* v_sq, void* vort_sq, double* workspace, double* out2, hipStream_t s);
+// out[k * out_stride + offset + p] = sum over the two other axes of statistic k at position p along `axis`
+hipError_t launch_stats_profiles(const KernelSelector& sel, const Geometry& g, int axis, const void* const v[3],
+                                 const void* rho, double* workspace, double* out, size_t out_stride, size_t offset,
+                                 hipStream_t s);
+
 }  // namespace slf

@@ -176,6 +176,9 @@ SIGNATURES = {
                                   POINTER(ctypes.c_uint64)]),
     'slf_peer_selftest_fill': (c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_void_p]),
     'slf_peer_selftest_check': (c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_void_p, POINTER(c_uint32)]),
+    'slf_stats_workspace_bytes': (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
+    'slf_stats_ke_enstrophy': (c_int, [c_void_p] * 10),
+    'slf_stats_profiles': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_size_t, c_void_p]),
     'slf_last_error': (c_char_p, []),
 }
 
@@ -185,6 +188,8 @@ SLF_FORCE_GUO, SLF_FORCE_EDM = 0, 1
 SLF_SUBGRID_NONE, SLF_SUBGRID_LES_SMAGORINSKY = 0, 1
 SLF_INVALID_NODE = 0xffffffff
 SLF_PEER_HANDLE_BYTES, SLF_PEER_CHANNELS = 64, 4
+SLF_STATS_KE_ENSTROPHY, SLF_STATS_PROFILES_X, SLF_STATS_PROFILES_Y, SLF_STATS_PROFILES_Z = range(4)
+SLF_STATS_PROFILE_COUNT = 22
 
 _lib = None
 

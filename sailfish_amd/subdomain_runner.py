@@ -26,7 +26,7 @@ import numpy as np
 
 from sailfish_amd import halo, hipabi, io, subdomain_connection, util, xface
 from sailfish_amd import node_type as nt
-from sailfish_amd.lb_base import LBSim  # noqa: F401  (type reference)
+from sailfish_amd.lb_base import LBMixIn, LBSim
 from sailfish_amd.profile import TimeProfile
 from sailfish_amd.stepqueue import DirectQueue, NotPlannable
 
@@ -876,6 +876,11 @@ class SubdomainRunner(object):
             self._output.dump_node_type(self._subdomain._type_vis_map)
         self._halo.reset()
         self._sim.before_main_loop(self)
+        # mix-ins have before_main_loop routines of their own (reference subdomain_runner.py:1590-1594): a simulation
+        # that overrides the hook, as the reference's kida_vortex.py does, need not call them
+        for c in type(self._sim).mro()[1:]:
+            if issubclass(c, LBMixIn) and not issubclass(c, LBSim) and 'before_main_loop' in vars(c):
+                c.before_main_loop(self._sim, self)
         self.backend.sync_stream(self._calc_stream)
         self.num_fluid_nodes = self._subdomain.num_fluid_nodes
 

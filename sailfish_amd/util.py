@@ -86,3 +86,25 @@ def setup_logger(config, name='sailfish'):
         fh.setLevel(getattr(config, 'loglevel', logging.INFO))
         logger.addHandler(fh)
     return logger
+
+
+def kinetic_energy(velocity):
+    """Mean kinetic energy of the fluid, sum |v|^2 / (2 nodes), of a velocity array [3 (or 2), ...] (reference util.py)."""
+    velocity = np.asarray(velocity)
+    return np.sum(np.square(velocity)) / (2.0 * velocity[0].size)
+
+
+def vorticity(velocity, dx=1.0):
+    """Vorticity array [3, nz, ny, nx] of a 3-D velocity array [3, nz, ny, nx] (components x, y, z; reference util.py):
+    central differences inside, first-order one-sided ones on the outermost layers (numpy.gradient), which is also the
+    stencil of the device kernel behind KineticEnergyEnstrophyMixIn."""
+    ux, uy, uz = velocity[0], velocity[1], velocity[2]
+    dz_ux, dy_ux = np.gradient(ux, dx, axis=(0, 1))
+    dz_uy, dx_uy = np.gradient(uy, dx, axis=(0, 2))
+    dy_uz, dx_uz = np.gradient(uz, dx, axis=(1, 2))
+    return np.array((dy_uz - dz_uy, dz_ux - dx_uz, dx_uy - dy_ux))
+
+
+def enstrophy(velocity, dx):
+    """Enstrophy, sum |curl v|^2 / (2 nodes) (reference util.py)."""
+    return np.sum(np.square(vorticity(velocity, dx))) / (2.0 * velocity[0].size)

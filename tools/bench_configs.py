@@ -92,7 +92,7 @@ def porous_wall_map(nx, ny, nz, fluid_fraction=0.3, radius=12, seed=7):
     return wall
 
 
-def _run(label, sim_cls, geo, settings, bytes_per_update):
+def _run(label, sim_cls, geo, settings, bytes_per_update, extra=None):
     cfg = dict(mode='benchmark', quiet=True, perf_stats_every=0)
     cfg.update(settings)
     ctrl = LBSimulationController(sim_cls, geo, default_config=cfg)
@@ -131,6 +131,8 @@ def _run(label, sim_cls, geo, settings, bytes_per_update):
         else:
             out['GBps_comp'] = round(ctrl.mlups_comp * bytes_per_update / 1e3, 1)   # sweep kernels only
             out['frac_of_8TBps'] = round(ctrl.mlups_comp * bytes_per_update / 8e6, 4)
+    if extra is not None:
+        out.update(extra(ctrl))
     print(json.dumps(out), flush=True)
     for r in ctrl.runners:      # give the device memory back before the next configuration
         r.release()
@@ -141,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -358,6 +360,97 @@ def main():
                        EqualSubdomainsGeometry3D,
                        dict(lat_nx=512, lat_ny=256, lat_nz=256, visc=0.05, subdomains=3, conn_axis='x', access_pattern='AA',
                             max_iters=int(1500 * it), benchmark_sample_from=int(500 * it)), 152))
+    # ---- flow statistics on the device (sailfish.stats; csrc/slf_stats.hip): the 256^3 periodic Kida box in place, first
+    # without statistics, then with a sample every 20 steps -- 11a energy and enstrophy (KineticEnergyEnstrophyMixIn),
+    # 11b the 22 profiles along y (ReynoldsStatsMixIn) -- and the time of ONE statistics call between two stream events.
+    # A sample costs the pass itself, the field stores of the step in front of it and, for 11a, a synchronisation; a
+    # simulation with an after_step hook is also stepped one step at a time.
+    if only & {'11a', '11b'}:
+        from examples.kida_vortex import KidaSim, KidaSubdomain
+        from sailfish.lb_single import LBFluidSim
+        from sailfish.stats import KineticEnergyEnstrophyMixIn, ReynoldsStatsMixIn
+        from sailfish_amd import hipabi
+
+        class PlainKida(LBFluidSim):
+            subdomain = KidaSubdomain
+            update_defaults = KidaSim.update_defaults
+
+        class TimedCalls(object):
+            def timed(self, runner, call):
+                b, s = runner.backend, runner._calc_stream
+                t0 = b.make_event(s, timing=True)
+                res = call(runner)
+                t1 = b.make_event(s, timing=True)
+                t1.synchronize()
+                self.call_ms = getattr(self, 'call_ms', []) + [t1.time_since(t0)]
+                return res
+
+        class EnergyKida(KidaSim, TimedCalls):
+            def after_step(self, runner):
+                mod = self.iteration % self.every
+                if mod == self.every - 1:
+                    self.need_fields_flag = True
+                elif mod == 0:
+                    self.stats.append((self.iteration,) + self.timed(runner, self.compute_ke_enstropy))
+
+        class ProfileKida(PlainKida, ReynoldsStatsMixIn, TimedCalls):
+            every = 20
+
+            def before_main_loop(self, runner):
+                self.prepare_reynolds_stats(runner, axis='y')
+
+            def after_step(self, runner):
+                mod = self.iteration % self.every
+                if mod == self.every - 1:
+                    self.need_fields_flag = True
+                elif mod == 0:
+                    self.timed(runner, self.collect_reynolds_stats)
+
+        def call_times(ctrl):
+            """stat_call_ms: one call as the simulation makes it (11a: with its synchronisation and read-back);
+            stat_pass_ms: the device time of the pass alone, 20 enqueued back to back between two events."""
+            r = ctrl.runners[0]
+            sim, b, s = r._sim, r.backend, r._calc_stream
+            ms = sorted(sim.call_ms)
+            def per_pass(one, n=20):
+                one()
+                t0 = b.make_event(s, timing=True)
+                for _ in range(n):
+                    one()
+                t1 = b.make_event(s, timing=True)
+                t1.synchronize()
+                return round(t1.time_since(t0) / n, 4)
+            if isinstance(sim, KineticEnergyEnstrophyMixIn):
+                def ke(fields):
+                    b.stats_ke_enstrophy(r.module, sim._ke_map, r.gpu_field(sim.v), sim._ke_workspace, sim._ke_gpu_sums,
+                                         r.gpu_field(sim.v_sq) if fields else 0, r.gpu_field(sim.vort_sq) if fields else 0, s)
+                passes = {'stat_pass_ms': per_pass(lambda: ke(True)), 'stat_pass_ms_sums_only': per_pass(lambda: ke(False))}
+            else:
+                passes = {}
+                for ax in range(3):
+                    ws = b.stats_workspace(r.module, hipabi.SLF_STATS_PROFILES_X + ax)
+                    passes['stat_pass_ms_' + 'xyz'[ax]] = per_pass(lambda: b.stats_profiles(
+                        r.module, ax, r.gpu_field(sim.v), r.gpu_field(sim.rho), ws, sim._reyn_gpu_ring,
+                        sim.stat_buf_size * sim._reyn_points, 0, s))
+                passes['stat_pass_ms'] = passes['stat_pass_ms_' + 'xyz'[sim._reyn_axis]]
+            return {'stat_calls': len(ms), 'stat_call_ms_median': round(ms[len(ms) // 2], 4), 'stat_call_ms_min': round(ms[0], 4),
+                    **passes}
+
+        kida256 = dict(lat_nx=256, lat_ny=256, lat_nz=256, grid='D3Q19', access_pattern='AA', max_iters=int(1500 * it),
+                       benchmark_sample_from=int(500 * it))
+        for cid, sim_cls, what in (('11a', EnergyKida, 'energy + enstrophy'), ('11b', ProfileKida, '22 profiles along y')):
+            if cid in only:
+                base = run('%s: D3Q19 BGK periodic Kida box 256^3 (AA), no statistics' % cid, PlainKida, LBGeometry3D, kida256, 152)
+                with_stats = run('%s: the same box, %s every 20 steps' % (cid, what), sim_cls, LBGeometry3D, kida256, 152,
+                                 extra=call_times)
+                step_ms = 256 ** 3 / (base['MLUPS_eff'] * 1e3)
+                summary = {'config': '%s: summary' % cid, 'MLUPS_without': base['MLUPS_eff'], 'MLUPS_with': with_stats['MLUPS_eff'],
+                           'step_ms_without': round(step_ms, 4), 'stat_call_ms_median': with_stats['stat_call_ms_median'],
+                           **dict((k, v) for k, v in with_stats.items() if k.startswith('stat_pass_ms')),
+                           'call_over_step': round(with_stats['stat_call_ms_median'] / step_ms, 3),
+                           'pass_over_step': round(with_stats['stat_pass_ms'] / step_ms, 3)}
+                print(json.dumps(summary), flush=True)
+                res += [base, with_stats, summary]
     if args.out:
         with open(args.out, 'w') as fh:
             for r in filter(None, res):
