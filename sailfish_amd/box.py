@@ -182,15 +182,18 @@ class BoxSim(object):
         self.iteration = 0
         self.backend.set_iteration(0)
 
+    def _sweep_of(self, it, save_macro):
+        """(sweep kernel, copy of the arrays it writes, does it leave the populations in opposite slots) of step `it`:
+        in place one kernel and one copy, the even steps swap; two copies: the kernel and the copy alternate."""
+        ks = self.k_sweep[int(save_macro)]
+        if self.aa:
+            return ks[0], 0, (it & 1) == 0
+        return ks[it & 1], 1 - (it & 1), False
+
     def step(self, save_macro=False, region=None):
         b = self.backend
-        it = self.iteration
-        if self.aa:
-            b.run_kernel(self.k_sweep[int(save_macro)][0], region, self.stream)
-            out, swap = 0, (it & 1) == 0
-        else:
-            b.run_kernel(self.k_sweep[int(save_macro)][it & 1], region, self.stream)
-            out, swap = 1 - (it & 1), False
+        k, out, swap = self._sweep_of(self.iteration, save_macro)
+        b.run_kernel(k, region, self.stream)
         for axis in self.pbc_axes:
             b.run_kernel(self.k_pbc[(out, axis, swap)], None, self.stream)
         self.iteration += 1

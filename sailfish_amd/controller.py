@@ -71,8 +71,7 @@ class LocalGroup(object):
         self.by_id = dict((r._spec.id, r) for r in runners)
         for r in runners:
             r._group = self
-        self._plans = {}
-        self._plan_ok = None
+        self._step_plans = None     # stepqueue.StepPlans, once the runners are prepared
 
     # ---------------------------------------------------------------- the group's step as a program
     def _program(self, q, it, reqs):
@@ -209,34 +208,17 @@ class LocalGroup(object):
         self.single_calc_stream = True
 
     def step(self, reqs):
-        from sailfish_amd.stepqueue import DirectQueue, NotPlannable
+        from sailfish_amd.stepqueue import StepPlans
         rs = self.runners
-        b0 = rs[0].backend
         it = rs[0]._sim.iteration
-        if self._plan_ok is None:
-            self._plan_ok = all(r._plan_ok for r in rs)
-        timed = any(r._profile.wants_gpu_events() for r in rs)
+        if self._step_plans is None:
+            self._step_plans = StepPlans(rs[0].backend, all(r._step_plans.enabled for r in rs))
         for r in rs:
             r._update_dynamic_params(it)
-        plan = None
-        if self._plan_ok and not timed:
-            key = (it & 1, tuple(bool(req[1]) for req in reqs))
-            plan = self._plans.get(key)
-            if plan is None:
-                plan = b0.make_plan()
-                try:
-                    self._program(plan, it, reqs)
-                    self._plans[key] = plan
-                except NotPlannable:
-                    self._plan_ok, plan = False, None
-        if plan is not None:
-            for r in rs:
-                r._set_step_state(it)
-            plan.run(it)
-        else:
-            for r in rs:
-                r.backend.set_iteration(it)
-            self._program(DirectQueue(b0), it, reqs)
+        for r in rs:
+            r._set_step_state(it)
+        self._step_plans.run((it & 1, tuple(bool(req[1]) for req in reqs)), it, lambda q: self._program(q, it, reqs),
+                             [r.backend for r in rs], may_plan=not any(r._profile.wants_gpu_events() for r in rs))
         for r in rs:
             r._halo.unbind()
             r._sim.iteration += 1

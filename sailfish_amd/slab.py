@@ -24,8 +24,9 @@ import os
 import numpy as np
 
 from sailfish_amd import hipabi, sym, xface
-from sailfish_amd.backend_hip import DirectQueue, HIPEvent, NotPlannable
+from sailfish_amd.backend_hip import DirectQueue, HIPEvent
 from sailfish_amd.box import BoxSim, make_box_desc
+from sailfish_amd.stepqueue import StepPlans
 
 AXES = {'x': 0, 'y': 1, 'z': 2}
 
@@ -138,8 +139,8 @@ class SlabSim(BoxSim):
         # (_program), replayed from a C-ABI step plan where the transport allows; exchangers that move whole buffers
         # between step_compute() and step_finish() (tests: two slabs in one process) keep the three-phase protocol
         self.mid_step = hasattr(self.exchanger, 'exchange_range') or self.peer is not None
-        self._plans = {}
-        self._plan_ok = getattr(b, 'supports_step_plans', False) and os.environ.get('SLF_STEP_PLAN', '1') != '0'
+        self._step_plans = StepPlans(b, getattr(b, 'supports_step_plans', False) and os.environ.get('SLF_STEP_PLAN', '1') != '0')
+        self._plans = self._step_plans.plans            # {(it & 1, int(save_macro)): plan}
         tdtype = torch.float32 if self.desc.precision == 4 else torch.float64
         dev = torch.device('cuda', b.gpu_id)
         self.xface = None
@@ -264,11 +265,6 @@ class SlabSim(BoxSim):
             return self._program_xface(q, it, save_macro)
         return self._program_box(q, it, save_macro)
 
-    def _step_kinds(self, it):
-        kind = 'own' if (self.aa and (it & 1) == 0) else 'push'
-        other = 'push' if (not self.aa or kind == 'own') else 'own'        # the step before and the step after
-        return kind, other
-
     def _program_xface_peer(self, q, it, save_macro):
         """x slabs whose send planes ARE the neighbours' receive planes (peer transport).  Calc stream: [wait] chunk
         [wait] chunk ...; halo stream: after every chunk the neighbours' next step counts on, a signal.  A wait is a
@@ -281,8 +277,8 @@ class SlabSim(BoxSim):
         The first step after the counters were drained (self._peer_open is None) has nothing to wait for."""
         from sailfish_amd.peer import CH_DIST
         x, plan, ny = self.xface, self.chunks, self.size[1]
-        k = self.k_sweep[int(save_macro)][0] if self.aa else self.k_sweep[int(save_macro)][it & 1]
-        kind, other = self._step_kinds(it)
+        k = self._sweep_of(it, save_macro)[0]
+        kind, other = xface.step_kinds(self.aa, it)
         par = it & 1
         snd, rcv = x.send[par], x.recv[1 - par]
         q.xface(self.module, snd[xface.LOW], snd[xface.HIGH], rcv[xface.LOW], rcv[xface.HIGH])
@@ -327,10 +323,7 @@ class SlabSim(BoxSim):
         unpack -> event.  The interior sweep depends on the neighbours only through the face layers of the step before
         (what the unpack writes -- the first real layer after a push step, the ghost layer after the even in-place
         step -- is read by the face layers alone), so its stream never waits for a transfer."""
-        if self.aa:
-            k, out, swap = self.k_sweep[int(save_macro)][0], 0, (it & 1) == 0
-        else:
-            k, out, swap = self.k_sweep[int(save_macro)][it & 1], 1 - (it & 1), False
+        k, out, swap = self._sweep_of(it, save_macro)
         ev, pev = self._ev[it & 1], self._ev[1 - (it & 1)]
         sk, sb, sh = self.calc_stream, self.calc_stream2, self.halo_stream
         if self.peer is not None and self._peer_open is not None:
@@ -373,10 +366,7 @@ class SlabSim(BoxSim):
         """Peer transport, z / y slabs: the second half of step `it`'s exchange -- wait for the neighbours' signal of that
         step, unpack what they wrote, record the event the next face layers wait for."""
         from sailfish_amd.peer import CH_DIST
-        if self.aa:
-            out, swap = 0, (it & 1) == 0
-        else:
-            out, swap = 1 - (it & 1), False
+        _, out, swap = self._sweep_of(it, False)
         ks, sh = self.k_halo[(swap, out)], self.halo_stream
         q.peer_wait(self.peer, self.neighbours, CH_DIST, sh, 1)
         q.launch(ks[2], None, sh)
@@ -388,13 +378,9 @@ class SlabSim(BoxSim):
         before it drains); after each chunk the planes of the send buffers it completed travel on the halo stream.  A
         chunk waits for (a) the transfers of the previous step that carry the planes it reads and (b) the chunks of the
         previous step that touched its planes or their neighbours and ran on the other stream."""
-        x, plan, ny = self.xface, self.chunks, self.size[1]
-        k = self.k_sweep[int(save_macro)][0] if self.aa else self.k_sweep[int(save_macro)][it & 1]
-        kind = 'own' if (self.aa and (it & 1) == 0) else 'push'
-        prev_kind = 'push' if (not self.aa or kind == 'own') else 'own'
+        x, plan = self.xface, self.chunks
+        kind, prev_kind = xface.step_kinds(self.aa, it)
         par = it & 1
-        if self.t_sets is not None:
-            self.t_bufs = self.t_sets[par]
         # the z-chunks alternate between the two calc streams only on request (SLF_XFACE_STREAMS=2): a chunk that starts
         # while the one before it drains was measured SLOWER than the drain it avoids (profiles/r04/NOTES.md)
         streams = [self.calc_stream, self.calc_stream2 if os.environ.get('SLF_XFACE_STREAMS', '1') == '2' else self.calc_stream]
@@ -406,35 +392,21 @@ class SlabSim(BoxSim):
             for a in snd:
                 if a:
                     q.memset(a, 0xFF, x.nbytes, streams[0])
-        evc, evb = self._ev_chunk[par], self._ev_batch[par]
-        pevc, pevb = self._ev_chunk[1 - par], self._ev_batch[1 - par]
+        events = (self._ev_chunk[par], self._ev_batch[par], self._ev_chunk[1 - par], self._ev_batch[1 - par])
         # buffers that are not copied (peer transport): a chunk also waits until the planes it writes have been read
         need = plan.peer_need(kind, prev_kind) if x.shared else plan.need[prev_kind]
-        pos_of = dict((c, pos) for pos, c in enumerate(plan.order))
-        sh = self.halo_stream
-        t0 = None
-        waited = {}
-        for pos, c in enumerate(plan.order):
-            st = streams[pos & 1]
-            if need[c] > waited.get(id(st), -1):     # the streams are in order: a later transfer waited for covers the earlier ones
-                q.wait(st, pevb[need[c]])
-                waited[id(st)] = need[c]
-            for c2 in plan.neighbours(c):
-                if streams[pos_of[c2] & 1] is not st:
-                    q.wait(st, pevc[pos_of[c2]])
-            q.launch(k, plan.region(c, ny), st)
-            if not plan.exchanges_at(pos) and streams[0] is streams[1] and not x.shared:
-                continue                 # nothing travels after this chunk and nobody waits for it
-            q.record(evc[pos], st)
-            q.wait(sh, evc[pos])
-            if self.time_halo and not q.planned and t0 is None:
-                t0 = self.backend.make_event(sh, timing=True)
+        t0 = []
+
+        def exchange(pos):
+            if self.time_halo and not q.planned and not t0:
+                t0.append(self.backend.make_event(self.halo_stream, timing=True))
             runs = plan.batches[kind][pos]
-            if runs or x.shared:
+            if runs or x.shared:        # shared planes: nothing to move, but the neighbours count on every signal
                 self._exchange(q, [(p0 * x.plane, (p1 - p0) * x.plane) for p0, p1 in runs])
-            q.record(evb[pos], sh)
-        if t0 is not None:
-            self._halo_events.append((t0, self.backend.make_event(sh, timing=True)))
+        xface.program_chunks(q, plan, self.size[1], [self._sweep_of(it, save_macro)[0]], streams, self.halo_stream, events,
+                             need, x.shared, exchange)
+        if t0:
+            self._halo_events.append((t0[0], self.backend.make_event(self.halo_stream, timing=True)))
 
     def step_compute(self, save_macro=False):
         """Three-phase protocol (exchangers that move whole buffers between step_compute() and step_finish()): face
@@ -444,10 +416,7 @@ class SlabSim(BoxSim):
             return self._step_compute_xface(save_macro)
         b = self.backend
         it = self.iteration
-        if self.aa:
-            k, out, swap = self.k_sweep[int(save_macro)][0], 0, (it & 1) == 0
-        else:
-            k, out, swap = self.k_sweep[int(save_macro)][it & 1], 1 - (it & 1), False
+        k, out, swap = self._sweep_of(it, save_macro)
         if self.ev_halo is not None:
             self.calc_stream.wait_for_event(self.ev_halo)
         for reg in self.regs_bnd:
@@ -469,7 +438,7 @@ class SlabSim(BoxSim):
         moves the face buffers between step_compute() and step_finish()."""
         b = self.backend
         it = self.iteration
-        k = self.k_sweep[int(save_macro)][0] if self.aa else self.k_sweep[int(save_macro)][it & 1]
+        k = self._sweep_of(it, save_macro)[0]
         plan, ny = self.chunks, self.size[1]
         par = self.xface.begin_step(it, self.calc_stream)
         self.t_bufs = self.t_sets[par]
@@ -508,35 +477,16 @@ class SlabSim(BoxSim):
         it = self.iteration
         peer_x = self.peer is not None
         first = peer_x and self._peer_open is None      # nothing of a previous step to wait for: not the plan's program
-        if self._plan_ok and not self.time_halo and not first:
-            key = (it & 1, int(bool(save_macro)))
-            plan = self._plans.get(key)
-            if plan is None:
-                plan = b.make_plan()
-                try:
-                    self._program(plan, it, save_macro)
-                    self._plans[key] = plan
-                except NotPlannable:            # the transport needs Python between the launches
-                    self._plan_ok, plan = False, None
-            if plan is not None:
-                if self.xface is not None and self.t_sets is not None:
-                    self.t_bufs = self.t_sets[it & 1]
-                plan.run(it)
-                self.iteration += 1
-                b.set_iteration(self.iteration)     # kernels launched through run_kernel() next see the new parity
-                if self.xface is not None:
-                    self.xface._bound = None        # the plan set the module's face buffers itself
-                if peer_x:
-                    self._peer_open = self._step_kinds(it)
-                return
-        b.set_iteration(it)
-        self._program(DirectQueue(b), it, save_macro)
+        if self.xface is not None and self.t_sets is not None:
+            self.t_bufs = self.t_sets[it & 1]           # the face buffers this step's exchanges move
+        self._step_plans.run((it & 1, int(bool(save_macro))), it, lambda q: self._program(q, it, save_macro), [b],
+                             may_plan=not self.time_halo and not first)
         self.iteration += 1
-        b.set_iteration(self.iteration)
+        b.set_iteration(self.iteration)     # kernels launched through run_kernel() next see the new parity
         if self.xface is not None:
-            self.xface._bound = None
+            self.xface._bound = None        # the program set the module's face buffers itself
         if peer_x:
-            self._peer_open = self._step_kinds(it)      # (kind of the step just enqueued, kind of the one that follows)
+            self._peer_open = xface.step_kinds(self.aa, it)     # (kind of the step just enqueued, kind of the one that follows)
 
     def release(self):
         BoxSim.release(self)            # (sync() drains the peer counters)
@@ -550,7 +500,7 @@ class SlabSim(BoxSim):
         b = self.backend
         it = self.iteration
         b.set_iteration(it)
-        k = self.k_sweep[0][0] if self.aa else self.k_sweep[0][it & 1]
+        k = self._sweep_of(it, False)[0]
         if self.halo and self.xface is not None:
             self.xface.begin_step(it, self.calc_stream)
             for c in self.chunks.order:

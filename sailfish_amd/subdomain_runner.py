@@ -28,7 +28,7 @@ from sailfish_amd import halo, hipabi, io, subdomain_connection, util, xface
 from sailfish_amd import node_type as nt
 from sailfish_amd.lb_base import LBMixIn, LBSim
 from sailfish_amd.profile import TimeProfile
-from sailfish_amd.stepqueue import DirectQueue, NotPlannable
+from sailfish_amd.stepqueue import StepPlans
 
 
 class GPUBuffer(object):
@@ -455,26 +455,10 @@ class SubdomainRunner(object):
         b = self.backend
         it = self._sim.iteration
         self._update_dynamic_params(it)
-        if self._plan_ok and not self._profile.wants_gpu_events():
-            key = (it & 1, bool(sync_req))
-            plan = self._plans.get(key)
-            if plan is None:
-                plan = b.make_plan()
-                try:
-                    self._program(plan, it, sync_req)
-                    self._plans[key] = plan
-                except NotPlannable:            # the transport needs Python between the launches
-                    self._plan_ok, plan = False, None
-            if plan is not None:
-                self._set_step_state(it)
-                plan.run(it)
-                self._halo.unbind()         # the plan set the module's face buffers itself
-                self._sim.iteration += 1
-                b.set_iteration(self._sim.iteration)
-                return
-        b.set_iteration(it)
-        self._program(DirectQueue(b), it, sync_req)
-        self._halo.unbind()
+        self._set_step_state(it)
+        self._step_plans.run((it & 1, bool(sync_req)), it, lambda q: self._program(q, it, sync_req), [b],
+                             may_plan=not self._profile.wants_gpu_events())
+        self._halo.unbind()         # (a plan sets the module's face buffers itself)
         self._sim.iteration += 1
         b.set_iteration(self._sim.iteration)
 
@@ -495,15 +479,12 @@ class SubdomainRunner(object):
                 self.backend.set_body_force(self.module, self._sim.body_force_at(it))
 
     # ------------------------------------------------------------------ the step as a program (stepqueue.py)
-    _plan_ok = False
-
     def _init_step_program(self):
         """Events, streams and plan table of step() (runners that own their process; a same-process group keeps the
         three-phase step_compute / exchange / step_finish protocol of controller.LocalGroup)."""
         b = self.backend
-        self._plans = {}
-        self._plan_ok = bool(getattr(b, 'supports_step_plans', False)) and getattr(self.config, 'hip_step_plans', True) and \
-            os.environ.get('SLF_STEP_PLAN', '1') != '0'
+        self._step_plans = StepPlans(b, getattr(b, 'supports_step_plans', False) and getattr(self.config, 'hip_step_plans', True) and
+                                     os.environ.get('SLF_STEP_PLAN', '1') != '0')
         names = ('bnd', 'bulk', 'halo', 'packed', 'copied', 'macro', 'macro_halo', 'macro_packed', 'macro_copied')
         self._pev = [dict((n, b.make_event(self._calc_stream)) for n in names) for _ in (0, 1)]
         # a second calc stream (SLF_CALC_STREAMS=1: off).  z / y decompositions sweep their face layers on it: the
@@ -536,7 +517,8 @@ class SubdomainRunner(object):
         self._step_parity = it & 1
 
     # in place the even steps pull, every other step pushes; the copy of the arrays the step writes; its z-chunk batches
-    _step_pulls = property(lambda self: self.config.access_pattern == 'AA' and self._step_parity == 0)
+    _step_pulls = property(lambda self: self._step_parity is not None and
+                           xface.step_kinds(self.config.access_pattern == 'AA', self._step_parity)[0] == 'own')
     _step_copy = property(lambda self: 0 if self.config.access_pattern == 'AA' else 1 - self._step_parity)
     _xface_kind = property(lambda self: 'own' if self._step_pulls else 'push')
 
@@ -670,8 +652,7 @@ class SubdomainRunner(object):
         prof, timed = self._profile, not q.planned
         x, plan = self._xface, self._xchunks
         par = it & 1
-        kind = self._xface_kind
-        prev_kind = 'push' if (self.config.access_pattern != 'AA' or kind == 'own') else 'own'
+        kind, prev_kind = xface.step_kinds(self.config.access_pattern == 'AA', it)
         ny = list(reversed(self._lat_size))[1] - 2
         streams = [self._calc_stream, self._bnd_stream]
         snd, rcv = x.send[par], x.recv[1 - par]
@@ -687,41 +668,27 @@ class SubdomainRunner(object):
             for a in snd:
                 if a:
                     q.memset(a, 0xFF, x.nbytes, streams[0])
-        evc, evb = self._ev_chunk[par], self._ev_batch[par]
-        pevc, pevb = self._ev_chunk[1 - par], self._ev_batch[1 - par]
-        # face buffers that are not copied (the neighbour's receive planes ARE my send planes: peer transport, subdomains of
-        # one process): a chunk also waits until the planes it writes have been read (xface.ChunkPlan.peer_need)
-        need = plan.peer_need(kind, prev_kind) if x.shared else plan.need[prev_kind]
-        every = x.shared and group is None      # a signal after every chunk: the neighbours' chunks count on it
-        pos_of = dict((c, pos) for pos, c in enumerate(plan.order))
-        sh = self._data_stream
         if timed:
             prof.record_gpu_start(TimeProfile.BULK, streams[0])
-        waited = {}
-        for pos, c in enumerate(plan.order):
-            st = streams[pos & 1]
-            if serial:
+        if serial:
+            for pos, c in enumerate(plan.order):
                 for k in kernels:
-                    q.launch(k, plan.region(c, ny), st)
-                continue
-            if need[c] > waited.get(id(st), -1):     # the streams are in order: a later transfer waited for covers the earlier ones
-                q.wait(st, pevb[need[c]])
-                waited[id(st)] = need[c]
-            for c2 in plan.neighbours(c):
-                if streams[pos_of[c2] & 1] is not st:
-                    q.wait(st, pevc[pos_of[c2]])
-            for k in kernels:
-                q.launch(k, plan.region(c, ny), st)
-            if not plan.exchanges_at(pos) and streams[0] is streams[1] and not every:
-                continue                 # nothing travels after this chunk and nobody waits for it
-            q.record(evc[pos], st)
-            if group is None:
-                q.wait(sh, evc[pos])
+                    q.launch(k, plan.region(c, ny), streams[pos & 1])
+        else:
+            events = (self._ev_chunk[par], self._ev_batch[par], self._ev_chunk[1 - par], self._ev_batch[1 - par])
+            # face buffers that are not copied (the neighbour's receive planes ARE my send planes: peer transport, subdomains
+            # of one process): a chunk also waits until the planes it writes have been read (xface.ChunkPlan.peer_need)
+            need = plan.peer_need(kind, prev_kind) if x.shared else plan.need[prev_kind]
+            every = x.shared and group is None      # a signal after every chunk: the neighbours' chunks count on it
+
+            def exchange(pos):
                 self._connector.enqueue_pieces(q, self, self.xface_pieces(pos))
-                q.record(evb[pos], sh)
+            # (a group copies the planes itself, after the fronts of all its runners)
+            xface.program_chunks(q, plan, ny, kernels, streams, self._data_stream, events, need, every,
+                                 exchange if group is None else None)
         if timed:
             if streams[1] is not streams[0]:
-                streams[0].wait_for_event(evc[len(plan.order) - 1])
+                streams[0].wait_for_event(self._ev_chunk[par][len(plan.order) - 1])
             prof.record_gpu_end(TimeProfile.BULK, streams[0])
 
     # ------------------------------------------------------------------ data movement
@@ -1038,44 +1005,58 @@ class SubdomainRunner(object):
         r = self._resident_setup()
         if r is None or n < 2 * r['steps']:
             return 0
-        b, prof, stream = self.backend, self._profile, self._calc_stream
-        it = self._sim.iteration
-        done = 0
-        first = True
-        for count in self.RESIDENT_LAUNCHES:
-            size = count * r['steps']
+        b, stream = self.backend, self._calc_stream
+
+        def enqueue(start, count):
+            def launches():
+                for j in range(count):
+                    b.set_iteration(start + j * r['steps'])
+                    b.run_kernel(r['fwd'] if (j & 1) == 0 else r['bwd'], None, stream)
+            return launches
+
+        def give_up(e):
+            self.config.logger.warning('HIP graph capture of the resident launches failed (%s)' % e)
+            # the path is given up for good: its scratch copies of the arrays and the graphs go with it
+            b.sync_stream(stream)
+            r['graphs'].clear()
+            for _, scratch in r['pairs']:
+                b.free_buf(scratch)
+            self._resident = False
+
+        def equalise():
+            # what no tile covers (padding, the ghost columns of an axis wrapped in-sweep) is the same in both buffers: no
+            # kernel ever writes there, so once is enough -- until the host rewrites the arrays (_debug_set_dist clears
+            # the flag)
+            if not r.get('equalised'):
+                for dist, scratch in r['pairs']:
+                    b.copy_buf_async(scratch, dist, r['nbytes'], stream)
+                r['equalised'] = True
+        return self._replay_graphs(n, 0, self.RESIDENT_LAUNCHES, r['steps'], r['graphs'], stream, enqueue, give_up, equalise)
+
+    def _replay_graphs(self, n, done, sizes, steps, graphs, stream, enqueue, capture_failed, before_first=None):
+        """Of the coming n host-free steps, `done` of which are behind us already: as many as whole graphs cover.  sizes:
+        launches per graph, largest first, `steps` steps each; graphs: {(launches, parity of the first step): graph},
+        captured on first use from enqueue(first step, launches) on `stream`.  A capture that fails ends the loop after
+        capture_failed(error).  before_first(): once, in front of the first launch.  Returns the steps done in all."""
+        b, prof = self.backend, self._profile
+        it = self._sim.iteration - done
+        for count in sizes:
+            size = count * steps
             while n - done >= size:
                 key = (count, (it + done) & 1)
-                if key not in r['graphs']:
-                    start = it + done
-
-                    def enqueue():
-                        for j in range(count):
-                            b.set_iteration(start + j * r['steps'])
-                            b.run_kernel(r['fwd'] if (j & 1) == 0 else r['bwd'], None, stream)
+                if key not in graphs:
                     try:
-                        r['graphs'][key] = b.capture_graph(stream, enqueue)
+                        graphs[key] = b.capture_graph(stream, enqueue(it + done, count))
                     except b.FatalError as e:
-                        self.config.logger.warning('HIP graph capture of the resident launches failed (%s)' % e)
-                        # the path is given up for good: its scratch copies of the arrays and the graphs go with it
-                        b.sync_stream(stream)
-                        r['graphs'].clear()
-                        for _, scratch in r['pairs']:
-                            b.free_buf(scratch)
-                        self._resident = False
+                        capture_failed(e)
                         b.set_iteration(self._sim.iteration)
                         return done
-                if first and not r.get('equalised'):
-                    # what no tile covers (padding, the ghost columns of an axis wrapped in-sweep) is the same in both
-                    # buffers: no kernel ever writes there, so once is enough -- until the host rewrites the arrays
-                    # (_debug_set_dist clears the flag)
-                    for dist, scratch in r['pairs']:
-                        b.copy_buf_async(scratch, dist, r['nbytes'], stream)
-                    r['equalised'] = True
-                first = False
+                if before_first is not None:
+                    before_first()
+                    before_first = None
                 prof.start_step()
                 prof.record_gpu_start(TimeProfile.BULK, stream)
-                r['graphs'][key].launch(stream)
+                graphs[key].launch(stream)
                 prof.record_gpu_end(TimeProfile.BULK, stream, steps=size)
                 done += size
                 self._sim.iteration = it + done
@@ -1095,36 +1076,20 @@ class SubdomainRunner(object):
             return 0
         b = self.backend
         done = self._fast_forward_resident(n)
-        it = self._sim.iteration - done
-        graphs = self.__dict__.setdefault('_graphs', {})
-        prof = self._profile
-        for size in self.GRAPH_STEPS:
-            while n - done >= size:
-                key = (size, (it + done) & 1)
-                if key not in graphs:
-                    start = it + done
 
-                    def enqueue():
-                        for s_ in range(size):
-                            b.set_iteration(start + s_)
-                            self._enqueue_plain_step(start + s_)
-                    try:
-                        graphs[key] = b.capture_graph(self._calc_stream, enqueue)
-                    except b.FatalError as e:
-                        # nothing was executed; carry on with plain launches
-                        self.config.logger.warning('HIP graph capture failed (%s); continuing without graphs' % e)
-                        self.config.hip_graphs = False
-                        b.set_iteration(self._sim.iteration)
-                        return done
-                prof.start_step()
-                prof.record_gpu_start(TimeProfile.BULK, self._calc_stream)
-                graphs[key].launch(self._calc_stream)
-                prof.record_gpu_end(TimeProfile.BULK, self._calc_stream, steps=size)
-                done += size
-                self._sim.iteration = it + done
-                prof.end_step(size)
-        b.set_iteration(self._sim.iteration)
-        return done
+        def enqueue(start, count):
+            def steps():
+                for s_ in range(start, start + count):
+                    b.set_iteration(s_)
+                    self._enqueue_plain_step(s_)
+            return steps
+
+        def carry_on(e):
+            # nothing was executed; carry on with plain launches
+            self.config.logger.warning('HIP graph capture failed (%s); continuing without graphs' % e)
+            self.config.hip_graphs = False
+        return self._replay_graphs(n, done, self.GRAPH_STEPS, 1, self.__dict__.setdefault('_graphs', {}), self._calc_stream,
+                                   enqueue, carry_on)
 
     def _quit_requested(self):
         return self._quit_event is not None and self._quit_event.is_set()

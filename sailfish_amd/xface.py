@@ -186,6 +186,44 @@ class ChunkPlan(object):
         return out
 
 
+def step_kinds(aa, it):
+    """(kind of step `it`, kind of the step before it and of the step after it): in place (aa) the even steps are
+    'own' and the odd ones 'push'; with two copies every step is 'push'."""
+    kind = 'own' if (aa and (it & 1) == 0) else 'push'
+    return kind, 'push' if (not aa or kind == 'own') else 'own'
+
+
+def program_chunks(q, plan, ny, kernels, streams, data_stream, events, need, every, after_chunk):
+    """The sweep of one step in the z-chunks of `plan`, as entries of the step queue `q` (stepqueue.py), with the transfer
+    that follows each chunk.  streams: the two calc streams, chunk position pos runs on streams[pos & 1] (twice the same
+    stream: everything in order).  events = (evc, evb, pevc, pevb): per position, 'chunk swept' and 'its transfer done' of
+    this step and of the step before.  need[c]: the position of the previous step whose transfer chunk c waits for (-1:
+    none; ChunkPlan.need / peer_need).  every: record evc after every chunk, also where nothing travels (somebody counts
+    on a signal per chunk).  after_chunk(pos) issues the transfer on the data stream, between its wait for evc[pos] and
+    the record of evb[pos]; None: somebody else moves the planes, on evc[pos] (a same-process group, after the sweeps of
+    all its runners)."""
+    evc, evb, pevc, pevb = events
+    pos_of = dict((c, pos) for pos, c in enumerate(plan.order))
+    waited = {}
+    for pos, c in enumerate(plan.order):
+        st = streams[pos & 1]
+        if need[c] > waited.get(id(st), -1):     # the streams are in order: a later transfer waited for covers the earlier ones
+            q.wait(st, pevb[need[c]])
+            waited[id(st)] = need[c]
+        for c2 in plan.neighbours(c):            # chunks of the previous step that touched these planes on the other stream
+            if streams[pos_of[c2] & 1] is not st:
+                q.wait(st, pevc[pos_of[c2]])
+        for k in kernels:
+            q.launch(k, plan.region(c, ny), st)
+        if not plan.exchanges_at(pos) and streams[0] is streams[1] and not every:
+            continue                 # nothing travels after this chunk and nobody waits for it
+        q.record(evc[pos], st)
+        if after_chunk is not None:
+            q.wait(data_stream, evc[pos])
+            after_chunk(pos)
+            q.record(evb[pos], data_stream)
+
+
 class XFaceHalo(object):
     def __init__(self, backend, module, grid, desc, send, recv, shared=False):
         """send / recv: [parity][face] device addresses of buffers of face_count(desc) reals each, 0 for a face that
