@@ -50,7 +50,8 @@ class LBSim(object):
                                 'AA (single domain copy in memory).')
         group.add_argument('--node_addressing', type=str, default='direct', choices=('direct', 'indirect'),
                            help='Node addressing mode: direct (dense arrays) or indirect (populations stored for the active '
-                                'nodes only; single-fluid models).')
+                                'nodes only; single-fluid models).  With --access_pattern=AA the active-node map has '
+                                'to keep the layer of nodes behind half-way bounce-back walls (refused otherwise).')
         group.add_argument('--minimize_roundoff', action='store_true', default=False,
                            help='tries to minimize round-off errors: the arrays hold f - w and the density field '
                                 'rho - 1, so that O(1) and O(Ma) quantities are never added (reference sym.py:573-661); '

@@ -206,7 +206,49 @@ class SubdomainRunner(object):
             kw['fluid_only'] = 0
             kw['node_addressing'] = hipabi.SLF_ADDR_INDIRECT
             kw['dist_stride'] = (self._subdomain.active_nodes + 1 + 31) // 32 * 32   # + one spare slot (halo lists)
+            self._check_halfbb_targets()
         return hipabi.make_desc(**kw)
+
+    def _check_halfbb_targets(self):
+        """Indirect addressing, in-place pattern: a half-way bounce-back node is a wet node whose even step stores the
+        population it reflects into the slot of the node behind the wall (slf_sweep.h; reference boundary.mako:653-683 with
+        propagation.mako:93-99).  A node without a slot cannot take it: the sweep would drop the store and the run would go on
+        with a population missing on every such link -- finite, and another flow.  (The reference indexes nodes[] unguarded
+        there.)  Refused here, before anything is built or launched."""
+        if self.config.access_pattern != 'AA':
+            return                                  # the two-copy step stores into the node's own slot
+        sub = self._subdomain
+        pos = np.argwhere(sub.visualization_map() == nt.NTHalfBBWall.id)        # real nodes, numpy axis order
+        if not len(pos):
+            return
+        grid = self._sim.grid
+        codes = sub._orientation[tuple(pos.T)].astype(np.int64)                 # link tags, or an orientation code
+        tagged = bool(getattr(self.config, 'use_link_tags', True))
+        mask = sub.active_node_mask
+        shape = np.array(sub.lat_shape)
+        wrap = list(reversed(self._local_periodic()))
+        es = self._spec.envelope_size
+        lost = np.zeros(len(pos), dtype=np.int64)
+        for bit, vec in enumerate(grid.basis[1:]):
+            if tagged:
+                missing = ((codes >> bit) & 1) == 0                             # the direction points to a non-fluid node
+            else:
+                normal = np.array([grid.dir_to_vec(int(c)) if c else [0] * self.dim for c in codes])
+                missing = (normal * np.array([int(c) for c in vec])).sum(axis=1) < 0
+            target = pos + np.array([int(c) for c in reversed(vec)])
+            for axis in range(self.dim):
+                if wrap[axis]:
+                    target[:, axis] %= shape[axis]
+            lost += missing & ~mask[tuple((target + es).T)]
+        if lost.any():
+            first = pos[np.nonzero(lost)[0][0]]
+            where = tuple(int(c) + int(o) for c, o in zip(reversed(first), self._spec.location))
+            raise ValueError('--node_addressing=indirect with --access_pattern=AA: %d links of half-way bounce-back nodes point '
+                             'to nodes that own no slot in the distribution arrays (first at node %s): the populations '
+                             'reflected there would be lost.  Keep the layer behind half-way bounce-back walls in the '
+                             'active-node map (count those wall nodes as fluid in the wall map given to '
+                             'set_active_node_map_from_wall_map), or use full-way bounce-back walls or the two-copy '
+                             'pattern (--access_pattern=AB).' % (int(lost.sum()), where))
 
     @property
     def indirect(self):
@@ -330,6 +372,14 @@ class SubdomainRunner(object):
                 self._gpu_grids_primary.append(b.alloc_buf(size=nbytes, align_offset=off))
                 if ab:
                     self._gpu_grids_secondary.append(b.alloc_buf(size=nbytes, align_offset=off))
+        if self.indirect:
+            # the spare slot the halo lists route slot-less nodes to (and the padding behind it) is written by no sweep: it
+            # starts as the "never written" sentinel the halo kernels do not deliver, like the ghost slots of dense arrays
+            # (whose fields start from +inf) -- a zero would travel into the slot of a wall node across the seam
+            fill = np.zeros((self._sim.grid.Q, self._dist_stride), dtype=self.float)
+            fill[:, self._subdomain.active_nodes:] = np.nan
+            for addr in self._gpu_grids_primary + self._gpu_grids_secondary:
+                b.to_buf(addr, fill)
         self.config.logger.debug('distributions: %d MiB' % (nbytes * (2 if self._gpu_grids_secondary else 1) >> 20))
 
     placement_tuning = None
@@ -737,6 +787,7 @@ class SubdomainRunner(object):
             addr = self._host_indirect_address.reshape(-1)
             act = addr != hipabi.SLF_INVALID_NODE
             raw[:, addr[act]] = dense[:, act]
+            raw[:, self._subdomain.active_nodes:] = np.nan       # the spare slot: never written (_alloc_distributions)
         else:
             raw[:, :self._get_nodes()] = dense
         self.backend.to_buf(self.gpu_dist(grid_num, copy), raw)
