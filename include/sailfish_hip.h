@@ -86,8 +86,14 @@ enum {
                                      step, the opposite slot of the ghost node behind it in an even one); two-copy pattern: a
                                      plain fluid node (node_type.py:296-307); refused with indirect addressing (ghost nodes own
                                      no slot) */
-  SLF_NK_SLIP = 15                /* NTSlip, boundary.mako:837-855 + sym.py:481-497: dry node, specular reflection -- every
+  SLF_NK_SLIP = 15,               /* NTSlip, boundary.mako:837-855 + sym.py:481-497: dry node, specular reflection -- every
                                      population with a component along the normal swaps with its mirror image */
+  SLF_NK_WALL_TMS = 16            /* NTWallTMS, boundary.mako:631-648, 696-723: Tamm-Mott-Smith wall (Chikatamarla & Karlin,
+                                     Physica A 392 (2013) 1925) -- a wet node with link tags or an orientation, like
+                                     SLF_NK_HALF_BB: the unknown populations are replaced by the equilibrium of the target
+                                     state (the moments of the populations as loaded), every population gets
+                                     feq(target) - feq(instantaneous) after the collision, then the half-way bounce-back
+                                     store.  Single-fluid modules; not CollideAndPropagateResident */
 };
 
 #define SLF_MAX_NODE_TYPES 16

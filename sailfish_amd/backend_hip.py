@@ -657,7 +657,8 @@ class HIPBackend(placement.VmmMixin):
         return (desc.lattice == hipabi.SLF_D3Q19 and not desc.fluid_only and not int(desc.node_addressing) and
                 not int(desc.simtype) and int(desc.incompressible) != hipabi.SLF_DENSITY_ROUNDOFF and
                 not int(desc.regularized) and not int(desc.subgrid) and
-                int(desc.model) != hipabi.SLF_ELBM)      # (those run the per-node kernels)
+                int(desc.model) != hipabi.SLF_ELBM and
+                hipabi.SLF_NK_WALL_TMS not in list(desc.type_kind[:desc.n_types]))      # (those run the per-node kernels)
 
     # -- streams / events -----------------------------------------------------
     def poll_invalid(self, module, stream):

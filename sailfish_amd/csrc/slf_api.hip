@@ -1007,11 +1007,16 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
   g.param_mask = (1u << d->nt_param_shift) - 1u;
   g.orient_shift = d->nt_misc_shift + d->nt_param_shift + d->nt_scratch_shift;
   g.type_lut = 0;
+  m->phys.tms_mask = 0;
   for (int i = 0; i < d->n_types; i++) {
-    const int k = d->type_kind[i];
+    int k = d->type_kind[i];
     if (k < 0 || k >= slf::NK_COUNT) {
       delete m;
       return fail(SLF_ERR_UNSUPPORTED, "node type kind not supported by the HIP backend");
+    }
+    if (k == SLF_NK_WALL_TMS) {      // inside the kernels: a half-way bounce-back type with a flag (slf_kernels.h)
+      m->phys.tms_mask |= 1u << i;
+      k = slf::NK_HALF_BB;
     }
     g.type_lut |= (unsigned long long)k << (4 * i);
   }
@@ -1083,6 +1088,11 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
     }
     g.variant = 0;       // per-node kernels: the tuned / whole-row ones implement the plain collision
   }
+  if (ph.tms_mask && d->fluid_only) {
+    delete m;
+    return fail(SLF_ERR_UNSUPPORTED, "NTWallTMS nodes are node types: the module must read the node map (fluid_only = 0)");
+  }
+  if (ph.tms_mask) g.variant = 0;       // Tamm-Mott-Smith walls: the per-node kernels and the slot sweep carry their code
   ph.entropic_equilibrium = d->entropic_equilibrium != 0;
   ph.entropy_tolerance = d->entropy_tolerance;
   ph.alpha_tolerance = d->alpha_tolerance;
@@ -1116,11 +1126,12 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
     for (int i = 0; ok && i < d->n_types; i++) {
       const int k = d->type_kind[i];
       ok = k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-           k == SLF_NK_FULL_BB || k == SLF_NK_HALF_BB || k == SLF_NK_EQUILIBRIUM_DENSITY || k == SLF_NK_EQUILIBRIUM_VELOCITY;
+           k == SLF_NK_FULL_BB || k == SLF_NK_HALF_BB || k == SLF_NK_WALL_TMS || k == SLF_NK_EQUILIBRIUM_DENSITY ||
+           k == SLF_NK_EQUILIBRIUM_VELOCITY;
     }
     if (!ok) {
       delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "minimize_roundoff: BGK single-fluid modules with fluid, bounce-back and equilibrium "
+      return fail(SLF_ERR_UNSUPPORTED, "minimize_roundoff: BGK single-fluid modules with fluid, bounce-back, TMS wall and equilibrium "
                                        "density / velocity nodes only (the reference's regularized and Zou-He expressions are "
                                        "inconsistent under the option)");
     }
@@ -1522,9 +1533,9 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
     if (g.axis_mode[0] == 1 || g.axis_mode[1] == 1)
       return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: periodic axes must be wrapped in-sweep (periodic_fused)");
     for (int t = 0; t < 16; t++) {
-      const int kind = (int)((g.type_lut >> (4u * t)) & 0xFull);
+      const int kind = slf::type_kind(g.type_lut, (uint32_t)t);
       if (kind == slf::NK_HALF_BB || kind == slf::NK_COPY || kind == slf::NK_YU_OUTFLOW || kind == slf::NK_DO_NOTHING)
-        return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: half-way bounce-back, outflow and do-nothing nodes read / "
+        return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: half-way bounce-back, TMS wall, outflow and do-nothing nodes read / "
                                          "write memory from their node code");
     }
   }

@@ -39,6 +39,15 @@ struct Geometry {
   int x_ghost_unused;
 };
 
+// Decoding a node code: the NodeKind (slf_node.h) of a dense type id and of a node code.  The LUT and the mask are passed
+// as values (call sites: g.type_lut, g.type_mask).
+__host__ __device__ __forceinline__ int type_kind(unsigned long long type_lut, uint32_t dense_type) {
+  return (int)((type_lut >> (4u * dense_type)) & 0xFull);
+}
+__host__ __device__ __forceinline__ int node_kind(unsigned long long type_lut, uint32_t type_mask, uint32_t code) {
+  return type_kind(type_lut, code & type_mask);
+}
+
 struct Physics {
   double tau, visc;
   double accel[3];
@@ -53,6 +62,11 @@ struct Physics {
   // --model=elbm (slf_module_desc; templates/entropic.mako): per-node kernels only
   int entropic_equilibrium;
   double entropy_tolerance, alpha_tolerance;
+  // NTWallTMS (Tamm-Mott-Smith wall): bit t set = dense type id t is a TMS wall; 0: the module has none.  Inside the kernels
+  // such a type is a half-way bounce-back type (its entry in Geometry::type_lut) with this flag (SweepParams::tms_mask),
+  // read only by the boundary-condition code of the instantiations launched for modules that have one
+  // (node_update<..., TMS = true>, slf_sweep.h).  Kept out of Geometry, which every kernel of the library takes by value.
+  uint32_t tms_mask;
 };
 
 struct ShanChen {

@@ -26,7 +26,9 @@ namespace slf {
 // TURB (--regularized / --subgrid): workgroups of at most 512 threads, i.e. 256 VGPRs -- the non-equilibrium flux tensor on
 // top of the collision does not fit the 128 of a 1024-thread workgroup (76-152 bytes of scratch per lane in the odd step).
 // MODEL = 2 (--model=elbm): the same bound -- f and fneq stay live across the Newton solve.
-template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false>
+// TMS: the instantiations for modules with Tamm-Mott-Smith wall nodes (node_update<..., TMS>, slf_sweep.h).
+template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false,
+          bool TMS = false>
 __global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const int gy = p.y0 + (int)blockIdx.y;
@@ -50,7 +52,7 @@ __global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kerne
   uint32_t code = 0;
   if constexpr (GENERAL) {
     code = p.map[gi];
-    kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    kind = node_kind(g.type_lut, g.type_mask, code);
     if (kind_is_excluded(kind)) return;
   }
 
@@ -74,7 +76,7 @@ __global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kerne
 
   R rho, v[3];
   bool wet = true;
-  node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+  node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
 
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   // ---- macroscopic output (save_macro_fields, kernel_common.mako:213-240)
@@ -316,7 +318,7 @@ __global__ void __launch_bounds__(1024) macro_kernel(const SweepParams<L, R> p) 
   int kind = NK_FLUID;
   if constexpr (GENERAL) {
     const uint32_t code = p.map[gi];
-    kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    kind = node_kind(g.type_lut, g.type_mask, code);
     if (!kind_is_wet(kind)) return;
   }
   const AxisOff ox = axis_off(gx, g.lat_nx, 1, g.wrap[0]);
@@ -377,15 +379,16 @@ static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, co
   hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
   pick<int, 0, 1, 2>(model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
     pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
-      pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) {
+      pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) { pick_bool(ph.tms_mask != 0, [&](auto TMS) {
         // indirect addressing: the node map is always read; --minimize_roundoff and --regularized / --subgrid exclude
-        // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only
-        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0)) return;
+        // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only;
+        // Tamm-Mott-Smith walls are node types: no such instantiation without the node map
+        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0) || (TMS && !G)) return;
         else {
-          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB>), grid, block, 0, s, p);
+          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS>), grid, block, 0, s, p);
           e = hipGetLastError();
         }
-      }); });
+      }); }); });
     }); });
   }); });
   return e;

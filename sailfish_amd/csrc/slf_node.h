@@ -35,9 +35,13 @@ enum NodeKind : int {
   NK_YU_OUTFLOW = 13,
   NK_DO_NOTHING = 14,       // in-place pattern: keeps its unknown populations (slf_sweep.h); two-copy pattern: a fluid node
   NK_SLIP = 15,             // dry: specular reflection (slip_reflect)
-  NK_COUNT = 16
+  NK_LUT_COUNT = 16,        // what fits the 4-bit LUT; the kinds below exist in module descriptors only
+  NK_WALL_TMS = 16,         // Tamm-Mott-Smith wall: in the LUT a NK_HALF_BB type, told apart by SweepParams::tms_mask
+  NK_COUNT = 17
 };
 
+// (Kinds as the LUT holds them, 0 .. 15: a TMS wall is NK_HALF_BB there and wet as such.  A test for NK_WALL_TMS here would
+// never be true in a kernel and still changed the code the compiler makes of the chain: profiles/r10/README.md.)
 SLF_HD bool kind_is_wet(int k) {
   return k == NK_FLUID || k == NK_HALF_BB || k == NK_REGULARIZED_VELOCITY || k == NK_EQUILIBRIUM_DENSITY ||
          k == NK_EQUILIBRIUM_VELOCITY || k == NK_ZOUHE_VELOCITY || k == NK_ZOUHE_DENSITY ||
@@ -562,6 +566,21 @@ SLF_D void regularized_bc(R (&f)[L::Q], R rho, R rho0, const R (&v)[3]) {
     const R val = feq<L, R, I>(rho, rho0, v, u15) + Weights<L, R>::w45(I) * acc;
     f[I] = val > (R)1e-7 ? val : (R)1e-7;
   });
+}
+
+// Tamm-Mott-Smith wall (NTWallTMS; Chikatamarla & Karlin, Physica A 392 (2013) 1925; reference boundary.mako:631-648,
+// 696-723).  Before the collision the node's unknown populations are replaced by the equilibrium of the target state
+// (tg_rho, tg_v) = the standard moments of the populations as loaded; after it every population gets
+// feq_i(tg_rho, tg_v) - feq_i(rho, v) with the instantaneous density and the velocity the relaxation left (u + a/2 under a
+// body force), in two passes like the reference: all additions first, then all subtractions.  rho0 / tg_rho0: the
+// equilibrium's second density (1 incompressible, rho + 1 under --minimize_roundoff, else rho).
+template <class L, class R>
+SLF_D void tms_add_equilibrium_difference(R (&f)[L::Q], R tg_rho, R tg_rho0, const R (&tg_v)[3], R rho, R rho0,
+                                          const R (&v)[3]) {
+  const R tg_u15 = usq15<L, R>(tg_v);
+  static_for<0, L::Q>([&](auto I) { f[I] = f[I] + feq<L, R, I>(tg_rho, tg_rho0, tg_v, tg_u15); });
+  const R u15 = usq15<L, R>(v);
+  static_for<0, L::Q>([&](auto I) { f[I] = f[I] - feq<L, R, I>(rho, rho0, v, u15); });
 }
 
 SLF_D float slf_sqrt(float x) { return sqrtf(x); }

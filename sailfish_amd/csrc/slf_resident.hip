@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(1024) resident_kernel(const ResidentParams<L, 
       if constexpr (GENERAL) {
         if (active) {
           code = p.map[gi];
-          const int kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+          const int kind = node_kind(g.type_lut, g.type_mask, code);
           active = !kind_is_excluded(kind);
           simple = kind == NK_FLUID || kind == NK_FULL_BB;
         }
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(1024) resident_kernel(const ResidentParams<L, 
         if (simple) {
           flags |= RI_SIMPLE;
           if constexpr (GENERAL) {
-            if ((int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull) == NK_FULL_BB) flags |= RI_WALL;
+            if (node_kind(g.type_lut, g.type_mask, code) == NK_FULL_BB) flags |= RI_WALL;
           }
         } else {
           s_complex[atomicAdd(&s_ncomplex, 1u)] = (uint16_t)n;
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(1024) resident_kernel(const ResidentParams<L, 
     int kind = (flags & RI_WALL) ? NK_FULL_BB : NK_FLUID;
     if constexpr (GENERAL && decltype(BCL)::value != 0) {
       code = codes[n];
-      kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+      kind = node_kind(g.type_lut, g.type_mask, code);
     }
     R rho, v[3];
     bool wet = true;

@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(1024, (row_min_waves<R, MODEL, GENERAL, FORCE,
   if constexpr (GENERAL) {
     if (cls != 0) {
       code = p.map[gi];
-      kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+      kind = node_kind(g.type_lut, g.type_mask, code);
       active = live && !kind_is_excluded(kind);
     }
   }
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(1024, (BCL == 0 ? row_min_waves<R, MODEL, GENE
   if constexpr (GENERAL) {
     if (cls != 0) {
       code = p.map[gi];
-      kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+      kind = node_kind(g.type_lut, g.type_mask, code);
       if (kind_is_excluded(kind)) return;
     }
   }
@@ -325,7 +325,7 @@ __global__ void __launch_bounds__(256) classify_rows_kernel(const uint32_t* __re
     int level = 0;
     if (x <= nx) {
       const uint32_t code = map[row + (uint32_t)x];
-      const int kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+      const int kind = node_kind(g.type_lut, g.type_mask, code);
       const bool plain = kind_is_excluded(kind) || kind == NK_FULL_BB;
       level = (kind == NK_FLUID) ? 0 : (plain ? 1 : 2);
     }

@@ -414,7 +414,7 @@ __global__ void __launch_bounds__(1024) sc_macro_kernel(const ScParams<L, R> p) 
   }
   if constexpr (GENERAL) {
     const uint32_t code = p.map[gi];
-    const int kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    const int kind = node_kind(g.type_lut, g.type_mask, code);
     if (!kind_is_wet(kind)) return;
   }
   const size_t ds = g.dist_size;
@@ -498,7 +498,7 @@ __global__ void __launch_bounds__(1024) sc_sweep_kernel(const ScParams<L, R> p) 
   bool active = live;
   if constexpr (GENERAL) {
     const uint32_t code = p.map[gi];
-    kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    kind = node_kind(g.type_lut, g.type_mask, code);
     if constexpr (!ROW) {
       if (kind_is_excluded(kind)) return;
     } else {
@@ -571,7 +571,7 @@ sc_fused_kernel(const ScParams<L, R> p) {
   bool active = live;
   if constexpr (GENERAL) {
     const uint32_t code = p.map[gi];
-    kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    kind = node_kind(g.type_lut, g.type_mask, code);
     if constexpr (!ROW) {
       if (kind_is_excluded(kind)) return;
     } else {
@@ -766,7 +766,7 @@ __global__ void __launch_bounds__(1024) scs_macro_kernel(const ScParams<L, R> p)
   }
   if constexpr (GENERAL) {
     const uint32_t code = p.map[n.gi];
-    const int kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    const int kind = node_kind(g.type_lut, g.type_mask, code);
     if (kind_is_excluded(kind)) return;
   }
   R f[L::Q];
@@ -807,7 +807,7 @@ __global__ void __launch_bounds__(1024) scs_sweep_kernel(const ScParams<L, R> p)
   bool active = live;
   if constexpr (GENERAL) {
     const uint32_t code = p.map[gi];
-    kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+    kind = node_kind(g.type_lut, g.type_mask, code);
     if constexpr (!ROW) {
       if (kind_is_excluded(kind)) return;
     } else {

@@ -22,7 +22,8 @@ namespace slf {
 // level-2 instantiation of the two-copy step keeps in 32 bytes of scratch per lane at its 128 VGPRs.
 // Double precision D3Q19: two waves per SIMD, i.e. 256 VGPRs -- at the 128 of four waves every instantiation kept 100-330
 // bytes per lane in scratch, more than the 304 bytes of populations a node moves.
-template <class L, class R, int MODEL, int PROP, int BCL = 2>
+// TMS: the instantiation for modules with Tamm-Mott-Smith wall nodes (node_update<..., TMS>), at level 2 only.
+template <class L, class R, int MODEL, int PROP, int BCL = 2, bool TMS = false>
 __global__ void __launch_bounds__(256, (sizeof(R) == 8 && L::Q > 9) ? 2 : 4) slot_sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const uint32_t si = blockIdx.x * 256u + threadIdx.x;
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 && L::Q > 9) ? 2 : 4) slo
   const int gx = (int)(gi - ((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gz));
   if (gx < 1 || gx > g.lat_nx - 2) return;                   // the layer of ghost nodes owns slots too
   const uint32_t code = p.map[gi];
-  const int kind = (int)((g.type_lut >> (4u * (code & g.type_mask))) & 0xFull);
+  const int kind = node_kind(g.type_lut, g.type_mask, code);
   if (kind_is_excluded(kind)) return;
   const AxisOff ox = axis_off(gx, g.lat_nx, 1, g.wrap[0]);
   const AxisOff oy = axis_off(gy, g.lat_ny, g.arr_nx, g.wrap[1]);
@@ -58,7 +59,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 && L::Q > 9) ? 2 : 4) slo
   });
   R rho, v[3];
   bool wet = true;
-  node_update<L, R, MODEL, PROP, true, true, FORCE_RUNTIME, BCL, false>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+  node_update<L, R, MODEL, PROP, true, true, FORCE_RUNTIME, BCL, false, false, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   if ((p.options & 1u) && wet) {
     p.rho[gi] = rho;
@@ -104,6 +105,11 @@ hipError_t launch_slot_sweep(int model, int prop, int bc_level, const SweepParam
   pick<int, 0, 1>(model == 0 ? 0 : 1, [&](auto MODEL) { pick_prop((Prop)prop, [&](auto P) {
     // (single-precision BGK, odd in-place step: the level-0 instantiation comes out of the register allocator with 28 bytes
     // of scratch at 128 VGPRs where level 1 has none at 124 -- profiles/r06/kernels_resources.txt -- so level 1 serves both)
+    if (q.tms_mask != 0) {
+      hipLaunchKernelGGL((slot_sweep_kernel<L, R, MODEL, P, 2, true>), sgrid, sblock, 0, s, q);
+      e = hipGetLastError();
+      return;
+    }
     constexpr bool skip0 = sizeof(R) == 4 && MODEL == 0 && P == PROP_AA_ODD && L::Q > 9;
     pick<int, 0, 1, 2>(bc_level == 0 && !skip0 ? 0 : (bc_level <= 1 ? 1 : 2), [&](auto BCL) {
       if constexpr (skip0 && BCL == 0) return;

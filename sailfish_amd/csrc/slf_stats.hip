@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(KE_MAX_BLOCK) ke_enstrophy_kernel(const Geomet
     if (live && !ghost_row) {
       bool active = true;
       if (map) {
-        const int kind = (int)((g.type_lut >> (4u * (map[gi] & g.type_mask))) & 0xFull);
+        const int kind = node_kind(g.type_lut, g.type_mask, map[gi]);
         active = !kind_is_excluded(kind);
       }
       if (active) {

@@ -50,6 +50,8 @@ struct SweepParams {
   // Newton start value of a node and the alpha it ended with; NULL: no alpha array (start from 2, nothing stored)
   R* alpha;
   ElbmParams<R> elbm;
+  // Tamm-Mott-Smith walls (Physics::tms_mask): read by the TMS instantiations of the per-node kernels and the slot sweep only
+  uint32_t tms_mask;
 };
 
 
@@ -312,6 +314,68 @@ __device__ __forceinline__ void elbm_collide(const SweepParams<L, R>& p, R (&f)[
   }
 }
 
+// Does direction I of a TMS node point to a non-fluid node?  Then population opp(I) is undefined there
+// (for_orientation_dist with link tags, boundary.mako:391-416).  The test of half_bb_store, for tms_fix_missing; the store
+// keeps the test in its own loop: as a call it cost every kernel with the store an instruction per direction.
+template <class L, int I>
+__device__ __forceinline__ bool link_missing(const Geometry& g, int orientation) {
+  bool missing;
+  if (g.use_link_tags) {
+    missing = ((orientation >> (I - 1)) & 1) == 0;
+  } else {
+    missing = false;
+    with_orientation<L>(orientation, [&](auto O) {
+      if constexpr (is_missing<L, L::opp(I), O>()) missing = true;
+    });
+  }
+  return missing;
+}
+
+// The half-way bounce-back store (_global_mem_fill_missing_dists_with_opposites, boundary.mako:653-666): every undefined
+// population opp(I) is fed with the reflected post-collision f_I, where the node's next step reads it.
+template <class L, class R, int PROP, bool INDIRECT>
+__device__ __forceinline__ void half_bb_store(const SweepParams<L, R>& p, const R (&f)[L::Q], int orientation, uint32_t gi,
+                                              uint32_t si, const AxisOff& ox, const AxisOff& oy, const AxisOff& oz) {
+  const Geometry& g = p.g;
+  const size_t ds = g.dist_size;
+  static_for<1, L::Q>([&](auto I) {
+    bool missing;
+    if (g.use_link_tags) {
+      missing = ((orientation >> (I - 1)) & 1) == 0;  // direction I points to a non-fluid node
+    } else {
+      missing = false;
+      with_orientation<L>(orientation, [&](auto O) {
+        if constexpr (is_missing<L, L::opp(I), O>()) missing = true;
+      });
+    }
+    if (missing) {
+      if constexpr (PROP == PROP_AA_EVEN) {
+        const int off = dir_offset<L, I>(ox, oy, oz, true);
+        uint32_t t = (uint32_t)((int)gi + off);
+        if constexpr (INDIRECT) t = p.nodes[t];
+        if (!INDIRECT || t != INVALID_NODE) (p.dout + ds * (size_t)I)[t] = f[I];
+      } else {
+        (p.dout + ds * (size_t)L::opp(I))[si] = f[I];
+      }
+    }
+  });
+}
+
+// fixMissingDistributions of a Tamm-Mott-Smith wall node (boundary.mako:631-648): the target state is the standard moments
+// of the populations as loaded -- from the second step on the unknown slots hold what the node's own store put there, the
+// bounced-back post-collision values of the step before -- and the unknown populations become its equilibrium.
+template <class L, class R, bool ROUNDOFF>
+__device__ __forceinline__ void tms_fix_missing(const Geometry& g, R (&f)[L::Q], int orientation, bool inc, R& tg_rho,
+                                                R (&tg_v)[3]) {
+  if constexpr (ROUNDOFF) macro_roundoff<L, R>(f, tg_rho, tg_v);
+  else macro_standard<L, R>(f, inc, tg_rho, tg_v);
+  const R tg_rho0 = ROUNDOFF ? tg_rho + (R)1 : (inc ? (R)1 : tg_rho);
+  const R u15 = usq15<L, R>(tg_v);
+  static_for<1, L::Q>([&](auto I) {
+    if (link_missing<L, I>(g, orientation)) f[L::opp(I)] = feq<L, R, L::opp(I)>(tg_rho, tg_rho0, tg_v, u15);
+  });
+}
+
 // gi: dense node index; si: the node's slot in the distribution arrays (= gi unless INDIRECT).
 // MODEL: 0 BGK, 1 MRT, 2 entropic (slf_node.h elbm_relax; the per-node kernels only).
 // BCL: the module's Geometry::bc_level the instantiation is for (2 = everything; the outflow, do-nothing and full-slip nodes
@@ -320,8 +384,11 @@ __device__ __forceinline__ void elbm_collide(const SweepParams<L, R>& p, R (&f)[
 // and half-way bounce-back nodes (the module is refused otherwise); the per-node kernels only.
 // TURB: the BGK collision with the options of the reference's relaxation preamble (--regularized, --subgrid; which of
 // the two: SweepParams::turb_flags) -- slf_node.h bgk_relax_turb; the per-node kernels only, MODEL = BGK.
+// TMS: the module has Tamm-Mott-Smith wall nodes (SweepParams::tms_mask != 0): half-way bounce-back types with the flag run
+// tms_fix_missing before and tms_add_equilibrium_difference after the collision; the target state stays live across it.
+// The per-node kernels and the slot sweep only; instantiations of their own, so that the others do not carry the registers.
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, int FORCE = FORCE_RUNTIME, int BCL = 2,
-          bool ROUNDOFF = false, bool TURB = false>
+          bool ROUNDOFF = false, bool TURB = false, bool TMS = false>
 __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L::Q], uint32_t code, int kind,
                                             uint32_t gi, const AxisOff& ox, const AxisOff& oy, const AxisOff& oz,
                                             R& rho, R (&v)[3], bool& wet, uint32_t si = INVALID_NODE) {
@@ -336,6 +403,13 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     // conditions whose reference expressions are consistent under the option (the regularized / Zou-He nodes are not:
     // ex_eq_flux keeps multiplying by the density DELTA, DESIGN.md §9 -- refused at module creation)
     bool bc = false;
+    R tg_rho = (R)0, tg_v[3] = {(R)0, (R)0, (R)0};
+    bool tms = false;
+    if constexpr (GENERAL && TMS) {
+      tms = kind == NK_HALF_BB && (((p.tms_mask >> (code & g.type_mask)) & 1u) != 0u);
+      if (tms) tms_fix_missing<L, R, true>(g, f, (int)(code >> g.orient_shift), false, tg_rho, tg_v);
+    }
+    (void)tg_rho; (void)tg_v; (void)tms;
     if constexpr (GENERAL) {
       const int orientation = (int)(code >> g.orient_shift);
       if ((kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY) && orientation != 0) {
@@ -375,27 +449,10 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
       bgk_relax_roundoff<L, R>(f, rho, v, p.cp.omega, p.cp.guo_pref, p.cp.has_force != 0, p.cp.accel, p.cp.force_edm != 0);
     if (GENERAL && kind == NK_HALF_BB) {
       const int orientation = (int)(code >> g.orient_shift);
-      static_for<1, L::Q>([&](auto I) {
-        bool missing;
-        if (g.use_link_tags) {
-          missing = ((orientation >> (I - 1)) & 1) == 0;
-        } else {
-          missing = false;
-          with_orientation<L>(orientation, [&](auto O) {
-            if constexpr (is_missing<L, L::opp(I), O>()) missing = true;
-          });
-        }
-        if (missing) {
-          if constexpr (PROP == PROP_AA_EVEN) {
-            const int off = dir_offset<L, I>(ox, oy, oz, true);
-            uint32_t t = (uint32_t)((int)gi + off);
-            if constexpr (INDIRECT) t = p.nodes[t];
-            if (!INDIRECT || t != INVALID_NODE) (p.dout + ds * (size_t)I)[t] = f[I];
-          } else {
-            (p.dout + ds * (size_t)L::opp(I))[si] = f[I];
-          }
-        }
-      });
+      if constexpr (TMS) {
+        if (tms) tms_add_equilibrium_difference<L, R>(f, tg_rho, tg_rho + (R)1, tg_v, rho, rho + (R)1, v);
+      }
+      half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
     }
     return;
   }
@@ -412,6 +469,13 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     const int orientation = (int)(code >> g.orient_shift);
     const int pidx = (int)((code >> g.param_shift) & g.param_mask);
     const bool inc = p.cp.incompressible != 0;
+    R tg_rho = (R)0, tg_v[3] = {(R)0, (R)0, (R)0};
+    bool tms = false;
+    if constexpr (TMS) {
+      tms = kind == NK_HALF_BB && (((p.tms_mask >> (code & g.type_mask)) & 1u) != 0u);
+      if (tms) tms_fix_missing<L, R, false>(g, f, orientation, inc, tg_rho, tg_v);
+    }
+    (void)tg_rho; (void)tg_v; (void)tms;
     // ---- fixMissingDistributions (boundary.mako:509-603): outflow nodes fill their unknown populations from
     // the incoming state of the nodes one / two steps along the inward normal (two-copy pattern only)
     if constexpr (PROP == PROP_AB && BCL == 2) {
@@ -513,29 +577,12 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
       }
     }
     // ---- post-collision: half-way bounce-back (boundary.mako:653-683)
+    // ... and the Tamm-Mott-Smith wall, which ends with the same store (boundary.mako:696-723)
     if (kind == NK_HALF_BB) {
-      static_for<1, L::Q>([&](auto I) {
-        bool missing;
-        if (g.use_link_tags) {
-          missing = ((orientation >> (I - 1)) & 1) == 0;  // direction I points to a non-fluid node
-        } else {
-          missing = false;
-          with_orientation<L>(orientation, [&](auto O) {
-            if constexpr (is_missing<L, L::opp(I), O>()) missing = true;
-          });
-        }
-        if (missing) {
-          // population opp(I) is undefined here: feed it with the reflected f_I.
-          if constexpr (PROP == PROP_AA_EVEN) {
-            const int off = dir_offset<L, I>(ox, oy, oz, true);
-            uint32_t t = (uint32_t)((int)gi + off);
-            if constexpr (INDIRECT) t = p.nodes[t];
-            if (!INDIRECT || t != INVALID_NODE) (p.dout + ds * (size_t)I)[t] = f[I];
-          } else {
-            (p.dout + ds * (size_t)L::opp(I))[si] = f[I];
-          }
-        }
-      });
+      if constexpr (TMS) {
+        if (tms) tms_add_equilibrium_difference<L, R>(f, tg_rho, inc ? (R)1 : tg_rho, tg_v, rho, inc ? (R)1 : rho, v);
+      }
+      half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
     }
   } else {
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
@@ -597,6 +644,7 @@ inline SweepParams<L, R> make_params(const Geometry& g, const Physics& ph, const
   p.elbm.entropy_tol = (R)ph.entropy_tolerance;
   p.elbm.alpha_tol = (R)ph.alpha_tolerance;
   p.elbm.entropic_eq = ph.entropic_equilibrium;
+  p.tms_mask = ph.tms_mask;
   p.g = g;
   p.cp.omega = (R)(1.0 / ph.tau);
   for (int k = 0; k < L::Q; k++) p.cp.mrt_s[k] = (R)ph.mrt_rates[k];

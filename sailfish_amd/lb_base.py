@@ -174,6 +174,14 @@ class LBSim(object):
     def initial_conditions(self, runner):
         pass
 
+    @classmethod
+    def check_module_desc(cls, kw):
+        """Refuses, on the host and with a clear message, what no kernel of the library covers (the library refuses the
+        same at module creation)."""
+        if hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []) and kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
+            raise NotImplementedError('NTWallTMS nodes: single-fluid simulations only (the Shan-Chen kernels serve fluid and '
+                                      'full-way bounce-back nodes)')
+
     def fill_module_desc(self, kw):
         """Contributes to the kernel-module descriptor (the counterpart of the reference's
         update_context(), lb_base.py:120-137)."""

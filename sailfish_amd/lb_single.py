@@ -90,17 +90,18 @@ class LBFluidSim(LBSim):
         return hipabi.SLF_DENSITY_COMPRESSIBLE
 
     ROUNDOFF_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                      hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB, hipabi.SLF_NK_EQUILIBRIUM_DENSITY,
-                      hipabi.SLF_NK_EQUILIBRIUM_VELOCITY)
+                      hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB, hipabi.SLF_NK_WALL_TMS,
+                      hipabi.SLF_NK_EQUILIBRIUM_DENSITY, hipabi.SLF_NK_EQUILIBRIUM_VELOCITY)
 
     @classmethod
     def check_module_desc(cls, kw):
         """Refuses, on the host and with a clear message, what the kernels of the chosen formulation do not cover
         (the library refuses the same at module creation)."""
+        super(LBFluidSim, cls).check_module_desc(kw)
         if kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
             bad = [k for k in kw.get('type_kind', []) if k not in cls.ROUNDOFF_KINDS]
             if bad:
-                raise NotImplementedError('--minimize_roundoff: fluid, bounce-back and equilibrium density / velocity nodes '
+                raise NotImplementedError('--minimize_roundoff: fluid, bounce-back, TMS wall and equilibrium density / velocity nodes '
                                           'only (node kinds %s are not covered: the reference\'s own regularized / Zou-He '
                                           'expressions are inconsistent under the option, DESIGN.md)' % sorted(set(bad)))
         if kw.get('entropic_equilibrium') and kw.get('model') != hipabi.SLF_ELBM:

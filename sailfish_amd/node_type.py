@@ -68,7 +68,7 @@ _TABLE = (
     # walls: half-way bounce-back reflects at the link mid-point (link tags), full-way at the node
     ('NTHalfBBWall', None, dict(_W, link_tags=True, location=-0.5, allow_unused=True, **dict(_S, **_O)), hipabi.SLF_NK_HALF_BB),
     ('NTFullBBWall', None, dict(_S, location=0.5, **_O), hipabi.SLF_NK_FULL_BB),
-    ('NTWallTMS', None, dict(_W, link_tags=True, location=0.5, allow_unused=True, **dict(_S, **_O)), None),
+    ('NTWallTMS', None, dict(_W, link_tags=True, location=0.5, allow_unused=True, **dict(_S, **_O)), hipabi.SLF_NK_WALL_TMS),
     ('NTSlip', None, dict(_S), hipabi.SLF_NK_SLIP),             # dry, specular reflection; the orientation is given: NTSlip(orientation=...)
     # imposed density (pressure)
     ('NTEquilibriumDensity', 'density', dict(_W, **_O), hipabi.SLF_NK_EQUILIBRIUM_DENSITY),

@@ -218,7 +218,8 @@ class SubdomainRunner(object):
         if self.config.access_pattern != 'AA':
             return                                  # the two-copy step stores into the node's own slot
         sub = self._subdomain
-        pos = np.argwhere(sub.visualization_map() == nt.NTHalfBBWall.id)        # real nodes, numpy axis order
+        # (Tamm-Mott-Smith walls end their step with the same store)
+        pos = np.argwhere(np.isin(sub.visualization_map(), (nt.NTHalfBBWall.id, nt.NTWallTMS.id)))    # real nodes, numpy axis order
         if not len(pos):
             return
         grid = self._sim.grid
@@ -243,7 +244,7 @@ class SubdomainRunner(object):
         if lost.any():
             first = pos[np.nonzero(lost)[0][0]]
             where = tuple(int(c) + int(o) for c, o in zip(reversed(first), self._spec.location))
-            raise ValueError('--node_addressing=indirect with --access_pattern=AA: %d links of half-way bounce-back nodes point '
+            raise ValueError('--node_addressing=indirect with --access_pattern=AA: %d links of half-way bounce-back / TMS nodes point '
                              'to nodes that own no slot in the distribution arrays (first at node %s): the populations '
                              'reflected there would be lost.  Keep the layer behind half-way bounce-back walls in the '
                              'active-node map (count those wall nodes as fluid in the wall map given to '
