@@ -443,6 +443,18 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
                         int needs_iteration);
 int slf_kernel_set_iteration(slf_kernel* k, uint32_t iteration);
 int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* stream); /* run_kernel */
+/* Two time steps per launch.  For a "CollideAndPropagate" kernel object whose arguments are set: after this call succeeds
+ * every launch of the object reads the populations of step t from its source array and writes those of step t + 2 to its
+ * destination array; the intermediate state never reaches memory (slf_pair.hip), and the result is bit-identical to two
+ * single-step launches (source -> destination -> source would leave it in the source; here it is in the destination).
+ * rows_per_strip (2 or 4) and planes_per_chunk size the piece of the box a workgroup marches through, 0 = the
+ * library's default.  Step plans and graphs need nothing new: they record launches of kernel objects.
+ * SLF_ERR_UNSUPPORTED, with the reason in slf_last_error(), unless the module is D3Q19, single precision, BGK, two-copy
+ * (SLF_AB), fluid_only with direct addressing, without a body force and without x-face buffers, all three axes wrapped
+ * inside the sweep (periodic_fused), nx a multiple of 64 in 64 .. 512, ny a multiple of rows_per_strip, source and
+ * destination different arrays and options bit 0 (field output) clear.  Launches take no region.  Setting the arguments
+ * again returns the object to single steps. */
+int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk);
 
 /* x faces connected to another subdomain (1-D decompositions along x, the reference's default axis, geo.py:100-135):
  * instead of pushing into the ghost columns x = 0 / nx + 1 and packing them with a strided gather afterwards

@@ -552,6 +552,16 @@ class HIPBackend(placement.VmmMixin):
                                                         int(nbytes), stream.handle if stream else None),
                'slf_memcpy_d2d_async')
 
+    def copy_dist_async(self, dst, src, nbytes, stream=None):
+        """Device-to-device copy between two buffers either of which may be a placed one: cut where either crosses the
+        boundary between two of its physical chunks (the runtime's copy calls work per allocation)."""
+        cuts = set([0, int(nbytes)])
+        for buf in (dst, src):
+            cuts.update(off for _, off, _ in self._segments(buf, nbytes))
+        cuts = sorted(cuts)
+        for lo, hi in zip(cuts, cuts[1:]):
+            self.copy_buf_async(dst + lo, src + lo, hi - lo, stream)
+
     def copy_peer_async(self, dst, dst_device, src, src_device, nbytes, stream=None):
         _check(self._lib, self._lib.slf_memcpy_peer_async(self._ctx, ctypes.c_void_p(dst), int(dst_device),
                                                          ctypes.c_void_p(src), int(src_device), int(nbytes),
@@ -577,6 +587,19 @@ class HIPBackend(placement.VmmMixin):
         kern = HIPKernel(self._lib, prog, name)
         kern.set_args(args, args_format, needs_iteration)
         return kern
+
+    def set_kernel_pair(self, kernel, rows=0, zchunk=0):
+        """Makes every launch of a CollideAndPropagate kernel object advance TWO time steps (C ABI slf_kernel_set_pair:
+        source array at step t -> destination array at step t + 2).  rows / zchunk: rows per strip and planes per chunk
+        of a workgroup, 0 = the library's default.  Returns None where the library accepts, otherwise its reason (the
+        module, the arguments or the bound arrays do not qualify: the object keeps stepping singly); any other failure
+        raises."""
+        status = self._lib.slf_kernel_set_pair(kernel.handle, int(rows), int(zchunk))
+        if status == 3:         # SLF_ERR_UNSUPPORTED
+            msg = self._lib.slf_last_error()
+            return msg.decode() if msg else 'unsupported'
+        _check(self._lib, status, 'slf_kernel_set_pair(%s)' % kernel.name)
+        return None
 
     def set_iteration(self, it):
         """The iteration number the AA kernels see (reference backend_cuda.py:128-130 rewrites the trailing kernel

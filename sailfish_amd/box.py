@@ -151,6 +151,7 @@ class BoxSim(object):
                     csig += 'P'
                 ks.append(b.get_kernel(m, 'CollideAndPropagate', (64,), args, csig, needs_iteration=self.aa))
             self.k_sweep[save] = ks
+        self._make_pair_kernels(sig)
         self.k_init = []
         for dbuf in self.gpu_dist:
             args = [dbuf] + self.gpu_v + [self.gpu_rho, self.gpu_map]
@@ -166,6 +167,65 @@ class BoxSim(object):
         args = [self.gpu_map, self.gpu_dist[0], self.gpu_dist[0], self.gpu_rho] + self.gpu_v + [1]
         self.k_macro = b.get_kernel(m, 'ComputeMacroFields', (64,), args, sig, needs_iteration=self.aa)
 
+    def _make_pair_kernels(self, sig):
+        """The two kernel objects that advance TWO steps per launch (copy 0 -> 1, 1 -> 0; C ABI slf_kernel_set_pair), where
+        the library accepts them: two-copy D3Q19 / f32 / BGK boxes wrapped in-sweep on every axis.
+        SLF_STEP_PAIRS=0 switches pairing off; SLF_PAIR_ROWS / SLF_PAIR_ZCHUNK size the piece of the box a workgroup
+        takes (0 / unset: the library's default).  A slab with a halo never pairs: its face layers leave every step."""
+        b = self.backend
+        self.k_pair = None          # [kernel that reads gpu_dist[0], kernel that reads gpu_dist[1]]
+        self.pair_refused = None    # the library's reason where it does not accept
+        self.pair_launches = 0
+        self._pending = False       # one step counted in `iteration` and not enqueued yet
+        self._flipped = False       # an odd number of pair launches since the arrays last held what single steps leave
+        if self.aa or getattr(self, 'halo', False) or not hasattr(b, 'set_kernel_pair'):
+            return
+        if os.environ.get('SLF_STEP_PAIRS', '1') == '0':
+            self.pair_refused = 'SLF_STEP_PAIRS=0'
+            return
+        if self.pbc_axes or self.gpu_alpha is not None:
+            self.pair_refused = 'pair sweep: every axis must be wrapped inside the sweep'
+            return
+        rows = int(os.environ.get('SLF_PAIR_ROWS', '0') or 0)
+        zchunk = int(os.environ.get('SLF_PAIR_ZCHUNK', '0') or 0)
+        ks = []
+        for i, o in ((0, 1), (1, 0)):
+            args = [self.gpu_map, self.gpu_dist[i], self.gpu_dist[o], self.gpu_rho] + self.gpu_v + [0]
+            k = b.get_kernel(self.module, 'CollideAndPropagate', (64,), args, sig)
+            why = b.set_kernel_pair(k, rows, zchunk)
+            if why is not None:
+                self.pair_refused = why
+                return
+            ks.append(k)
+        self.k_pair = ks
+
+    def _flush(self):
+        """Brings the device to what `iteration` says, in the array single steps would have left it in: enqueues the
+        pending step with the single-step kernel and, after an odd number of pair launches (the populations sit in the
+        other array), copies them over and puts `gpu_dist` and the kernel lists back in their original order.  Everything
+        that looks at or replaces device state calls this first."""
+        if getattr(self, 'k_pair', None) is None:
+            return
+        b = self.backend
+        if self._pending:
+            self._pending = False
+            b.run_kernel(self.k_sweep[0][(self.iteration - 1) & 1], None, self.stream)
+        if self._flipped:
+            cur = self.gpu_dist[self.iteration & 1]
+            other = self.gpu_dist[1 - (self.iteration & 1)]
+            b.copy_dist_async(other, cur, self.Q * self.stride * self.dtype().itemsize, self.stream)
+            self._flip()
+
+    def _flip(self):
+        """`gpu_dist[iteration & 1]` is the current copy, and kernel i of a list reads gpu_dist[i]: after a pair launch the
+        populations are in the other physical array while the parity of `iteration` is what it was, so the lists turn
+        round, in place (whoever holds the list sees it)."""
+        self.gpu_dist.reverse()
+        self.k_pair.reverse()
+        for ks in self.k_sweep.values():
+            ks.reverse()
+        self._flipped = not self._flipped
+
     def set_fields(self, rho, v):
         """rho, v[d]: arrays over the *real* nodes ((nz,) ny, nx)."""
         self.real_view(self.rho)[...] = rho
@@ -177,6 +237,7 @@ class BoxSim(object):
 
     def initial_conditions(self):
         """SetInitialConditions on every dist copy (reference lb_single.py:72-94)."""
+        self._flush()
         for k in self.k_init:
             self.backend.run_kernel(k, None, self.stream)
         self.iteration = 0
@@ -192,6 +253,20 @@ class BoxSim(object):
 
     def step(self, save_macro=False, region=None):
         b = self.backend
+        if self.k_pair is not None:
+            if not save_macro and region is None:
+                # deferred stepping: the first of two steps is only counted, the second enqueues both as one launch
+                if self._pending:
+                    b.run_kernel(self.k_pair[(self.iteration - 1) & 1], None, self.stream)
+                    self.pair_launches += 1
+                    self._flip()
+                self._pending = not self._pending
+                self.iteration += 1
+                b.set_iteration(self.iteration)
+                return
+            if self._pending:       # (the arrays may stay turned round: this step's kernels come from the same lists)
+                self._pending = False
+                b.run_kernel(self.k_sweep[0][(self.iteration - 1) & 1], None, self.stream)
         k, out, swap = self._sweep_of(self.iteration, save_macro)
         b.run_kernel(k, region, self.stream)
         for axis in self.pbc_axes:
@@ -204,6 +279,7 @@ class BoxSim(object):
             self.step(save_macro=(save_last and i == n - 1))
 
     def sync(self):
+        self._flush()
         self.stream.synchronize()
 
     def release(self):
@@ -215,12 +291,12 @@ class BoxSim(object):
             b.free_buf(addr)
         self.gpu_dist = []
         # drop the kernel objects: the backend's registry of iteration-dependent kernels holds them weakly
-        for name in ('k_init', 'k_sweep', 'k_pbc', 'k_macro', 'k_halo'):
+        for name in ('k_init', 'k_sweep', 'k_pair', 'k_pbc', 'k_macro', 'k_halo'):
             if hasattr(self, name):
                 setattr(self, name, None)
 
     def fetch_fields(self):
-        self.sync()
+        self.sync()       # (flushes a pending step)
         self.backend.from_buf(self.gpu_rho)
         for g in self.gpu_v:
             self.backend.from_buf(g)
@@ -248,6 +324,7 @@ class BoxSim(object):
         return np.ascontiguousarray(raw[:, :self.nodes]).reshape((self.Q,) + self.shape)
 
     def set_dist(self, host, which=None):
+        self._flush()
         idx = self.current_dist_index() if which is None else which
         raw = np.zeros((self.Q, self.stride), dtype=self.dtype)
         raw[:, :self.nodes] = np.asarray(host, dtype=self.dtype).reshape(self.Q, self.nodes)

@@ -113,6 +113,7 @@ struct slf_kernel {
   bool bound;
   bool sc_local_velocity;   // ShanChenPrepareDensities / ShanChenCollideAndPropagateFusedV
   bool alpha_arg = false;   // CollideAndPropagate of an entropic module: the last pointer is the alpha field
+  int pair_rows = 0, pair_zc = 0;   // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); 0: single steps
 };
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
@@ -1662,6 +1663,7 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
   }
   if (k->ptrs.size() != want_p || k->ints.size() != want_i)
     return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature");
+  k->pair_rows = k->pair_zc = 0;     // new arguments: slf_kernel_set_pair has to look at them again
   k->needs_iteration = needs_iteration;
   k->bound = true;
   if (k->kind == KK_COLLIDE_AND_PROPAGATE && k->mod->geo.indirect && !k->ptrs.empty() &&
@@ -1717,7 +1719,44 @@ int sweep_common(const slf_kernel* k, slf::SweepArgs& a) {
   return SLF_OK;
 }
 
+// the launch arguments of a pair sweep (slf_kernel_set_pair) from the bound arguments of a CollideAndPropagate kernel
+void pair_args(const slf_kernel* k, slf::SweepArgs& a) {
+  const slf_module* m = k->mod;
+  const int b0 = m->geo.indirect ? 1 : 0;
+  a.nodes = m->geo.indirect ? (const void*)k->ptrs[0] : nullptr;
+  a.map = (const void*)k->ptrs[b0 + 0];
+  a.dist_in = (void*)k->ptrs[b0 + 1];
+  a.dist_out = (void*)k->ptrs[b0 + 2];
+  a.node_params = m->node_params;
+  a.status = m->status;
+  a.options = (uint32_t)k->ints[0];
+  for (int f = 0; f < 2; f++) {
+    a.xsend[f] = m->xsend[f];
+    a.xrecv[f] = m->xrecv[f];
+  }
+}
+
 }  // namespace
+
+int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk) {
+  if (!k) return fail(SLF_ERR_INVALID, "kernel is NULL");
+  if (k->kind != KK_COLLIDE_AND_PROPAGATE)
+    return fail(SLF_ERR_UNSUPPORTED, "pair sweep: CollideAndPropagate kernels of single-fluid modules only");
+  if (!k->bound) return fail(SLF_ERR_INVALID, "pair sweep: set the kernel arguments first (source and destination are checked)");
+  if (rows_per_strip < 0 || planes_per_chunk < 0) return fail(SLF_ERR_INVALID, "pair sweep: negative strip / chunk size");
+  const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows();
+  const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk();
+  const slf_module* m = k->mod;
+  if (m->sc.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
+    return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
+  slf::SweepArgs a = {};
+  pair_args(k, a);
+  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc))
+    return fail(SLF_ERR_UNSUPPORTED, why);
+  k->pair_rows = rows;
+  k->pair_zc = zc;
+  return SLF_OK;
+}
 
 int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* stream) {
   if (!k) return fail(SLF_ERR_INVALID, "kernel is NULL");
@@ -1730,6 +1769,18 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
   switch (k->kind) {
     case KK_COLLIDE_AND_PROPAGATE:
     case KK_COMPUTE_MACRO: {
+      if (k->pair_rows) {
+        // two steps per launch: whatever has changed since slf_kernel_set_pair accepted (a body force, face buffers)
+        // is an error here, never a quiet single step
+        slf::SweepArgs pa = {};
+        pair_args(k, pa);
+        if (region) return fail(SLF_ERR_UNSUPPORTED, "pair sweep: whole-box launches only");
+        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, s, &e)) {
+          const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc);
+          return fail(SLF_ERR_UNSUPPORTED, why ? why : "pair sweep: no kernel for this strip size");
+        }
+        break;
+      }
       slf::SweepArgs a = {};
       const int b0 = g.indirect ? 1 : 0;
       a.nodes = g.indirect ? (const void*)k->ptrs[0] : nullptr;

@@ -203,6 +203,17 @@ hipError_t launch_resident(const KernelSelector& sel, bool aa, const Geometry& g
 int resident_halo(bool aa, int it0, int steps);
 size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y);
 
+// ---- two steps per launch of the two-copy sweep (slf_pair.hip): periodic D3Q19 / f32 / BGK boxes ----
+// a.dist_in: the populations of step t, a.dist_out: where those of step t + 2 go; strips of `rows` rows (2 or 4), chunks
+// of `zc` planes.  pair_refusal: why the module / the arguments do not qualify, NULL if they do; launch_sweep_pair
+// returns false (nothing launched) in exactly those cases.
+const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                         int rows, int zc);
+bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                       int rows, int zc, hipStream_t s, hipError_t* err);
+int pair_default_rows();
+int pair_default_zchunk();
+
 // ---- flow statistics (slf_stats.hip): 3-D lattices, fields in the module's dense layout ----
 // Launch shape of a statistics pass: a function of the lattice size alone, so the order of every addition is too.
 constexpr int STATS_PROFILE_COUNT = 22;   // f, f^2, f^3, f^4 of ux, uy, uz, rho; ux uy, ux uz, uy uz, ux rho, uy rho, uz rho

@@ -1,0 +1,215 @@
+// Two time steps per pass over memory for the two-copy (AB) sweep of the periodic D3Q19 / f32 / BGK box.
+//
+// fast_row_kernel (slf_fast.hip) streams the populations once per step at the rate of a plain copy: the only traffic
+// left to remove is the round trip of the intermediate populations through HBM between step t and step t + 1.
+// pair_row_kernel reads the populations of step t from the source copy, keeps what step t produces in registers, and
+// writes the populations of step t + 2 to the other copy.
+//
+// One workgroup owns a strip of TY rows (y0 .. y0 + TY - 1) of zc planes (z0 .. z0 + zc - 1) and has one thread per x
+// (blockDim.x = nx, a multiple of 64: the row is a ring of whole waves).  It marches along z; at plane k it
+//   phase A  loads and collides the TY + 2 rows y0 - 1 .. y0 + TY of plane k (step t).  A post-collision value f_i of
+//            row r belongs to row r + e_y, plane k + e_z of the intermediate state: it is filed there if that row is
+//            one of the strip's own (the x shift is left for phase B);
+//   phase B  (from the third plane on) plane k - 1 of the intermediate state is complete: for every own row the x shift
+//            (one DPP move per direction, the wave-edge words through LDS), the collision of step t + 1 and the push to
+//            the destination copy, exactly as fast_row_kernel's AB branch does it;
+//   rotates  the three register planes.
+// A thread holds, per own row, the 19 values of plane k - 1, the 14 (e_z >= 0) of plane k that have arrived and the 5
+// (e_z = +1) of plane k + 1.  The halo rows and planes are collided again by the neighbouring strips / chunks: reads
+// (TY + 2) / TY x (zc + 2) / zc, writes 1.  Pushed (node, direction) pairs are written exactly once, so strips and
+// chunks never store to the same word.
+//
+// The arithmetic is slf_node.h's, called as fast_row_kernel calls it; with -ffp-contract=off the result is bit-identical
+// to two single steps.  Not served: macro field output (options bit 0), body forces, node maps, x-face buffers.
+#include "slf_dispatch.h"
+#include "slf_rowpush.h"
+
+namespace slf {
+
+namespace {
+
+constexpr int PAIR_NT = 3;       // non-temporal loads and stores, as in slf_fast.hip
+constexpr int PAIR_NW = 8;       // waves of a row: nx <= 512
+
+__device__ __forceinline__ int wrap1(int c, int n) {      // c in 0 .. n + 1 -> 1 .. n
+  if (c < 1) c += n;
+  if (c > n) c -= n;
+  return c;
+}
+
+template <int MODEL, int TY>
+__global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const SweepParams<D3Q19, float> p, const int zc) {
+  using L = D3Q19;
+  static_assert(MODEL == 0, "BGK only");
+  static_assert(TY % 2 == 0, "the push slots alternate by row");
+  constexpr int NXD = count_x_dirs<L>();
+  // raw intermediate values at the wave edges, per register plane: written as phase A produces them
+  __shared__ float s_in_p[3][TY][PAIR_NW][NXD], s_in_m[3][TY][PAIR_NW][NXD];
+  __shared__ float s_out_p[2][PAIR_NW][NXD], s_out_m[2][PAIR_NW][NXD];      // pushed values at the wave edges, by row parity
+  const Geometry& g = p.g;
+  const int ny = g.lat_ny - 2, nz = g.lat_nz - 2;
+  const int lane = (int)threadIdx.x & 63;
+  const int w = sgpr((int)threadIdx.x >> 6);
+  const int nwave = sgpr((int)blockDim.x >> 6);
+  // the row is a ring of waves (nwave = 1: a wave is its own neighbour)
+  const int slot_p = sgpr(w == 0 ? nwave - 1 : w - 1);
+  const int slot_m = sgpr(w == nwave - 1 ? 0 : w + 1);
+  const int x = (int)threadIdx.x + 1;
+  const uint32_t xb = (uint32_t)x * 4u;
+  const int y0 = sgpr(1 + (int)blockIdx.y * TY);
+  const int z0 = sgpr(1 + (int)blockIdx.z * zc);
+  int zn = nz - (z0 - 1);                 // planes of this chunk: the last one may be shorter
+  if (zn > zc) zn = zc;
+  zn = sgpr(zn);
+  const size_t ds = g.dist_size;
+  const AxisOff ox0 = {0, 0};
+  const bool inc = p.cp.incompressible != 0;
+
+  // intermediate state before the x shift: P0 plane k - 1, P1 plane k (e_z >= 0), P2 plane k + 1 (e_z > 0)
+  float P0[TY][L::Q], P1[TY][L::Q], P2[TY][L::Q];
+  static_for<0, TY>([&](auto J) {
+    static_for<0, L::Q>([&](auto I) { P0[J][I] = P1[J][I] = P2[J][I] = 0.0f; });
+  });
+
+  int c0 = 0, c1 = 1, c2 = 2;     // LDS slots of the planes k - 1, k, k + 1
+  for (int s = 0; s < zn + 2; s++) {
+    const int gz = sgpr(wrap1(z0 - 1 + s, nz));
+    const bool own_plane = s >= 1 && s <= zn;
+    // ---- phase A: step t of rows y0 - 1 .. y0 + TY of plane k = z0 - 1 + s
+    static_for<0, TY + 2>([&](auto RR) {
+      constexpr int rr = (int)RR - 1;
+      const int gy = sgpr(wrap1(y0 + rr, ny));
+      const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gz);
+      float f[L::Q];
+      static_for<0, L::Q>([&](auto I) {
+        f[I] = ldg<PAIR_NT>(at_byte(uniform_base(p.din + ds * (size_t)I + row), xb));
+      });
+      float rho, v[3];
+      macro_standard<L, float>(f, inc, rho, v);
+      if constexpr (rr >= 0 && rr < TY) {
+        if (own_plane) check_invalid<float>(p.status, p.options, rho, x, gy, gz);
+      }
+      if (p.relaxation_enabled) bgk_relax<L, float, false>(f, rho, v, p.cp);
+      static_for<0, L::Q>([&](auto I) {
+        constexpr int j = rr + L::ey(I);
+        if constexpr (j >= 0 && j < TY) {
+          if constexpr (L::ez(I) > 0) P2[j][I] = f[I];
+          else if constexpr (L::ez(I) == 0) P1[j][I] = f[I];
+          else P0[j][I] = f[I];
+        }
+      });
+      // ... and the words that will cross a wave edge in phase B
+      if (lane == 63) {
+        static_for<1, L::Q>([&](auto I) {
+          constexpr int j = rr + L::ey(I);
+          if constexpr (L::ex(I) > 0 && j >= 0 && j < TY)
+            s_in_p[L::ez(I) > 0 ? c2 : (L::ez(I) == 0 ? c1 : c0)][j][w][x_dir_rank<L, I>()] = f[I];
+        });
+      }
+      if (lane == 0) {
+        static_for<1, L::Q>([&](auto I) {
+          constexpr int j = rr + L::ey(I);
+          if constexpr (L::ex(I) < 0 && j >= 0 && j < TY)
+            s_in_m[L::ez(I) > 0 ? c2 : (L::ez(I) == 0 ? c1 : c0)][j][w][x_dir_rank<L, I>()] = f[I];
+        });
+      }
+    });
+    // ---- phase B: plane k - 1 of the intermediate state is complete; step t + 1 of the own rows
+    if (s >= 2) {
+      const int gzb = sgpr(z0 + s - 2);
+      AxisOff oz = axis_off(gzb, g.lat_nz, g.arr_nxy, 1);
+      oz.p = sgpr(oz.p); oz.m = sgpr(oz.m);
+      __syncthreads();
+      static_for<0, TY>([&](auto J) {
+        constexpr int buf = (int)J & 1;
+        float f[L::Q];
+        {
+          int kp = 0, km = 0;
+          static_for<0, L::Q>([&](auto I) {
+            if constexpr (L::ex(I) > 0) f[I] = lane_shift1<float, true>(s_in_p[c0][J][slot_p][kp++], P0[J][I]);
+            else if constexpr (L::ex(I) < 0) f[I] = lane_shift1<float, false>(s_in_m[c0][J][slot_m][km++], P0[J][I]);
+            else f[I] = P0[J][I];
+          });
+        }
+        const int gy = sgpr(y0 + (int)J);
+        float rho, v[3];
+        macro_standard<L, float>(f, inc, rho, v);
+        check_invalid<float>(p.status, p.options, rho, x, gy, gzb);
+        if (p.relaxation_enabled) bgk_relax<L, float, false>(f, rho, v, p.cp);
+        // push: the value of node x travels to x + e_x and is stored by the thread that owns the target x
+        if (lane == 63) {
+          int k = 0;
+          static_for<1, L::Q>([&](auto I) { if constexpr (L::ex(I) > 0) s_out_p[buf][w][k++] = f[I]; });
+        }
+        if (lane == 0) {
+          int k = 0;
+          static_for<1, L::Q>([&](auto I) { if constexpr (L::ex(I) < 0) s_out_m[buf][w][k++] = f[I]; });
+        }
+        __syncthreads();
+        const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gzb);
+        AxisOff oy = axis_off(gy, g.lat_ny, g.arr_nx, 1);
+        oy.p = sgpr(oy.p); oy.m = sgpr(oy.m);
+        int kp = 0, km = 0;
+        static_for<0, L::Q>([&](auto I) {
+          const int off = dir_offset<L, I>(ox0, oy, oz, true);
+          const auto base = uniform_base(p.dout + ds * (size_t)I + (uint32_t)((int)row + off));
+          float t = f[I];
+          if constexpr (L::ex(I) > 0) t = lane_shift1<float, true>(s_out_p[buf][slot_p][kp++], f[I]);
+          if constexpr (L::ex(I) < 0) t = lane_shift1<float, false>(s_out_m[buf][slot_m][km++], f[I]);
+          stg<PAIR_NT>(at_byte(base, xb), t);
+        });
+      });
+    }
+    // ---- rotate the register planes and their LDS slots
+    { const int t = c0; c0 = c1; c1 = c2; c2 = t; }
+    static_for<0, TY>([&](auto J) {
+      static_for<0, L::Q>([&](auto I) {
+        if constexpr (L::ez(I) >= 0) P0[J][I] = P1[J][I];
+        if constexpr (L::ez(I) > 0) P1[J][I] = P2[J][I];
+      });
+    });
+  }
+}
+
+}  // namespace
+
+int pair_default_rows() { return 2; }
+int pair_default_zchunk() { return 64; }
+
+const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                         int rows, int zc) {
+  if (sel.lattice != 1 || sel.precision != 4 || sel.model != 0) return "pair sweep: D3Q19, single precision, BGK modules only";
+  if (!two_copy) return "pair sweep: the two-copy (AB) access pattern only";
+  if (sel.general || a.map) return "pair sweep: modules without a node map only";
+  if (g.indirect || a.nodes) return "pair sweep: direct addressing only";
+  if (ph.has_force) return "pair sweep: body forces are not served";
+  if (!(g.variant & 1) || (g.variant & 256)) return "pair sweep: the tuned kernels are switched off for this module";
+  if (!g.wrap[0] || !g.wrap[1] || !g.wrap[2]) return "pair sweep: every axis must be wrapped inside the sweep";
+  if (a.xsend[0] || a.xsend[1] || a.xrecv[0] || a.xrecv[1]) return "pair sweep: not with x-face buffers";
+  const int nx = g.lat_nx - 2, ny = g.lat_ny - 2;
+  if (nx % 64 != 0 || nx < 64 || nx > 64 * PAIR_NW) return "pair sweep: rows of 64 .. 512 nodes, a multiple of 64";
+  if (rows != 2 && rows != 4) return "pair sweep: 2 or 4 rows per strip";
+  if (ny % rows != 0) return "pair sweep: ny must be a multiple of the rows per strip";
+  if (zc < 1) return "pair sweep: planes per chunk must be positive";
+  if (!a.dist_in || !a.dist_out) return "pair sweep: source or destination array is NULL";
+  if (a.dist_in == a.dist_out) return "pair sweep: source and destination must be different arrays";
+  if (a.options & 1u) return "pair sweep: macro field output is not served (options bit 0)";
+  return nullptr;
+}
+
+bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                       int rows, int zc, hipStream_t s, hipError_t* err) {
+  if (pair_refusal(sel, two_copy, g, ph, a, rows, zc)) return false;
+  const SweepParams<D3Q19, float> p = make_params<D3Q19, float>(g, ph, a, 1, 1);
+  const int nx = g.lat_nx - 2, ny = g.lat_ny - 2, nz = g.lat_nz - 2;
+  if (zc > nz) zc = nz;
+  dim3 block(nx, 1, 1);
+  dim3 grid(1, ny / rows, (nz + zc - 1) / zc);
+  const bool done = pick<int, 2, 4>(rows, [&](auto TY) {
+    hipLaunchKernelGGL((pair_row_kernel<0, TY>), grid, block, 0, s, p, zc);
+  });
+  if (done) *err = hipGetLastError();
+  return done;
+}
+
+}  // namespace slf

@@ -138,6 +138,7 @@ SIGNATURES = {
     'slf_kernel_set_args': (c_int, [c_void_p, c_char_p, POINTER(c_void_p), c_int, c_int]),
     'slf_kernel_set_iteration': (c_int, [c_void_p, c_uint32]),
     'slf_kernel_launch': (c_int, [c_void_p, POINTER(SlfRegion), c_void_p]),
+    'slf_kernel_set_pair': (c_int, [c_void_p, c_int, c_int]),
     'slf_module_poll_invalid': (c_int, [c_void_p, c_void_p, POINTER(c_int32 * 4)]),
     'slf_module_classify_rows': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int32 * 4)]),
     'slf_module_update_node_params': (c_int, [c_void_p, c_int, POINTER(c_double), c_int, c_void_p]),

@@ -498,6 +498,7 @@ class SlabSim(BoxSim):
         """The sweep launches of one step without any halo traffic (timing reference: what the calc stream costs
         when nothing has to be waited for).  Leaves the slab faces stale -- re-initialise afterwards."""
         b = self.backend
+        self._flush()
         it = self.iteration
         b.set_iteration(it)
         k = self._sweep_of(it, False)[0]
@@ -526,6 +527,7 @@ class SlabSim(BoxSim):
     def sync(self):
         """Everything this slab has enqueued is done -- and, with the peer transport, everything its neighbours' last
         step wrote into its face buffers (the waits of a step refer to the step before: the last step's are due now)."""
+        self._flush()           # a step the box driver has counted and not enqueued yet (box.py: deferred pair stepping)
         if self.halo:
             self._peer_drain()
         self.stream.synchronize()
