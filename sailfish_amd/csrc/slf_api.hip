@@ -114,6 +114,7 @@ struct slf_kernel {
   bool sc_local_velocity;   // ShanChenPrepareDensities / ShanChenCollideAndPropagateFusedV
   bool alpha_arg = false;   // CollideAndPropagate of an entropic module: the last pointer is the alpha field
   int pair_rows = 0, pair_zc = 0;   // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); 0: single steps
+  int pair_prefetch = 0;            // ... with this load path in phase A (SLF_PAIR_PREFETCH)
 };
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
@@ -1744,17 +1745,25 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: CollideAndPropagate kernels of single-fluid modules only");
   if (!k->bound) return fail(SLF_ERR_INVALID, "pair sweep: set the kernel arguments first (source and destination are checked)");
   if (rows_per_strip < 0 || planes_per_chunk < 0) return fail(SLF_ERR_INVALID, "pair sweep: negative strip / chunk size");
-  const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows();
-  const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk();
   const slf_module* m = k->mod;
+  const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows(m->geo);
+  const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk(m->geo);
+  // SLF_PAIR_PREFETCH: the load path of phase A (0: synchronous; unset: the default); read here, per kernel object
+  int prefetch = slf::pair_default_prefetch();
+  if (const char* e = getenv("SLF_PAIR_PREFETCH")) {
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*e) prefetch = (end && !*end && v >= 0 && v < 1000) ? (int)v : -1;
+  }
   if (m->sc.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
   slf::SweepArgs a = {};
   pair_args(k, a);
-  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc))
+  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc, prefetch))
     return fail(SLF_ERR_UNSUPPORTED, why);
   k->pair_rows = rows;
   k->pair_zc = zc;
+  k->pair_prefetch = prefetch;
   return SLF_OK;
 }
 
@@ -1775,8 +1784,10 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
         slf::SweepArgs pa = {};
         pair_args(k, pa);
         if (region) return fail(SLF_ERR_UNSUPPORTED, "pair sweep: whole-box launches only");
-        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, s, &e)) {
-          const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc);
+        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, k->pair_prefetch, s,
+                                    &e)) {
+          const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc,
+                                              k->pair_prefetch);
           return fail(SLF_ERR_UNSUPPORTED, why ? why : "pair sweep: no kernel for this strip size");
         }
         break;

@@ -21,6 +21,10 @@
 //
 // The arithmetic is slf_node.h's, called as fast_row_kernel calls it; with -ffp-contract=off the result is bit-identical
 // to two single steps.  Not served: macro field output (options bit 0), body forces, node maps, x-face buffers.
+//
+// Phase A has two load paths (template argument PF, SLF_PAIR_PREFETCH).  PF 0 loads a row into registers and waits for it
+// before it collides.  PF 1 keeps the NEXT row of the march in flight while the current one collides: the loads write LDS
+// directly (no register destination, so the 19 values in flight cost no VGPRs), see the comment at stage_row below.
 #include "slf_dispatch.h"
 #include "slf_rowpush.h"
 
@@ -37,11 +41,31 @@ __device__ __forceinline__ int wrap1(int c, int n) {      // c in 0 .. n + 1 -> 
   return c;
 }
 
-template <int MODEL, int TY>
+// PF > 0: the stage of phase A's asynchronous loads (dynamic LDS: 19 x 64 words per wave of the row)
+extern __shared__ float s_stage[];
+#define SLF_LDS __attribute__((address_space(3)))
+
+// The workgroup barrier of phase B.  RAW: `s_waitcnt lgkmcnt(0)` + `s_barrier` and nothing else -- __syncthreads() carries
+// a fence that, with an LDS-DMA outstanding, waits vmcnt(0) and so would drain the prefetch of the next plane's first row.
+// The LDS words the barrier orders (s_in_*, s_out_*) are written and read by ds_ instructions only: lgkmcnt(0) retires the
+// writes of this wave, the memory clobbers keep the compiler from moving LDS accesses across.
+template <bool RAW>
+__device__ __forceinline__ void pair_barrier() {
+  if constexpr (RAW) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  } else {
+    __syncthreads();
+  }
+}
+
+template <int MODEL, int TY, int PF>
 __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const SweepParams<D3Q19, float> p, const int zc) {
   using L = D3Q19;
   static_assert(MODEL == 0, "BGK only");
   static_assert(TY % 2 == 0, "the push slots alternate by row");
+  static_assert(PF == 0 || PF == 1, "ring depth");
   constexpr int NXD = count_x_dirs<L>();
   // raw intermediate values at the wave edges, per register plane: written as phase A produces them
   __shared__ float s_in_p[3][TY][PAIR_NW][NXD], s_in_m[3][TY][PAIR_NW][NXD];
@@ -71,6 +95,47 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
     static_for<0, L::Q>([&](auto I) { P0[J][I] = P1[J][I] = P2[J][I] = 0.0f; });
   });
 
+  // PF: the 19 values of a row go straight to LDS (global_load_lds_dword: no VGPR destination), each wave the 64 x of its
+  // own segment into words of its own.  The image is lane-linear (wave-uniform base in M0 + lane x 4) and the wave reads
+  // it back at its own lane, so no other wave touches the words and staging needs no barrier.  What orders the accesses
+  // is written by hand, the compiler emits none of it:
+  //   s_waitcnt vmcnt(0)    before the first read of a staged row: the DMAs have landed (a missing wait reads stale words);
+  //   s_waitcnt lgkmcnt(0)  after the 19 reads, before the refill: the reads have returned, the words may be overwritten.
+  // The refill is the NEXT row of the march (after the last row of a plane: the first row of the next plane), so its
+  // latency runs under this wave's collision of the current row resp. under the whole of phase B.
+  // One statement issues the 19 DMAs of a row: source = wave-uniform base of the direction (an SGPR pair, here VCC, stepped
+  // by the distance between two directions) + the lane's x in a VGPR shared by all 19, non-temporal as the loads of the
+  // synchronous form are; destination = M0 (the compiler's register: saved and put back) + lane x 4, stepped by 256 B.
+  float* const stage_w = s_stage + sgpr(w * (L::Q * 64));
+  const uint32_t stage_m0 = sgpr((uint32_t)(uintptr_t)(SLF_LDS float*)stage_w);
+  const uint64_t dir_bytes = (uint64_t)ds * sizeof(float);
+  const uint32_t dlo = sgpr((uint32_t)dir_bytes), dhi = sgpr((uint32_t)(dir_bytes >> 32));
+  auto stage_row = [&](int gy, int gz) {
+    const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gz);
+    const uint64_t src = (uint64_t)(p.din + row);
+    const uint32_t slo = sgpr((uint32_t)src), shi = sgpr((uint32_t)(src >> 32));
+    uint32_t keep;
+    static_assert(L::Q == 19 && (PAIR_NT & 1), "the statement below: 1 + 18 loads, nt");
+    asm volatile(
+        "s_mov_b32 %[keep], m0\n\t"
+        "s_mov_b32 vcc_lo, %[slo]\n\t"
+        "s_mov_b32 vcc_hi, %[shi]\n\t"
+        "s_mov_b32 m0, %[lds]\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dword %[xb], vcc nt\n\t"
+        ".rept 18\n\t"
+        "s_add_u32 m0, m0, 0x100\n\t"
+        "s_add_u32 vcc_lo, vcc_lo, %[dlo]\n\t"
+        "s_addc_u32 vcc_hi, vcc_hi, %[dhi]\n\t"
+        "global_load_lds_dword %[xb], vcc nt\n\t"
+        ".endr\n\t"
+        "s_mov_b32 m0, %[keep]"
+        : [keep] "=&s"(keep)
+        : [slo] "s"(slo), [shi] "s"(shi), [lds] "s"(stage_m0), [dlo] "s"(dlo), [dhi] "s"(dhi), [xb] "v"(xb)
+        : "vcc", "scc", "memory");
+  };
+  if constexpr (PF > 0) stage_row(sgpr(wrap1(y0 - 1, ny)), sgpr(wrap1(z0 - 1, nz)));
+
   int c0 = 0, c1 = 1, c2 = 2;     // LDS slots of the planes k - 1, k, k + 1
   for (int s = 0; s < zn + 2; s++) {
     const int gz = sgpr(wrap1(z0 - 1 + s, nz));
@@ -79,11 +144,19 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
     static_for<0, TY + 2>([&](auto RR) {
       constexpr int rr = (int)RR - 1;
       const int gy = sgpr(wrap1(y0 + rr, ny));
-      const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gz);
       float f[L::Q];
-      static_for<0, L::Q>([&](auto I) {
-        f[I] = ldg<PAIR_NT>(at_byte(uniform_base(p.din + ds * (size_t)I + row), xb));
-      });
+      if constexpr (PF > 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        static_for<0, L::Q>([&](auto I) { f[I] = stage_w[(int)I * 64 + lane]; });
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if constexpr (rr < TY) stage_row(sgpr(wrap1(y0 + rr + 1, ny)), gz);
+        else if (s + 1 < zn + 2) stage_row(sgpr(wrap1(y0 - 1, ny)), sgpr(wrap1(z0 + s, nz)));
+      } else {
+        const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gz);
+        static_for<0, L::Q>([&](auto I) {
+          f[I] = ldg<PAIR_NT>(at_byte(uniform_base(p.din + ds * (size_t)I + row), xb));
+        });
+      }
       float rho, v[3];
       macro_standard<L, float>(f, inc, rho, v);
       if constexpr (rr >= 0 && rr < TY) {
@@ -119,7 +192,7 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
       const int gzb = sgpr(z0 + s - 2);
       AxisOff oz = axis_off(gzb, g.lat_nz, g.arr_nxy, 1);
       oz.p = sgpr(oz.p); oz.m = sgpr(oz.m);
-      __syncthreads();
+      pair_barrier<(PF > 0)>();
       static_for<0, TY>([&](auto J) {
         constexpr int buf = (int)J & 1;
         float f[L::Q];
@@ -145,7 +218,7 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
           int k = 0;
           static_for<1, L::Q>([&](auto I) { if constexpr (L::ex(I) < 0) s_out_m[buf][w][k++] = f[I]; });
         }
-        __syncthreads();
+        pair_barrier<(PF > 0)>();
         const uint32_t row = sgpr((uint32_t)g.arr_nx * (uint32_t)gy + (uint32_t)g.arr_nxy * (uint32_t)gzb);
         AxisOff oy = axis_off(gy, g.lat_ny, g.arr_nx, 1);
         oy.p = sgpr(oy.p); oy.m = sgpr(oy.m);
@@ -173,11 +246,14 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
 
 }  // namespace
 
-int pair_default_rows() { return 2; }
-int pair_default_zchunk() { return 64; }
+// Four-row strips where the box allows them: with the next row in flight under the collision they are what the bytes say
+// (reads 1.5 x 66/64 against 2 x 66/64), profiles/NOTES.md; two-row strips only need an even ny.
+int pair_default_rows(const Geometry& g) { return (g.lat_ny - 2) % 4 == 0 ? 4 : 2; }
+int pair_default_zchunk(const Geometry&) { return 64; }
+int pair_default_prefetch() { return 1; }
 
 const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                         int rows, int zc) {
+                         int rows, int zc, int prefetch) {
   if (sel.lattice != 1 || sel.precision != 4 || sel.model != 0) return "pair sweep: D3Q19, single precision, BGK modules only";
   if (!two_copy) return "pair sweep: the two-copy (AB) access pattern only";
   if (sel.general || a.map) return "pair sweep: modules without a node map only";
@@ -191,6 +267,7 @@ const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometr
   if (rows != 2 && rows != 4) return "pair sweep: 2 or 4 rows per strip";
   if (ny % rows != 0) return "pair sweep: ny must be a multiple of the rows per strip";
   if (zc < 1) return "pair sweep: planes per chunk must be positive";
+  if (prefetch != 0 && prefetch != 1) return "pair sweep: SLF_PAIR_PREFETCH is 0 (synchronous loads) or 1 (one row staged in LDS)";
   if (!a.dist_in || !a.dist_out) return "pair sweep: source or destination array is NULL";
   if (a.dist_in == a.dist_out) return "pair sweep: source and destination must be different arrays";
   if (a.options & 1u) return "pair sweep: macro field output is not served (options bit 0)";
@@ -198,15 +275,20 @@ const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometr
 }
 
 bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                       int rows, int zc, hipStream_t s, hipError_t* err) {
-  if (pair_refusal(sel, two_copy, g, ph, a, rows, zc)) return false;
+                       int rows, int zc, int prefetch, hipStream_t s, hipError_t* err) {
+  if (pair_refusal(sel, two_copy, g, ph, a, rows, zc, prefetch)) return false;
   const SweepParams<D3Q19, float> p = make_params<D3Q19, float>(g, ph, a, 1, 1);
   const int nx = g.lat_nx - 2, ny = g.lat_ny - 2, nz = g.lat_nz - 2;
   if (zc > nz) zc = nz;
   dim3 block(nx, 1, 1);
   dim3 grid(1, ny / rows, (nz + zc - 1) / zc);
+  // the stage of the asynchronous loads: 19 x 64 words per wave of the row (38 912 B at nx = 512: two workgroups of
+  // two-row strips resp. one of four-row strips per CU, as the registers allow; narrower rows take less)
+  const size_t lds = prefetch ? (size_t)(nx / 64) * D3Q19::Q * 64 * sizeof(float) : 0;
   const bool done = pick<int, 2, 4>(rows, [&](auto TY) {
-    hipLaunchKernelGGL((pair_row_kernel<0, TY>), grid, block, 0, s, p, zc);
+    pick<int, 0, 1>(prefetch, [&](auto PF) {
+      hipLaunchKernelGGL((pair_row_kernel<0, TY, PF>), grid, block, lds, s, p, zc);
+    });
   });
   if (done) *err = hipGetLastError();
   return done;
