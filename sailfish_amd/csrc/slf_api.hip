@@ -115,6 +115,7 @@ struct slf_kernel {
   bool alpha_arg = false;   // CollideAndPropagate of an entropic module: the last pointer is the alpha field
   int pair_rows = 0, pair_zc = 0;   // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); 0: single steps
   int pair_prefetch = 0;            // ... with this load path in phase A (SLF_PAIR_PREFETCH)
+  int pair_xcd_log2 = 0, pair_march = 0;      // ... this strip placement and row order (SLF_PAIR_XCD_LOG2, SLF_PAIR_MARCH)
 };
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
@@ -1748,22 +1749,30 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   const slf_module* m = k->mod;
   const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows(m->geo);
   const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk(m->geo);
-  // SLF_PAIR_PREFETCH: the load path of phase A (0: synchronous; unset: the default); read here, per kernel object
-  int prefetch = slf::pair_default_prefetch();
-  if (const char* e = getenv("SLF_PAIR_PREFETCH")) {
+  // The knobs of the kernel, read here, per kernel object (unset or empty: the default; not a small non-negative integer:
+  // -1, which pair_refusal names).  SLF_PAIR_PREFETCH: the load path of phase A (0: synchronous); SLF_PAIR_XCD_LOG2:
+  // neighbouring strips on one XCD, at most 1 << this each (0: off); SLF_PAIR_MARCH: 1 = odd strips walk downwards
+  auto knob = [](const char* name, int dflt) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
     char* end = nullptr;
     const long v = strtol(e, &end, 10);
-    if (*e) prefetch = (end && !*end && v >= 0 && v < 1000) ? (int)v : -1;
-  }
+    return (end && !*end && v >= 0 && v < 1000) ? (int)v : -1;
+  };
+  const int prefetch = knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch());
+  const int xcd_log2 = knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2());
+  const int march = knob("SLF_PAIR_MARCH", slf::pair_default_march());
   if (m->sc.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
   slf::SweepArgs a = {};
   pair_args(k, a);
-  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc, prefetch))
+  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc, prefetch, xcd_log2, march))
     return fail(SLF_ERR_UNSUPPORTED, why);
   k->pair_rows = rows;
   k->pair_zc = zc;
   k->pair_prefetch = prefetch;
+  k->pair_xcd_log2 = xcd_log2;
+  k->pair_march = march;
   return SLF_OK;
 }
 
@@ -1784,10 +1793,10 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
         slf::SweepArgs pa = {};
         pair_args(k, pa);
         if (region) return fail(SLF_ERR_UNSUPPORTED, "pair sweep: whole-box launches only");
-        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, k->pair_prefetch, s,
-                                    &e)) {
+        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, k->pair_prefetch,
+                                    k->pair_xcd_log2, k->pair_march, s, &e)) {
           const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc,
-                                              k->pair_prefetch);
+                                              k->pair_prefetch, k->pair_xcd_log2, k->pair_march);
           return fail(SLF_ERR_UNSUPPORTED, why ? why : "pair sweep: no kernel for this strip size");
         }
         break;

@@ -206,15 +206,19 @@ size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y);
 // ---- two steps per launch of the two-copy sweep (slf_pair.hip): periodic D3Q19 / f32 / BGK boxes ----
 // a.dist_in: the populations of step t, a.dist_out: where those of step t + 2 go; strips of `rows` rows (2 or 4), chunks
 // of `zc` planes; prefetch: 0 = phase A loads into registers and waits, 1 = the next row is in flight to LDS while the
-// current one collides.  pair_refusal: why the module / the arguments do not qualify, NULL if they do; launch_sweep_pair
+// current one collides; xcd_log2: neighbouring strips go to one XCD, at most 1 << this each (0: strips as they come); march:
+// 1 = odd strips walk phase A's rows downwards.  pair_refusal: why the module / the arguments do not qualify, NULL if they do; launch_sweep_pair
 // returns false (nothing launched) in exactly those cases.
 const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                         int rows, int zc, int prefetch);
+                         int rows, int zc, int prefetch, int xcd_log2, int march);
 bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                       int rows, int zc, int prefetch, hipStream_t s, hipError_t* err);
+                       int rows, int zc, int prefetch, int xcd_log2, int march, hipStream_t s, hipError_t* err);
 int pair_default_rows(const Geometry& g);
 int pair_default_zchunk(const Geometry& g);
 int pair_default_prefetch();
+int pair_default_xcd_log2();
+int pair_default_march();
+int pair_xcd_shift(int strips, int limit);
 
 // ---- flow statistics (slf_stats.hip): 3-D lattices, fields in the module's dense layout ----
 // Launch shape of a statistics pass: a function of the lattice size alone, so the order of every addition is too.
