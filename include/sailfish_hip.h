@@ -548,6 +548,27 @@ int slf_stats_ke_enstrophy(slf_module* m, const void* map, const void* vx, const
 int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, const void* vz, const void* rho,
                        void* workspace, double* out, size_t out_stride, size_t offset, slf_stream* stream);
 
+/* ---- force on bodies by momentum exchange: the reference's ForceObject (lb_base.py:418-456; kernel
+ *      ComputeForceObjects, templates/kernel_force_objects.mako, whose per-link values the reference copies to the host
+ *      and sums there).  An entry point, not a slf_kernel_get name.  A link l is a solid node, a direction dir[l] = i
+ *      (1 .. Q - 1) that points from it to a fluid node, and the two words of the distribution array of lattice 0 that hold
+ *      the populations crossing it after propagation: idx[l] and idx2[l], indices into `dist` counted in elements of the
+ *      module's precision (population * dist_stride + node or slot).  Object o owns the links seg[o] .. seg[o + 1] - 1.
+ *        out[3 o + k] = sum over the links of object o of (double)(dist[idx[l]] + dist[idx2[l]]) * e_opp(i)[k],
+ *      the bracket formed in the module's precision, the sum in double without floating-point atomics in an order the
+ *      tables alone fix (chunks of 4096 links cut from the object's first link; the same data give the same bits, and
+ *      an object's sum does not depend on the other objects of the call).  k = 2 is 0 for D2Q9; an object without links
+ *      gives zeros.  All of dist, idx, idx2, dir, seg, workspace and out are device pointers; the indices are NOT checked
+ *      on the device: the caller keeps them below Q * dist_stride.  max_links is the largest seg[o + 1] - seg[o]
+ *      (it sizes the launch; links beyond it would be left out).  Single-fluid modules, D2Q9 and D3Q19, either
+ *      precision, access pattern and addressing mode; everything is enqueued on `stream`; n_objects = 0 does nothing.
+ *        slf_force_workspace_bytes  size of `workspace` for a call with these counts (0: every object fits one chunk,
+ *                                   the call is a single launch and workspace may be NULL). ---- */
+int slf_force_workspace_bytes(slf_module* m, int n_objects, uint32_t max_links, size_t* bytes);
+int slf_force_objects(slf_module* m, const void* dist, const uint32_t* idx, const uint32_t* idx2, const uint8_t* dir,
+                      const uint32_t* seg, int n_objects, uint32_t max_links, void* workspace, double* out,
+                      slf_stream* stream);
+
 /* ---- step plans (extension): the launch list of ONE time step, built once, enqueued with one call.
  *      The reference enqueues every kernel, event and copy of a step from Python (SubdomainRunner.step(),
  *      subdomain_runner.py:960-974; the boundary / bulk overlap with its event chain, :1028-1058; _send_dists /

@@ -335,6 +335,7 @@ class HIPBackend(placement.VmmMixin):
         self.options = options
         self.gpu_id = gpu_id
         self.buffers = {}   # device address -> host mirror
+        self.buffer_streams = {}    # device address -> stream whose enqueued work produces it (from_buf waits for it once)
         self._sizes = {}
         self._raw = {}
         self._placed = {}
@@ -531,6 +532,9 @@ class HIPBackend(placement.VmmMixin):
 
     def from_buf(self, buf, target=None):
         host = self._resolve(buf, target)
+        producer = self.buffer_streams.pop(buf, None)
+        if producer is not None:        # a result enqueued on a (non-blocking) stream: the copy below would not wait for it
+            producer.synchronize()
         for a, off, n in self._segments(buf, host.nbytes):
             _check(self._lib, self._lib.slf_memcpy_d2h(self._ctx, host.ctypes.data + off, ctypes.c_void_p(a), n),
                    'slf_memcpy_d2h')
@@ -673,6 +677,25 @@ class HIPBackend(placement.VmmMixin):
                                                        P(gpu_v[2] if len(gpu_v) > 2 else None), P(gpu_rho), P(workspace),
                                                        P(out), int(out_stride), int(offset),
                                                        stream.handle if stream else None), 'slf_stats_profiles')
+
+    # -- force on bodies by momentum exchange (C ABI slf_force_*; lb_base.ForceObject) ---------------
+    def force_workspace(self, module, n_objects, max_links):
+        """Device workspace of force_objects() calls with these counts; 0 where the call needs none (no object has more
+        than hipabi.SLF_FORCE_CHUNK links)."""
+        n = ctypes.c_size_t()
+        _check(self._lib, self._lib.slf_force_workspace_bytes(module.handle, int(n_objects), int(max_links), ctypes.byref(n)),
+               'slf_force_workspace_bytes')
+        return self.alloc_buf(size=n.value) if n.value else 0
+
+    def force_objects(self, module, gpu_dist, idx, idx2, dirs, seg, n_objects, max_links, workspace, out, stream=None):
+        """Enqueues: out[3 o + k] (device doubles) = sum over the links seg[o] .. seg[o + 1] - 1 of
+        (dist[idx] + dist[idx2]) e_opp(dirs)[k].  idx / idx2 (uint32 word indices into the distribution array at
+        `gpu_dist`), dirs (uint8), seg (uint32, n_objects + 1 offsets) are device addresses; the indices are not checked on
+        the device."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_force_objects(module.handle, P(gpu_dist), P(idx or None), P(idx2 or None), P(dirs or None),
+                                                      P(seg), int(n_objects), int(max_links), P(workspace or None), P(out),
+                                                      stream.handle if stream else None), 'slf_force_objects')
 
     @staticmethod
     def supports_row_classes(desc):

@@ -1498,6 +1498,38 @@ int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, 
   return SLF_OK;
 }
 
+// ---- force on bodies by momentum exchange (slf_force.hip) --------------------------------------------------------
+static int check_force_call(const slf_module* m, int n_objects, uint32_t max_links, const char* what) {
+  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  if (m->sc.enabled)
+    return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": single-fluid modules only (the force is read off lattice 0 alone)");
+  if (n_objects < 0 || n_objects > 65535) return fail(SLF_ERR_INVALID, std::string(what) + ": 0 .. 65535 objects per call");
+  if (max_links > 0x7FFFFFFFu) return fail(SLF_ERR_INVALID, std::string(what) + ": fewer than 2^31 links");
+  return SLF_OK;
+}
+
+int slf_force_workspace_bytes(slf_module* m, int n_objects, uint32_t max_links, size_t* bytes) {
+  if (int e = check_force_call(m, n_objects, max_links, "slf_force_workspace_bytes")) return e;
+  if (!bytes) return fail(SLF_ERR_INVALID, "bytes is NULL");
+  *bytes = slf::force_shape(n_objects, max_links).workspace_doubles * sizeof(double);
+  return SLF_OK;
+}
+
+int slf_force_objects(slf_module* m, const void* dist, const uint32_t* idx, const uint32_t* idx2, const uint8_t* dir,
+                      const uint32_t* seg, int n_objects, uint32_t max_links, void* workspace, double* out,
+                      slf_stream* stream) {
+  if (int e = check_force_call(m, n_objects, max_links, "slf_force_objects")) return e;
+  if (n_objects == 0) return SLF_OK;
+  if (!dist || !seg || !out) return fail(SLF_ERR_INVALID, "slf_force_objects: dist / seg / out is NULL");
+  if (max_links && (!idx || !idx2 || !dir)) return fail(SLF_ERR_INVALID, "slf_force_objects: a link table is NULL");
+  if (slf::force_shape(n_objects, max_links).workspace_doubles && !workspace)
+    return fail(SLF_ERR_INVALID, "slf_force_objects: workspace is NULL (slf_force_workspace_bytes)");
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  SLF_HIP(slf::launch_force_objects(m->sel, dist, idx, idx2, dir, seg, n_objects, max_links, (double*)workspace, out,
+                                    native(stream)));
+  return SLF_OK;
+}
+
 int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   if (!m || !name || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   KernelKind kk;

@@ -239,4 +239,16 @@ hipError_t launch_stats_profiles(const KernelSelector& sel, const Geometry& g, i
                                  const void* rho, double* workspace, double* out, size_t out_stride, size_t offset,
                                  hipStream_t s);
 
+// ---- momentum-exchange force on bodies (slf_force.hip): lattice 0 of a module, any access pattern and addressing ----
+constexpr int FORCE_CHUNK = 4096;   // links of one object a workgroup adds up; the chunks of an object are added in index order
+struct ForceShape {
+  int block, grid_x;           // grid_x: chunks of the longest object
+  size_t workspace_doubles;    // partial sums of the chunks (0 when every object is one chunk: no second launch)
+};
+ForceShape force_shape(int n_objects, uint32_t max_links);
+// out[3 o + k] = sum over the links l = seg[o] .. seg[o + 1] - 1 of (double)(dist[idx[l]] + dist[idx2[l]]) * e_opp(dir[l])[k]
+hipError_t launch_force_objects(const KernelSelector& sel, const void* dist, const uint32_t* idx, const uint32_t* idx2,
+                                const uint8_t* dir, const uint32_t* seg, int n_objects, uint32_t max_links,
+                                double* workspace, double* out, hipStream_t s);
+
 }  // namespace slf

@@ -180,6 +180,8 @@ SIGNATURES = {
     'slf_stats_workspace_bytes': (c_int, [c_void_p, c_int, POINTER(c_size_t)]),
     'slf_stats_ke_enstrophy': (c_int, [c_void_p] * 10),
     'slf_stats_profiles': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_size_t, c_void_p]),
+    'slf_force_workspace_bytes': (c_int, [c_void_p, c_int, c_uint32, POINTER(c_size_t)]),
+    'slf_force_objects': (c_int, [c_void_p] * 6 + [c_int, c_uint32, c_void_p, c_void_p, c_void_p]),
     'slf_last_error': (c_char_p, []),
 }
 
@@ -191,6 +193,7 @@ SLF_INVALID_NODE = 0xffffffff
 SLF_PEER_HANDLE_BYTES, SLF_PEER_CHANNELS = 64, 4
 SLF_STATS_KE_ENSTROPHY, SLF_STATS_PROFILES_X, SLF_STATS_PROFILES_Y, SLF_STATS_PROFILES_Z = range(4)
 SLF_STATS_PROFILE_COUNT = 22
+SLF_FORCE_CHUNK = 4096      # links per partial sum of slf_force_objects
 
 _lib = None
 

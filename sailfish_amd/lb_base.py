@@ -34,6 +34,38 @@ class VectorField(Field):
     pass
 
 
+class ForceObject(object):
+    """Tracks the momentum exchanged between the fluid and a solid body, i.e. the force ON the body (reference
+    lb_base.py:418-456; Ladd, Phys. Rev. Lett. 88, 048301).  start / end: lowest / highest corner of the body's bounding
+    box in global node coordinates, both inclusive.  Register it with LBSim.add_force_oject(); a step's force is read with
+
+        runner.update_force_objects()                   # enqueued, no host wait
+        runner.backend.from_buf(fo.gpu_force_buf)       # dim doubles
+        fx, fy[, fz] = fo.force()
+
+    Every subdomain runner has a simulation object, and so force objects, of its own; force() is the part of the links
+    this subdomain owns.  The sum over the links is formed on the device (csrc/slf_force.hip)."""
+
+    def __init__(self, start, end):
+        self.start = start
+        self.end = end
+        self.id = None
+        self.num_links = 0              # links in this subdomain
+        self.gpu_force_buf = None       # device address of this object's sums
+        self.force_buf = None           # (dim,) float64 host mirror, filled by backend.from_buf(gpu_force_buf)
+
+    @property
+    def initialized(self):
+        return self.force_buf is not None
+
+    def __str__(self):
+        return 'ForceObject(id=%s)' % self.id
+
+    def force(self):
+        """Force on the object: a list of dim floats (lattice units), as of the last from_buf(gpu_force_buf)."""
+        return [float(x) for x in self.force_buf]
+
+
 class LBSim(object):
     """Describes a type of LB simulation (reference lb_base.py:30-320)."""
     subdomain_runner = None
@@ -173,6 +205,13 @@ class LBSim(object):
 
     def initial_conditions(self, runner):
         pass
+
+    def add_force_oject(self, obj):
+        """Registers a ForceObject (the reference's spelling, lb_base.py:297-299)."""
+        obj.id = len(self.force_objects)
+        self.force_objects.append(obj)
+
+    add_force_object = add_force_oject
 
     @classmethod
     def check_module_desc(cls, kw):

@@ -355,6 +355,9 @@ class Subdomain(object):
         cfg = self.config
         self._type_map_encoded = False
         self.boundary_conditions(*self._get_mgrid_base(cfg))
+        if getattr(getattr(self.spec.runner, '_sim', None), 'force_objects', None):
+            # what the user's boundary conditions made of the ghost layer, before it is overwritten (fo_links_leaving)
+            self._user_type_map = np.array(self._type_map_ghost, dtype=np.uint8)
         self._define_ghosts(unset_only=True)
         self._postprocess_nodes()
         tagged = False
@@ -370,6 +373,66 @@ class Subdomain(object):
         if encode:
             self.encoded_map()
         cfg.logger.info('Fluid node fraction: %.1f%%' % (100.0 * self.num_fluid_nodes / self.spec.num_nodes))
+
+    # -- force objects ---------------------------------------------------------------------
+    def _fo_solid_nodes(self, fo):
+        """Real nodes inside the bounding box of `fo` that are not plain fluid nodes."""
+        cond = self._type_vis_map != nt._NTFluid.id
+        for mx, x0, x1 in zip(self._get_mgrid(), fo.start, fo.end):
+            cond &= (mx >= x0) & (mx <= x1)
+        return cond
+
+    def get_fo_distributions(self, fo):
+        """Which distributions carry momentum between the ForceObject `fo` and the fluid (reference subdomain.py:734-770):
+        dict direction index -> tuple of coordinate arrays (numpy axis order, envelope offset included, np.where order) of
+        the non-fluid nodes inside the object's box whose neighbour along that direction is a plain fluid node.  As in
+        the reference the neighbourhood wraps around the array of real nodes; the runner refuses the links that do
+        (SubdomainRunner._init_force_objects)."""
+        cond = self._fo_solid_nodes(fo)
+        self.config.logger.debug('%s: num solid nodes: %d' % (fo, np.sum(cond)))
+        ret = {}
+        for i, vec in enumerate(self.grid.basis[1:], 1):
+            t = np.where(cond & (self._at_neighbour(self._type_vis_map, vec) == nt._NTFluid.id))
+            if t[0].size > 0:
+                ret[i] = tuple(x + self.spec.envelope_size for x in t)
+        return ret
+
+    FACE_NAMES = ('x_low', 'x_high', 'y_low', 'y_high', 'z_low', 'z_high')
+
+    def fo_links_leaving(self, fo):
+        """(direction index, face name, global position of the solid node) of the first momentum-carrying link of `fo` whose
+        fluid end is not a real node of this subdomain, or None.  Decided from the node map WITH its ghost layer: a ghost
+        node counts as fluid when it stands for a node of the global lattice (behind a connected face, or the periodic
+        image of a real node) that the boundary conditions left plain fluid."""
+        es = self.spec.envelope_size
+        user = getattr(self, '_user_type_map', None)
+        if user is None or not es:
+            return None
+        # ghost-including map: real nodes as they are simulated, ghost nodes as above, everything else not fluid
+        full = np.full(self.full_lat_shape, nt._NTGhost.id, dtype=np.uint8)
+        inside = np.ones(self.full_lat_shape, dtype=bool)
+        periodic = [self.config.periodic_x, self.config.periodic_y] + ([self.config.periodic_z] if self.dim == 3 else [])
+        for axis, (g, size) in enumerate(zip(self._index_grids(es), reversed(self.grid_shape))):
+            if not periodic[axis]:
+                inside &= (g >= 0) & (g < size)
+        full[inside] = user[inside]
+        full[self.spec._nonghost_slice] = self._type_vis_map
+        real = np.zeros(self.full_lat_shape, dtype=bool)
+        real[self.spec._nonghost_slice] = True
+        cond = np.zeros(self.full_lat_shape, dtype=bool)
+        cond[self.spec._nonghost_slice] = self._fo_solid_nodes(fo)
+        for i, vec in enumerate(self.grid.basis[1:], 1):
+            # (rolling the ghost-including array: what wraps lands on ghost nodes, which are no solid nodes of the box)
+            hit = cond & (self._at_neighbour(full, vec) == nt._NTFluid.id) & ~self._at_neighbour(real, vec)
+            if hit.any():
+                pos = np.argwhere(hit)[0]
+                for axis in range(self.dim):
+                    p = int(pos[self.dim - 1 - axis]) + int(vec[axis])
+                    if p < es or p >= es + self.spec.size[axis]:
+                        face = self.FACE_NAMES[2 * axis + int(p >= es)]
+                        where = tuple(int(pos[self.dim - 1 - a]) - es + self.spec.location[a] for a in range(self.dim))
+                        return i, face, where
+        return None
 
     @property
     def scratch_space_size(self):

@@ -48,6 +48,9 @@ class SubdomainRunner(object):
         self._spec = spec
         self._output = output
         self.backend = backend
+        if quit_event is None:          # always there: a user hook ends the run with runner._quit_event.set()
+            import threading
+            quit_event = threading.Event()
         self._quit_event = quit_event
         self.config = simulation.config
         self._spec.runner = self
@@ -742,6 +745,113 @@ class SubdomainRunner(object):
                 streams[0].wait_for_event(self._ev_chunk[par][len(plan.order) - 1])
             prof.record_gpu_end(TimeProfile.BULK, streams[0])
 
+    # ------------------------------------------------------------------ force objects (lb_base.ForceObject)
+    _fo_tables = None
+
+    def _init_force_objects(self):
+        """Link tables of the simulation's force objects on the device (reference subdomain_runner.py:1459-1509): per link
+        the two words of the distribution array of lattice 0 that hold the populations crossing it after propagation, and its
+        direction.  Links in the reference's order -- objects, ascending direction, np.where order of the solid node --
+        whatever the access pattern and the addressing mode; all objects of the subdomain share one set of tables, object k
+        owning the links seg[k] .. seg[k + 1] - 1.
+
+        Word indices.  Link "solid node s, direction i, fluid node f = s + e_i": the reference reads dist[opp(i)][s] +
+        dist[i][f] of the copy the last step wrote.  In the in-place pattern the array is in that natural order after an
+        even number of steps; after an odd number the post-propagation value of direction k at node x sits in slot opp(k)
+        at x - e_k, which puts the first term at (i, f) and the second at (opp(i), s): the same two words.  One table
+        serves both patterns and both parities."""
+        sim, sub = self._sim, self._subdomain
+        if not sim.force_objects:
+            return
+        cfg = self.config
+        if len(sim.grids) != 1 or int(self._desc.simtype) != hipabi.SLF_SIM_LBM:
+            raise NotImplementedError('force objects: single-fluid simulations only (the momentum exchange is read off one '
+                                      'lattice; Shan-Chen and binary models are not covered)')
+        if getattr(cfg, 'minimize_roundoff', False):
+            raise NotImplementedError('force objects with --minimize_roundoff: the arrays hold f - w, not the populations')
+        if not hasattr(self.backend, 'force_objects'):
+            raise NotImplementedError('force objects: backend %s has no force_objects()' % getattr(self.backend, 'name', '?'))
+        cfg.logger.info('Processing force objects.')
+        grid, es = sim.grid, self._spec.envelope_size
+        stride, phys = self._dist_stride, self._physical_size
+        addr = self._host_indirect_address.reshape(-1) if self.indirect else None
+        idx, idx2, dirs, seg, live = [], [], [], [0], []
+        for fo in sim.force_objects:
+            dists = sub.get_fo_distributions(fo)
+            leaving = sub.fo_links_leaving(fo)
+            for dist_num, locs in sorted(dists.items()):
+                if leaving is not None:
+                    break
+                vec = grid.basis[dist_num]
+                for axis in range(self.dim):
+                    p = locs[self.dim - 1 - axis] + int(vec[axis])
+                    out = (p < es) | (p >= es + self._spec.size[axis])
+                    if out.any():
+                        k = int(np.nonzero(out)[0][0])
+                        where = tuple(int(locs[self.dim - 1 - a][k]) - es + self._spec.location[a] for a in range(self.dim))
+                        leaving = (dist_num, sub.FACE_NAMES[2 * axis + int(p[k] >= es)], where)
+                        break
+            if leaving is not None:
+                raise NotImplementedError(
+                    '%s (box %s .. %s): the link from the solid node %s along direction %d leaves subdomain %d through its '
+                    'face %s.  Momentum links across subdomain seams, periodic faces or the ghost layer are not supported: '
+                    'keep the object inside one subdomain and away from periodic faces.'
+                    % (fo, tuple(fo.start), tuple(fo.end), leaving[2], leaving[0], self._spec.id, leaving[1]))
+            if not dists:
+                cfg.logger.warning('No momentum-transferring distributions found for %s' % fo)
+                continue
+            for dist_num, locs in sorted(dists.items()):
+                vec = grid.basis[dist_num]
+                solid = np.ravel_multi_index(locs, phys).astype(np.int64)
+                fluid = np.ravel_multi_index(tuple(l + int(c) for l, c in zip(locs, reversed(vec))), phys).astype(np.int64)
+                if addr is not None:
+                    solid, fluid = addr[solid].astype(np.int64), addr[fluid].astype(np.int64)
+                    if (solid == hipabi.SLF_INVALID_NODE).any() or (fluid == hipabi.SLF_INVALID_NODE).any():
+                        raise ValueError('%s: a momentum link ends at a node that owns no slot in the distribution arrays '
+                                         '(the active-node map leaves out a solid node next to a fluid node)' % fo)
+                idx.append(grid.idx_opposite[dist_num] * stride + solid)       # momentum transferred to the solid node
+                idx2.append(dist_num * stride + fluid)                         # ... and from it
+                dirs.append(np.full(solid.size, dist_num, dtype=np.uint8))
+            seg.append(seg[-1] + sum(l[0].size for l in dists.values()))
+            fo.num_links = seg[-1] - seg[-2]
+            cfg.logger.debug('%s: total momentum links: %d' % (fo, fo.num_links))
+            live.append(fo)
+        if not live:
+            return
+        idx, idx2, dirs = np.concatenate(idx), np.concatenate(idx2), np.concatenate(dirs)
+        words = grid.Q * stride
+        assert idx.min() >= 0 and idx2.min() >= 0 and idx.max() < words and idx2.max() < words < 2 ** 32
+        b = self.backend
+        t = self._fo_tables = {'n': len(live), 'max_links': int(np.diff(seg).max()), 'objects': live,
+                               'host': (idx.astype(np.uint32), idx2.astype(np.uint32), dirs, np.array(seg, dtype=np.uint32)),
+                               'out_host': np.zeros(3 * len(live), dtype=np.float64)}
+        t['idx'], t['idx2'], t['dirs'], t['seg'] = [b.alloc_buf(like=a) for a in t['host']]
+        t['out'] = b.alloc_buf(like=t['out_host'])
+        t['workspace'] = b.force_workspace(self.module, t['n'], t['max_links'])
+        for k, fo in enumerate(live):
+            # the object's dim doubles inside the result array: from_buf(fo.gpu_force_buf) fills fo.force_buf
+            fo.force_buf = np.zeros(self.dim, dtype=np.float64)
+            fo.gpu_force_buf = t['out'] + 24 * k
+            b.buffers[fo.gpu_force_buf] = fo.force_buf
+
+    def update_force_objects(self):
+        """Enqueues, on the calc stream and without a host wait, the sums of all initialised force objects of this
+        subdomain from the populations as they are after the last completed step (they are read AFTER propagation,
+        reference subdomain_runner.py:1512-1526).  Read a result with backend.from_buf(fo.gpu_force_buf)."""
+        t = self._fo_tables
+        if t is None:
+            return
+        calc = self._calc_stream
+        for s in self._all_streams():
+            if s is not calc:         # whatever part of the step ran on another stream comes first
+                calc.wait_for_event(self.backend.make_event(s))
+        self.backend.force_objects(self.module, self.gpu_dist(0, self._sim.iteration & 1), t['idx'], t['idx2'], t['dirs'],
+                                   t['seg'], t['n'], t['max_links'], t['workspace'], t['out'], calc)
+        pending = getattr(self.backend, 'buffer_streams', None)
+        if pending is not None:       # from_buf() of a result waits for the stream that produces it, and for nothing else
+            for fo in t['objects']:
+                pending[fo.gpu_force_buf] = calc
+
     # ------------------------------------------------------------------ data movement
     def _fields_to_host(self, sync=True):
         bs = getattr(self, '_bnd_stream', None)
@@ -881,6 +991,7 @@ class SubdomainRunner(object):
         self._subdomain.init_fields(self._sim)
         self._sim.verify_fields()
         self._init_gpu_data()
+        self._init_force_objects()
         self._init_halo()
         self._prepare_compute_kernels()
         self._init_step_program()

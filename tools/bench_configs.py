@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -325,6 +325,65 @@ def main():
         res.append(run('9b: examples/sphere_3d.py D3Q19 BGK 512x256x256 (AA)', SphereSim, LBGeometry3D,
                        dict(lat_nx=512, lat_ny=256, lat_nz=256, access_pattern='AA', max_iters=int(1500 * it),
                             benchmark_sample_from=int(500 * it)), 152))
+    # 9c: the sphere of 9b with a force object around it (lb_base.ForceObject; csrc/slf_force.hip) read EVERY step, the way
+    # examples/square_cylinder_2d.py reads its force.  Three runs, because a simulation with an after_step hook is stepped
+    # one step at a time with a return to the host after each: the sphere with an empty hook (that cost alone), with the
+    # force enqueued every step and no read-back, and with update_force_objects() + from_buf() + force() every step.  Plus
+    # the device time of the force call alone: 20 calls enqueued back to back between two stream events.  Compare with 9b.
+    if '9c' in only:
+        from sailfish.lb_base import ForceObject
+
+        class HookedSphere(SphereSim):
+            def after_step(self, runner):
+                pass
+
+        class ForceSphere(SphereSim):
+            read_back = True
+
+            def __init__(self, config):
+                super(ForceSphere, self).__init__(config)
+                d = config.lat_ny / 3.0
+                lo, hi = 2.0 * d - d / 2 - 8, 2.0 * d + d / 2 + 8
+                self.add_force_oject(ForceObject((lo, config.lat_ny / 2.0 - d / 2 - 8, config.lat_nz / 2.0 - d / 2 - 8),
+                                                 (hi, config.lat_ny / 2.0 + d / 2 + 8, config.lat_nz / 2.0 + d / 2 + 8)))
+                self.last_force = None
+
+            def after_step(self, runner):
+                runner.update_force_objects()
+                if self.read_back:
+                    fo = self.force_objects[0]
+                    runner.backend.from_buf(fo.gpu_force_buf)
+                    self.last_force = fo.force()
+
+        class EnqueuedForceSphere(ForceSphere):
+            read_back = False
+
+        def force_call(ctrl):
+            r = ctrl.runners[0]
+            b, s, fo = r.backend, r._calc_stream, r._sim.force_objects[0]
+            r.update_force_objects()
+            t0 = b.make_event(s, timing=True)
+            for _ in range(20):
+                r.update_force_objects()
+            t1 = b.make_event(s, timing=True)
+            t1.synchronize()
+            b.from_buf(fo.gpu_force_buf)
+            return {'force_links': fo.num_links, 'force_call_ms': round(t1.time_since(t0) / 20, 4), 'force': fo.force()}
+
+        sphere = dict(lat_nx=512, lat_ny=256, lat_nz=256, access_pattern='AA', max_iters=int(1500 * it),
+                      benchmark_sample_from=int(500 * it))
+        hooked = run('9c: examples/sphere_3d.py D3Q19 BGK 512x256x256 (AA), empty after_step hook', HookedSphere, LBGeometry3D,
+                     sphere, 152)
+        enq = run('9c: the same sphere, force object enqueued every step, not read', EnqueuedForceSphere, LBGeometry3D, sphere,
+                  152, extra=force_call)
+        read = run('9c: the same sphere, force object read every step', ForceSphere, LBGeometry3D, sphere, 152, extra=force_call)
+        nodes = float(read['fluid_nodes'])
+        summary = {'config': '9c: summary', 'force_links': read['force_links'], 'force_call_ms': read['force_call_ms'],
+                   'step_ms_hook_only': round(nodes / (hooked['MLUPS_eff'] * 1e3), 4),
+                   'step_ms_force_enqueued': round(nodes / (enq['MLUPS_eff'] * 1e3), 4),
+                   'step_ms_force_read': round(nodes / (read['MLUPS_eff'] * 1e3), 4)}
+        print(json.dumps(summary), flush=True)
+        res += [hooked, enq, read, summary]
     # the entropic collision (--model=elbm, LBEntropicFluidSim: per-node kernels, the alpha field stored every step: 4 more
     # bytes per update) on the 256^3 lid-driven cavity at Re = 1000, with the polynomial and the product-form equilibrium.
     # Like-for-like baseline: 10c, the same cavity with BGK -- under SLF_VARIANT=0 through the per-node kernels as well.
