@@ -21,6 +21,7 @@ import math
 import os
 import pickle
 import time
+import weakref
 
 import numpy as np
 
@@ -37,6 +38,17 @@ class GPUBuffer(object):
     def __init__(self, host_buffer, backend):
         self.host = host_buffer
         self.gpu = backend.alloc_buf(like=host_buffer) if host_buffer is not None else None
+
+
+_hup_runners = weakref.WeakSet()        # runners that take part in SIGHUP -> checkpoint (_install_signal_handlers)
+_hup_state = {'previous': None}         # what handled SIGHUP before the first runner of the process
+
+
+def _hup_dispatch(signum, frame):
+    for runner in list(_hup_runners):
+        runner.sighup_handler(signum, frame)
+    if callable(_hup_state['previous']):
+        _hup_state['previous'](signum, frame)
 
 
 class SubdomainRunner(object):
@@ -973,13 +985,14 @@ class SubdomainRunner(object):
         import signal
         import threading
         if hasattr(signal, 'SIGHUP') and threading.current_thread() is threading.main_thread():
-            previous = signal.getsignal(signal.SIGHUP)
-
-            def handler(signum, frame):
-                self.sighup_handler(signum, frame)
-                if callable(previous):          # several runners in one process: every one gets the request
-                    previous(signum, frame)
-            signal.signal(signal.SIGHUP, handler)
+            # several runners in one process: every one gets the request.  One handler for the process and a weak set of
+            # runners -- a handler per runner that calls the one before it grows by a frame with every simulation the
+            # process has run (and keeps their runners alive): after a thousand of them SIGHUP ended in a RecursionError.
+            _hup_runners.add(self)
+            current = signal.getsignal(signal.SIGHUP)
+            if current is not _hup_dispatch:
+                _hup_state['previous'] = current
+                signal.signal(signal.SIGHUP, _hup_dispatch)
 
     def prepare(self):
         """Everything up to (not including) the main loop (reference run(), :1537-1602)."""

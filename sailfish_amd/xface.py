@@ -34,7 +34,7 @@ NXD = 5          # D3Q19 directions per sign of e_x
 
 def supported(grid, desc, indirect=False, simtype=0):
     """Can a module built from `desc` take x-face buffers (slf_module_set_xface_buffers)?  D3Q19 single fluid, direct
-    addressing, rows of at most 1024 nodes -- and the whole-row kernels must be what runs: the --minimize_roundoff
+    addressing, rows of at most 1024 nodes, no NTCopy / NTYuOutflow nodes -- and the whole-row kernels must be what runs: the --minimize_roundoff
     formulation lives in the per-node kernels only (slf_api.hip: variant = 0), and so does everything under an
     SLF_VARIANT without bit 8."""
     from sailfish_amd import hipabi
@@ -44,6 +44,12 @@ def supported(grid, desc, indirect=False, simtype=0):
         return False
     variant = os.environ.get('SLF_VARIANT')
     if variant is not None and not (int(variant) & 8):
+        return False
+    # NTCopy / NTYuOutflow nodes take their unknown populations from the input ARRAY of the nodes one / two steps upstream
+    # (slf_sweep.h: fixMissingDistributions).  On a y or z face next to a connected x face those include populations that
+    # entered through a face buffer and never reach the array: the x faces go through the ghost columns then.
+    if not desc.fluid_only and any(int(k) in (hipabi.SLF_NK_COPY, hipabi.SLF_NK_YU_OUTFLOW)
+                                   for k in desc.type_kind[:int(desc.n_types)]):
         return False
     return grid.dim == 3 and grid.Q == 19 and not indirect and not simtype and desc.lat_nx - 2 <= 1024
 

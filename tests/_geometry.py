@@ -1,7 +1,11 @@
 """Hand-encoded node maps for parity tests (test-only helper).
 
 Encoding = the reference's bit layout orientation | scratch | param | type
-(sailfish/geo_encoder.py:365-382) with a fixed dense type-id table."""
+(sailfish/geo_encoder.py:365-382) with a fixed dense type-id table.
+
+The channels here have their flow along +x and their walls on y (the x frame).  For anything else -- the flow along
+another axis or in the other sense, walls on x or z -- see tests/_faces.py, which builds the same channels in any frame
+from these encodings."""
 import numpy as np
 
 from sailfish_amd import hipabi as h

@@ -4,6 +4,7 @@ tests/test_gpu_indirect.py and tests/_indirect_worker.py on the GPU); test-only.
 The geometry: flow along x, walls on the two y rims, a solid block 6 nodes long and about half the channel high standing
 on the lower wall (its inner nodes have no fluid neighbour: they own no slot under indirect addressing), an inlet on
 hx == 0, an outlet on hx == gx - 1; z, where there is one, is periodic (`periodic_z=True` in the case's config).
+The cases whose names carry `@<frame>` lay the same geometry out with the flow along y or z (make_sim's `frame`).
 load_active_node_map() goes through set_active_node_map_from_wall_map(), as examples/external_geometry.py does."""
 import numpy as np
 
@@ -22,8 +23,15 @@ LEVEL = {'NTFullBBWall': 0, 'NTHalfBBWall': 1, 'NTRegularizedVelocity': 1, 'NTZo
          'NTZouHeDensity': 1, 'NTRegularizedDensity': 1, 'NTEquilibriumDensity': 1, 'NTCopy': 2, 'NTYuOutflow': 2, 'NTSlip': 2}
 
 
+def frame_axes(dim, frame):
+    """(a, s, b): flow axis, sign of the flow, wall axis of a frame of tests/_faces.py; None = the x frame."""
+    if frame is None:
+        return 0, 1, 1
+    return (frame[0], frame[1], frame[2]) if dim == 3 else (frame[0], frame[1], 1 - frame[0])
+
+
 def make_sim(dim, wall='NTFullBBWall', inlet=None, outlet=None, slip=False, force=None, halfbb_solid=True, block=None,
-             block_len=6, block_height=None, block_y0=1, u0=U_IN):
+             block_len=6, block_height=None, block_y0=1, u0=U_IN, frame=None):
     """An LBFluidSim subclass (with LBForcedSim and a body force when `force` is given).
     wall: node type of the y rims and of the block; slip: NTSlip on the y rims instead (the block keeps `wall`).
     inlet / outlet: node-type names for hx == 0 / hx == gx - 1 (velocity types get (U_IN, 0[, 0]), density types 1.0,
@@ -36,57 +44,70 @@ def make_sim(dim, wall='NTFullBBWall', inlet=None, outlet=None, slip=False, forc
     block is then an inner node of the block, without a slot.
     block_y0: the block's first row; 1 = it stands on the lower wall.  Under slip walls it must not: the mirror image of a
     link from a slip node below the block's edge into the fluid comes out of the block, where the dense run reads the
-    storage of a node that is not simulated and the sparse run has none."""
+    storage of a node that is not simulated and the sparse run has none.
+    frame: a frame of tests/_faces.py -- (flow axis, sign, wall axis) in 3-D, (flow axis, sign) in 2-D -- in which all of
+    the above is laid out: read "x" as the position along the flow axis counted from the upstream end, "y" as the
+    position along the wall axis; the inlet velocity, `u0` and `force` (given as its size along the flow) point along
+    the flow.  None = flow along +x, walls on y."""
     base = Subdomain2D if dim == 2 else Subdomain3D
     grid = D2Q9 if dim == 2 else D3Q19
-    zeros = (0.0,) * (dim - 1)
     at_outlet = block == 'outlet'
+    fa, fs, fb = frame_axes(dim, frame)
+
+    def unit(axis, size):
+        v = [0.0] * dim if isinstance(size, float) else [0] * dim
+        v[axis] = size
+        return v
 
     class ChannelSubdomain(base):
-        def _parts(self, hx, hy):
-            """(rims, block, inlet, outlet) over the given index grids; positions outside the domain are rim."""
-            rim = (hy <= 0) | (hy >= self.gy - 1) | (hx < 0) | (hx > self.gx - 1)
-            x0 = (self.gx - 1 - block_len) if at_outlet else (self.gx // 3 if block is None else block)
-            h = self.gy // 2 if block_height is None else block_height
-            blk = (hx >= x0) & (hx < x0 + block_len) & (hy >= block_y0) & (hy < block_y0 + h) & ~rim
+        def _parts(self, *h):
+            """(rims, block, inlet, outlet) over the given index grids; positions outside the domain are rim.  Works in
+            (position along the flow from the upstream end, position along the wall axis)."""
+            g = (self.gx, self.gy) + ((self.gz,) if dim == 3 else ())
+            gx, gy = g[fa], g[fb]
+            hx = h[fa] if fs > 0 else gx - 1 - h[fa]
+            hy = h[fb]
+            rim = (hy <= 0) | (hy >= gy - 1) | (hx < 0) | (hx > gx - 1)
+            x0 = (gx - 1 - block_len) if at_outlet else (gx // 3 if block is None else block)
+            ht = gy // 2 if block_height is None else block_height
+            blk = (hx >= x0) & (hx < x0 + block_len) & (hy >= block_y0) & (hy < block_y0 + ht) & ~rim
             free = ~rim & ~blk
             ins = free & (hx == 0) if inlet else np.zeros_like(rim)
-            outs = free & (hx == self.gx - 1) if outlet else np.zeros_like(rim)
-            return rim, blk, ins, outs
+            outs = free & (hx == gx - 1) if outlet else np.zeros_like(rim)
+            inside = (hx >= 0) & (hx <= gx - 1) & (hy >= 0) & (hy <= gy - 1)
+            return rim, blk, ins, outs, inside, hy, gy
 
-        def boundary_conditions(self, hx, hy, *hz):
-            rim, blk, ins, outs = self._parts(hx, hy)
-            rim = rim & (hx >= 0) & (hx <= self.gx - 1) & (hy >= 0) & (hy <= self.gy - 1)      # the ghost layers stay unset
+        def boundary_conditions(self, *h):
+            rim, blk, ins, outs, inside, hy, gy = self._parts(*h)
+            rim = rim & inside      # the ghost layers stay unset
             wall_type = getattr(nt, wall)
             if slip:
-                up = [0, 1] + [0] * (dim - 2)
-                down = [0, -1] + [0] * (dim - 2)
-                self.set_node(rim & (hy <= 0), nt.NTSlip(orientation=grid.vec_to_dir(up)))
-                self.set_node(rim & (hy >= self.gy - 1), nt.NTSlip(orientation=grid.vec_to_dir(down)))
+                self.set_node(rim & (hy <= 0), nt.NTSlip(orientation=grid.vec_to_dir(unit(fb, 1))))
+                self.set_node(rim & (hy >= gy - 1), nt.NTSlip(orientation=grid.vec_to_dir(unit(fb, -1))))
                 self.set_node(blk, wall_type)
             else:
                 self.set_node(rim | blk, wall_type)
             if inlet:
-                self.set_node(ins, getattr(nt, inlet)((U_IN,) + zeros))
+                self.set_node(ins, getattr(nt, inlet)(tuple(unit(fa, fs * U_IN))))
             if outlet:
                 cls = getattr(nt, outlet)
                 if cls.value_name == 'density':
                     self.set_node(outs, cls(1.0))
                 elif at_outlet:
-                    self.set_node(outs, cls(orientation=grid.vec_to_dir([-1] + [0] * (dim - 1))))
+                    self.set_node(outs, cls(orientation=grid.vec_to_dir(unit(fa, -fs))))
                 else:
                     self.set_node(outs, cls)
 
-        def initial_conditions(self, sim, hx, hy, *hz):
+        def initial_conditions(self, sim, *h):
             sim.rho[:] = 1.0
-            sim.vx[:] = u0
+            (sim.vx, sim.vy, sim.vz if dim == 3 else None)[fa][:] = fs * u0
 
-        def solid_map(self, hx, hy):
-            rim, blk, _, _ = self._parts(hx, hy)
+        def solid_map(self, *h):
+            rim, blk = self._parts(*h)[:2]
             return rim | blk
 
-        def load_active_node_map(self, hx, hy, *hz):
-            solid = self.solid_map(hx, hy)
+        def load_active_node_map(self, *h):
+            solid = self.solid_map(*h)
             if wall == 'NTHalfBBWall' and not halfbb_solid:
                 # half-way bounce-back nodes next to the fluid are wet nodes: count them as fluid, so that the nodes their
                 # even in-place step stores into (the layer behind them) own a slot
@@ -105,7 +126,7 @@ def make_sim(dim, wall='NTFullBBWall', inlet=None, outlet=None, slip=False, forc
         def __init__(self, config):
             super(ChannelSim, self).__init__(config)
             if force is not None:
-                self.add_body_force(tuple(force))
+                self.add_body_force(tuple(force) if frame is None else tuple(unit(fa, fs * float(force[0]))))
 
     return ChannelSim
 
@@ -141,6 +162,8 @@ def cavity_sim(dim):
 # ---- the case table -------------------------------------------------------------------------------------------------------
 SIZE = {2: dict(lat_nx=40, lat_ny=14), 3: dict(lat_nx=40, lat_ny=12, lat_nz=6, periodic_z=True)}
 GRID = {2: 'D2Q9', 3: 'D3Q19'}
+# the frames (tests/_faces.py) beyond the x frame that the table adds: flow along y / z, both senses, walls on each other axis
+OTHER_FRAMES = {2: [(1, 1), (1, -1)], 3: [(a, s, b) for a in (1, 2) for s in (1, -1) for b in range(3) if b != a]}
 ALL_PM = [(p, m) for p in ('single', 'double') for m in ('bgk', 'mrt')]
 
 
@@ -223,6 +246,45 @@ def _build_cases():
         for pattern in ('AA', 'AB'):
             add('regions-' + tag(dim, 'double', 'bgk', pattern), dict(dim=dim, **types), dim,
                 _cfg(dim, 'double', 'bgk', pattern, subdomains=2, conn_axis='y' if dim == 2 else 'z'), pattern, 1)
+    # other frames: the flow along y and along z, both senses, the walls on each remaining axis -- the outflow look-ups
+    # one / two nodes upstream, the in-place half-way store and the slip reflection then cross rows and planes
+    for dim in (2, 3):
+        for frame in OTHER_FRAMES[dim]:
+            fa, fs, fb = frame_axes(dim, frame)
+            ftag = '%s%s' % ('+' if fs > 0 else '-', 'xyz'[fa]) + ('_walls_%s' % 'xyz'[fb] if dim == 3 else '')
+
+            def ftagged(precision, model, pattern):
+                return '%s@%s' % (tag(dim, precision, model, pattern), ftag)
+
+            def fcfg(precision, model, pattern, periodic_flow=False, **kw):
+                ext = [0] * dim
+                ext[fa], ext[fb] = SIZE[dim]['lat_nx'], SIZE[dim]['lat_ny']
+                cfg = dict(grid=GRID[dim], visc=0.05, precision=precision, model=model, access_pattern=pattern,
+                           node_addressing='indirect', **kw)
+                if dim == 3:
+                    fc = 3 - fa - fb
+                    ext[fc] = SIZE[dim]['lat_nz']
+                    cfg['periodic_' + 'xyz'[fc]] = True
+                if periodic_flow:
+                    cfg['periodic_' + 'xyz'[fa]] = True
+                cfg.update(('lat_n' + 'xyz'[k], ext[k]) for k in range(dim))
+                return cfg
+
+            types = dict(wall='NTFullBBWall', inlet='NTRegularizedVelocity', outlet='NTZouHeDensity', frame=frame)
+            for precision in ('single', 'double'):
+                add('regvel_zhrho-' + ftagged(precision, 'bgk', 'AA'), dict(dim=dim, **types), dim,
+                    fcfg(precision, 'bgk', 'AA'), 'AA', 1)
+            types = dict(wall='NTFullBBWall', inlet='NTRegularizedVelocity', outlet='NTCopy', frame=frame)
+            add('copy-' + ftagged('single', 'bgk', 'AB'), dict(dim=dim, **types), dim, fcfg('single', 'bgk', 'AB'), 'AB', 2)
+            types = dict(wall='NTHalfBBWall', inlet='NTZouHeVelocity', outlet='NTYuOutflow', frame=frame)
+            add('yu_guard-' + ftagged('single', 'bgk', 'AB'), dict(dim=dim, block='outlet', **types), dim,
+                fcfg('single', 'bgk', 'AB'), 'AB', 2, dense=False)
+            types = dict(wall='NTHalfBBWall', inlet='NTZouHeVelocity', outlet='NTEquilibriumDensity', halfbb_solid=False,
+                         frame=frame)
+            add('halfbb_inplace-' + ftagged('single', 'bgk', 'AA'), dict(dim=dim, **types), dim,
+                fcfg('single', 'bgk', 'AA'), 'AA', 1)
+            add('slip-' + ftagged('single', 'mrt', 'AA'), dict(dim=dim, slip=True, force=(1e-5,), block_y0=3, frame=frame),
+                dim, fcfg('single', 'mrt', 'AA', periodic_flow=True, force_implementation='guo'), 'AA', 2)
     # level 0 in double: the two examples the single-precision tests use
     for model in ('bgk', 'mrt'):
         for pattern in ('AA', 'AB'):

@@ -14,6 +14,7 @@ from sailfish_amd import hipabi, sym
 from sailfish_amd.box import BoxSim, make_box_desc
 from tests import _geometry as geo
 from tests._oracle_box import OracleBox, synthetic_fields
+from tests._pair import run_pair as _run_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -27,40 +28,6 @@ def backend():
     class Opt(object):
         pass
     return HIPBackend(Opt(), 0)
-
-
-def _run_pair(backend, grid, size, steps, periodic, node_map_fn=None, u_scale=0.05, init='synthetic', **kw):
-    desc = make_box_desc(grid, size, **kw)
-    nmap = node_map_fn(desc) if node_map_fn else None
-    rho, v = synthetic_fields(size, grid.dim)
-    if init == 'rest':
-        rho = np.ones_like(rho)
-        v = [np.zeros_like(c) for c in v]
-    sims = []
-    for cls, args in ((BoxSim, (backend, desc)), (OracleBox, (desc,))):
-        s = cls(*args, periodic=periodic, node_map=nmap)
-        s.set_fields(rho, v)
-        s.initial_conditions()
-        s.run(steps, save_last=True)
-        sims.append(s)
-    g, o = sims
-    g_rho, g_v = g.fetch_fields()
-    f_g = g.real_view(g.get_dist())
-    f_o = o.real_view(o.current_dist())
-    wet = np.isfinite(o.real_view(o.rho)) if nmap is None else None
-    res = {'dist_exact': np.array_equal(f_g, f_o, equal_nan=True)}
-    r_g, r_o = g.real_view(g_rho), o.real_view(o.rho)
-    mask = np.isfinite(r_o)
-    assert np.array_equal(mask, np.isfinite(r_g))
-    res['rho_err'] = float(np.max(np.abs(r_g[mask] - r_o[mask]) / np.abs(r_o[mask])))
-    verr = 0.0
-    for d in range(grid.dim):
-        a, b = g.real_view(g_v[d])[mask], o.real_view(o.v[d])[mask]
-        verr = max(verr, float(np.max(np.abs(a - b))) / u_scale)
-    res['v_err'] = verr
-    fm = np.isfinite(f_o)
-    res['dist_err'] = float(np.max(np.abs(f_g[fm] - f_o[fm])))
-    return res
 
 
 BOX = [(sym.D2Q9, (70, 11)), (sym.D3Q19, (70, 6, 5))]

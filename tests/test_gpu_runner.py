@@ -702,6 +702,57 @@ def test_time_dependent_boundary_values(pattern, dim, nsub, axis):
     assert all(r._time_dependent() for r in ctrl.runners)
 
 
+def _pulsating_face(dim=3):
+    """A duct along z, periodic along x and y, whose inlet covers the whole face z = 0 with a density that depends on time
+    AND on both in-plane coordinates: one entry of the parameter table per node of the face, all in one update range."""
+    import sympy
+    from sailfish_amd import node_type as nt
+    from sailfish_amd import sym
+    from sailfish_amd.lb_single import LBFluidSim
+    from sailfish_amd.subdomain import Subdomain3D
+    S = sym.S
+    amp, om = 0.004, 2 * np.pi / 7.0
+
+    class Duct(Subdomain3D):
+        def boundary_conditions(self, hx, hy, hz):
+            self.set_node(hz == 0, nt.NTEquilibriumDensity(nt.DynamicValue(
+                1.0 + amp * sympy.sin(S.time * om) * (1 + 0.01 * S.gx) * (1 - 0.02 * S.gy))))
+            self.set_node(hz == self.gz - 1, nt.NTEquilibriumDensity(1.0))
+
+        def initial_conditions(self, sim, hx, hy, hz):
+            sim.rho[:] = 1.0
+
+    class DuctSim(LBFluidSim):
+        subdomain = Duct
+    return DuctSim
+
+
+@pytest.mark.parametrize('precision', ['single', 'double'])
+@pytest.mark.parametrize('pattern', ['AB', 'AA'])
+@pytest.mark.parametrize('nx,ny', [(13, 15), (14, 14), (13, 18)])
+def test_long_parameter_updates(nx, ny, pattern, precision):
+    """slf_module_update_node_params on both sides of its 256 entries (slf_api.hip: PARAM_UPDATE_MAX): up to there the
+    values travel as kernel arguments, beyond it through a ring of four pinned staging buffers.  Faces of 255, 256 and
+    300 nodes (the ghost nodes around the periodic face have entries too), eleven steps -- every staging buffer is used at
+    least twice, with other values --, bit-identical to the oracle twin, which takes the same values."""
+    n = (nx + 2) * (ny + 2)
+    assert n in (255, 256, 300)
+    cfg = dict(lat_nx=nx, lat_ny=ny, lat_nz=8, visc=0.08, access_pattern=pattern, precision=precision, periodic_x=True,
+               periodic_y=True)
+    ctrl, exact = check_against_oracle(_pulsating_face(), None, 3, cfg, 11, 0.01)
+    assert exact
+    r, = ctrl.runners
+    assert r._time_dependent()
+    enc = r._subdomain._encoder
+    updates = enc.dynamic_updates(0)
+    assert [len(values) for first, values in updates] == [n]
+    # the values differ from node to node and from step to step
+    assert len(np.unique(enc.dynamic_updates(3)[0][1])) > n // 2
+    assert all(not np.array_equal(enc.dynamic_updates(it)[0][1], enc.dynamic_updates(it + 4)[0][1]) for it in range(1, 7))
+    assert np.nanmax(np.abs(merged_gpu(ctrl, 'v2'))) > 1e-5
+    r.release()
+
+
 def test_womersley_flow_follows_the_analytical_profile():
     """examples/womersley.py: a pipe driven by dP(t) = dP0 sin(omega t) through time-dependent equilibrium-density
     nodes.  After seven periods (the start-up transient decays with the slowest viscous mode, nu 2.405^2 / R^2 = 1 / 4400

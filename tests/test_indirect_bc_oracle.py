@@ -74,10 +74,14 @@ def test_outflow_nodes_behind_the_block_have_upstream_neighbours_without_a_slot(
     outflow = getattr(S.nt, case['sim']['outlet']).id
     pos = np.argwhere(vis == outflow) + 1                          # real node -> ghost-including index
     assert len(pos) > 0
-    z = (lambda p: p[0]) if case['dim'] == 3 else (lambda p: 0)
-    s1 = np.array([addr[z(p), p[-2], p[-1] - 1] for p in pos])
-    s2 = np.array([addr[z(p), p[-2], p[-1] - 2] for p in pos])
-    own = np.array([addr[z(p), p[-2], p[-1]] for p in pos])
+    # one / two nodes upstream = along the outlet's inward normal, in the case's frame (array axes are [z,] y, x)
+    fa, fs, _ = S.frame_axes(case['dim'], case['sim'].get('frame'))
+    up = np.zeros(3, dtype=np.int64)
+    up[2 - fa] = -fs
+    full = [np.array([p[0] if case['dim'] == 3 else 0, p[-2], p[-1]]) for p in pos]
+    s1 = np.array([addr[tuple(p + up)] for p in full])
+    s2 = np.array([addr[tuple(p + 2 * up)] for p in full])
+    own = np.array([addr[tuple(p)] for p in full])
     assert np.all(own != hipabi.SLF_INVALID_NODE)
     missing = (s1 == hipabi.SLF_INVALID_NODE) | (s2 == hipabi.SLF_INVALID_NODE)
     assert missing.any() and not missing.all()

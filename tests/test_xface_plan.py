@@ -118,3 +118,19 @@ def test_signals_and_waits_of_the_peer_schedule_balance(nz, wrap, nchunks):
         for pos, c in enumerate(p.order):
             consumed += by_pos.get(pos, 0)
             assert signalled[consumed - 1] == max(need[c2] for c2 in p.order[:pos + 1])     # exactly up to what is needed so far
+
+
+def test_outflow_nodes_keep_the_x_faces_in_the_ghost_columns():
+    """NTCopy / NTYuOutflow nodes read the populations of the nodes one / two steps upstream from the input array
+    (slf_sweep.h: fixMissingDistributions).  On a y or z face next to a connected x face those include populations that
+    entered through a face buffer and never reach the array (found by tests/test_gpu_faces.py: a Yu outlet on a y face,
+    two subdomains cut along x, drifted from the oracle by 2e-6 in 40 steps): such modules take no x-face buffers."""
+    from sailfish_amd import sym, xface
+    from sailfish_amd.box import make_box_desc
+    from tests import _geometry as geo
+    kw = dict(precision='single', access_pattern='AB', visc=0.05, fluid_only=False, nt_bits=geo.NT_BITS)
+    assert xface.supported(sym.D3Q19, make_box_desc(sym.D3Q19, (20, 8, 6), access_pattern='AB'))
+    assert xface.supported(sym.D3Q19, make_box_desc(sym.D3Q19, (20, 8, 6), type_kind=geo.TYPE_KIND, **kw))
+    assert xface.supported(sym.D3Q19, make_box_desc(sym.D3Q19, (20, 8, 6), type_kind=geo.TYPE_KIND_INPLACE, **kw))
+    assert not xface.supported(sym.D3Q19, make_box_desc(sym.D3Q19, (20, 8, 6), type_kind=geo.TYPE_KIND_OUTFLOW, **kw))
+    assert not xface.supported(sym.D3Q19, make_box_desc(sym.D3Q19, (20, 8, 6), type_kind=geo.TYPE_KIND[:3] + [geo.h.SLF_NK_COPY], **kw))
