@@ -44,7 +44,7 @@ enum { SLF_AB = 0, SLF_AA = 1 };
  * compressible (rho0 = rho), --incompressible (rho0 = 1), --minimize_roundoff (the arrays hold f_i - w_i, the density
  * variable is rho - 1, rho0 = rho; BGK with fluid and bounce-back nodes only, as in the reference "BGK-like models") */
 enum { SLF_DENSITY_COMPRESSIBLE = 0, SLF_DENSITY_INCOMPRESSIBLE = 1, SLF_DENSITY_ROUNDOFF = 2 };
-enum { SLF_SIM_LBM = 0, SLF_SIM_SHAN_CHEN_BINARY = 1, SLF_SIM_SHAN_CHEN_SINGLE = 2 };
+enum { SLF_SIM_LBM = 0, SLF_SIM_SHAN_CHEN_BINARY = 1, SLF_SIM_SHAN_CHEN_SINGLE = 2, SLF_SIM_FREE_ENERGY = 3 };
 
 /* Node addressing (reference subdomain_runner.py:829-878, kernel_common.mako:140-167).  INDIRECT: the
  * distribution arrays hold the *active* nodes only (dist_stride >= number of active nodes); a dense
@@ -161,6 +161,19 @@ typedef struct slf_module_desc {
   int32_t regularized;
   int32_t subgrid;
   double smagorinsky_const;
+  /* simtype = SLF_SIM_FREE_ENERGY (reference lb_binary.py:139-372): the free-energy binary fluid, BGK.  Lattice 0 carries
+   * rho, lattice 1 the order parameter phi; tau_phi relaxes lattice 1, lattice 0 relaxes with tau_b + (phi + 1)
+   * (tau_a - tau_b) / 2 clamped to [-1, 1] in phi (tau and visc are not read).  Gamma, kappa, A: --Gamma, --kappa, --A.
+   * Full-way bounce-back walls take phi of the fluid node bc_wall_grad_order (1 | 2) nodes along their normal minus
+   * bc_wall_grad_order * bc_wall_grad_phase.  fe_zero_grad_rim[axis]: 1 = gradient and Laplacian of phi are zero on the
+   * first real layer of the axis, 2 = on the last one, 0 = neither (the reference's zero_gradient_at_boundaries,
+   * mako_utils.mako:168-197: the host decides from the periodicity and the connections of the subdomain).
+   * Fluid, ghost, unused, propagation-only and full-way bounce-back nodes; direct addressing; no body force. */
+  double fe_Gamma, fe_kappa, fe_A;
+  double fe_tau_a, fe_tau_b;
+  double bc_wall_grad_phase;
+  int32_t bc_wall_grad_order;
+  int32_t fe_zero_grad_rim[3];
   /* model = SLF_ELBM (reference lb_single.py:31-69): f_i += alpha beta (feq_i - f_i) with beta = 1 / (2 visc / cs^2 + 1)
    * and alpha from the entropy equality H(f + alpha (feq - f)) = H(f): 2 where max_i |feq_i / f_i - 1| < 1e-6, the
    * series of PRL 97, 010201 below 0.01, Newton's method otherwise.  entropic_equilibrium (--entropic_equilibrium): the
@@ -420,6 +433,15 @@ int slf_module_classify_rows(slf_module* m, const void* map_dptr, slf_stream* st
  * Single-component Shan-Chen modules (SLF_SIM_SHAN_CHEN_SINGLE) keep the single-fluid kernel names; their
  * "CollideAndPropagate" adds the pseudopotential force, and "PrepareMacroFields"(map, dist, rho, options)
  * computes the density field it reads (reference templates/models/lb_single_fluid.mako:129-229).
+ * Free-energy modules (simtype = SLF_SIM_FREE_ENERGY) provide, with the reference's argument lists
+ * (templates/models/lb_binary_fluid.mako:130-369, lb_binary.py:295-308):
+ * "FreeEnergyPrepareMacroFields"(map, dist1, dist2, rho, phi, options): phi of every node (wetting walls included),
+ * "FreeEnergyCollideAndPropagateFluid"(map, dist_in, dist_out, rho, phi, vx, vy[, vz], phi_laplacian, options): lattice 0;
+ * stores the velocity and the Laplacian of phi on every wet node, rho where options has bit 0,
+ * "FreeEnergyCollideAndPropagateOrderParam"(map, dist_in, dist_out, phi, vx, vy[, vz], phi_laplacian, options): lattice 1,
+ * with the velocity and the Laplacian the fluid kernel of the same step stored -- launch them in this order -- and
+ * the two-lattice "SetInitialConditions" above, which reads phi at the neighbours of every real node: the caller fills
+ * phi's ghost layer first.
  * Launch-bound 2-D subdomains (no counterpart in the reference, which launches CollideAndPropagate once per step,
  * subdomain_runner.py:960-974): "CollideAndPropagateResident"(map, src_a, src_b, dst_a, dst_b, options, steps, tile_x,
  * tile_y, halo), format "PPPPPiiiii", needs_iteration = 1 (the iteration of its FIRST step) performs `steps` time

@@ -207,6 +207,23 @@ class LocalGroup(object):
             r._calc_stream = r._bnd_stream = shared
         self.single_calc_stream = True
 
+    def _startup_fields(self):
+        """Models whose initial conditions read a field at neighbouring nodes (NNSubdomainRunner._gpu_initial_conditions):
+        now that every runner has its fields on its device, their local periodic images and one exchange of the fields
+        between the runners, then every runner's SetInitialConditions."""
+        from sailfish_amd.stepqueue import DirectQueue
+        rs = self.runners
+        q = DirectQueue(rs[0].backend)
+        for r in rs:
+            r._set_step_state(0)
+        for r in rs:
+            r._program_startup_fields(q, group=self)
+        self._program_copies(q, 0, 'macro')
+        for r in rs:
+            r._program_macro_back(q, 0)
+        for r in rs:
+            r._finish_startup()
+
     def step(self, reqs):
         from sailfish_amd.stepqueue import StepPlans
         rs = self.runners
@@ -235,6 +252,8 @@ class LocalGroup(object):
             for r in runners:
                 r.prepare()
         self._share_xface_buffers()
+        if any(getattr(r, '_startup_pending', False) for r in runners):
+            self._startup_fields()
         cfg = runners[0].config
         t_prev, it_prev = time.time(), runners[0]._sim.iteration
         t0, it0 = t_prev, it_prev

@@ -58,7 +58,11 @@ enum KernelKind {
   KK_SC_INIT,
   KK_SCS_MACRO,
   KK_SCS_SWEEP,
-  KK_RESIDENT,                // several steps inside one launch (slf_resident.hip)
+  KK_FE_MACRO,                // free-energy binary fluid (slf_fe.hip); the three in the order of slf::fe_kernel_index()
+  KK_FE_FLUID,
+  KK_FE_ORDER,
+  KK_FE_INIT,
+  KK_RESIDENT,               // several steps inside one launch (slf_resident.hip)
 };
 
 }  // namespace
@@ -84,6 +88,7 @@ struct slf_module {
   slf::Geometry geo;
   slf::Physics phys;
   slf::ShanChen sc;
+  slf::FreeEnergy fe;
   int access_pattern;
   int block_x;
   void* node_params;  // device copy, in the module's precision
@@ -982,7 +987,8 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
   }
   if (d->node_addressing == SLF_ADDR_INDIRECT) {
     if (d->fluid_only) { delete m; return fail(SLF_ERR_INVALID, "indirect addressing needs the node map (fluid_only = 0)"); }
-    if (d->simtype != SLF_SIM_LBM && d->simtype != SLF_SIM_SHAN_CHEN_BINARY && d->simtype != SLF_SIM_SHAN_CHEN_SINGLE) {
+    if (d->simtype != SLF_SIM_LBM && d->simtype != SLF_SIM_SHAN_CHEN_BINARY && d->simtype != SLF_SIM_SHAN_CHEN_SINGLE &&
+        d->simtype != SLF_SIM_FREE_ENERGY) {      // (free energy: refused below, with its own message)
       delete m;
       return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: unknown simtype");
     }
@@ -1159,6 +1165,41 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
         delete m;
         return fail(SLF_ERR_UNSUPPORTED, "Shan-Chen modules support fluid and full-way bounce-back nodes only");
       }
+    }
+  }
+  m->fe = slf::FreeEnergy{};
+  if (d->simtype == SLF_SIM_FREE_ENERGY) {
+    // what slf_fe.hip implements of the reference's model (lb_binary.py:139-372); everything else is named and refused
+    slf::FreeEnergy& fe = m->fe;
+    fe.enabled = 1;
+    fe.Gamma = d->fe_Gamma; fe.kappa = d->fe_kappa; fe.A = d->fe_A;
+    fe.tau_a = d->fe_tau_a; fe.tau_b = d->fe_tau_b; fe.tau_phi = d->tau_phi;
+    fe.wall_phase = d->bc_wall_grad_phase;
+    fe.wall_order = d->bc_wall_grad_order;
+    for (int i = 0; i < 3; i++) fe.rim[i] = d->fe_zero_grad_rim[i];
+    const char* why = nullptr;
+    if (d->model == SLF_MRT) why = "free energy: --model=mrt (the FE-MRT collision, relaxation.mako:15-54) is not implemented; BGK only";
+    else if (d->model != SLF_BGK) why = "free energy: the BGK collision only";
+    else if (d->has_force || d->accel1[0] != 0.0 || d->accel1[1] != 0.0 || d->accel1[2] != 0.0)
+      why = "free energy: body forces (free_energy_external_force, use_force_for_equilibrium) are not implemented";
+    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "free energy: indirect addressing is not implemented; direct addressing only";
+    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "free energy: --incompressible / --minimize_roundoff are not implemented";
+    else if (!(d->fe_tau_a > 0.5) || !(d->fe_tau_b > 0.5) || !(d->tau_phi > 0.5)) why = "free energy: tau_a, tau_b and tau_phi must be > 0.5";
+    else if (d->bc_wall_grad_order != 1 && d->bc_wall_grad_order != 2) why = "free energy: bc_wall_grad_order must be 1 or 2";
+    for (int i = 0; !why && i < 3; i++) {
+      if (d->fe_zero_grad_rim[i] < 0 || d->fe_zero_grad_rim[i] > 2) why = "free energy: fe_zero_grad_rim entries are 0, 1 (low rim) or 2 (high rim)";
+    }
+    for (int i = 0; !why && i < d->n_types; i++) {
+      const int k = d->type_kind[i];
+      if (k == SLF_NK_HALF_BB) why = "free energy: NTHalfBBWall wetting walls are not implemented; full-way bounce-back walls only";
+      else if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
+        why = "free energy: fluid and full-way bounce-back (NTFullBBWall) nodes only; NTGuoDensity and the other boundary "
+              "conditions are not implemented";
+    }
+    // (--regularized / --subgrid were refused above: single-fluid modules only)
+    if (why) {
+      delete m;
+      return fail(SLF_ERR_UNSUPPORTED, why);
     }
   }
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
@@ -1375,7 +1416,7 @@ static int check_xface_buffers(const slf_module* m, void* send_low, void* send_h
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
   if (send_low || send_high || recv_low || recv_high) {
     const slf::Geometry& g = m->geo;
-    if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || !(g.variant & 8))
+    if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || m->fe.enabled || !(g.variant & 8))
       return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: D3Q19 single-fluid modules with direct addressing (whole-row kernels) only");
     if (g.wrap[0]) return fail(SLF_ERR_INVALID, "x-face buffers make no sense with x wrapped inside the sweep");
     if (g.lat_nx - 2 > 1024) return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: rows of at most 1024 nodes");
@@ -1501,7 +1542,7 @@ int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, 
 // ---- force on bodies by momentum exchange (slf_force.hip) --------------------------------------------------------
 static int check_force_call(const slf_module* m, int n_objects, uint32_t max_links, const char* what) {
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
-  if (m->sc.enabled)
+  if (m->sc.enabled || m->fe.enabled)
     return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": single-fluid modules only (the force is read off lattice 0 alone)");
   if (n_objects < 0 || n_objects > 65535) return fail(SLF_ERR_INVALID, std::string(what) + ": 0 .. 65535 objects per call");
   if (max_links > 0x7FFFFFFFu) return fail(SLF_ERR_INVALID, std::string(what) + ": fewer than 2^31 links");
@@ -1536,7 +1577,7 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   bool sc_local_velocity = false;
   if (!strcmp(name, "CollideAndPropagate")) kk = (m->sc.enabled == 2) ? KK_SCS_SWEEP : KK_COLLIDE_AND_PROPAGATE;
   else if (!strcmp(name, "PrepareMacroFields")) kk = KK_SCS_MACRO;
-  else if (!strcmp(name, "SetInitialConditions")) kk = (m->sc.enabled == 1) ? KK_SC_INIT : KK_SET_INITIAL_CONDITIONS;
+  else if (!strcmp(name, "SetInitialConditions")) kk = m->fe.enabled ? KK_FE_INIT : ((m->sc.enabled == 1) ? KK_SC_INIT : KK_SET_INITIAL_CONDITIONS);
   else if (!strcmp(name, "ShanChenPrepareMacroFields")) kk = KK_SC_MACRO;
   else if (!strcmp(name, "ShanChenCollideAndPropagate0")) kk = KK_SC_SWEEP0;
   else if (!strcmp(name, "ShanChenCollideAndPropagate1")) kk = KK_SC_SWEEP1;
@@ -1556,12 +1597,13 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   else if (!strcmp(name, "DistributeContinuousMacroData")) kk = KK_DISTRIBUTE_MACRO_FACE;
   else if (!strcmp(name, "ComputeMacroFields")) kk = KK_COMPUTE_MACRO;
   else if (!strcmp(name, "CollideAndPropagateResident")) kk = KK_RESIDENT;
+  else if (slf::fe_kernel_index(name) >= 0) kk = (KernelKind)(KK_FE_MACRO + slf::fe_kernel_index(name));   // FreeEnergy...
   else return fail(SLF_ERR_NOT_FOUND, std::string("unknown kernel: ") + name);
   if (kk == KK_RESIDENT) {
     // what the resident kernel serves (slf_resident.hip): 2-D single-fluid modules, direct addressing, the standard
     // density formulation, node kinds whose code touches nothing but the node's own populations
     const slf::Geometry& g = m->geo;
-    if (g.dim != 2 || m->sc.enabled || g.indirect || m->phys.incompressible == SLF_DENSITY_ROUNDOFF || m->phys.regularized ||
+    if (g.dim != 2 || m->sc.enabled || m->fe.enabled || g.indirect || m->phys.incompressible == SLF_DENSITY_ROUNDOFF || m->phys.regularized ||
         m->phys.subgrid || m->sel.model == SLF_ELBM)
       return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: 2-D single-fluid modules with direct addressing and the "
                                        "standard density formulation only");
@@ -1580,6 +1622,10 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
     return fail(SLF_ERR_NOT_FOUND, "Shan-Chen kernels only exist in modules built with simtype = SLF_SIM_SHAN_CHEN_BINARY");
   if ((kk == KK_COLLIDE_AND_PROPAGATE || kk == KK_COMPUTE_MACRO) && m->sc.enabled == 1)
     return fail(SLF_ERR_NOT_FOUND, "single-fluid kernels do not exist in a Shan-Chen module");
+  if ((kk == KK_FE_MACRO || kk == KK_FE_FLUID || kk == KK_FE_ORDER) && !m->fe.enabled)
+    return fail(SLF_ERR_NOT_FOUND, "FreeEnergy... kernels only exist in modules built with simtype = SLF_SIM_FREE_ENERGY");
+  if ((kk == KK_COLLIDE_AND_PROPAGATE || kk == KK_COMPUTE_MACRO) && m->fe.enabled)
+    return fail(SLF_ERR_NOT_FOUND, "single-fluid kernels do not exist in a free-energy module");
   if ((kk == KK_PBC || kk == KK_PBC_SWAP) && m->geo.indirect)
     return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: periodic boundaries are wrapped inside the sweep "
                                      "(periodic_fused), there are no ghost-layer PBC kernels");
@@ -1658,6 +1704,10 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
     case KK_SC_FUSED: want_p = 7 + dim; want_i = 1; break;        // map, dist0 in, out, dist1 in, out, rho, phi, v.., options
     case KK_SC_INIT: want_p = 5 + dim; want_i = 0; break;         // map, dist1, dist2, v.., rho, phi
     case KK_SCS_MACRO: want_p = 3; want_i = 1; break;             // map, dist, rho, options
+    case KK_FE_MACRO: want_p = 5; want_i = 1; break;              // map, dist1, dist2, rho, phi, options
+    case KK_FE_FLUID: want_p = 6 + dim; want_i = 1; break;        // map, dist in, out, rho, phi, v.., phi_laplacian, options
+    case KK_FE_ORDER: want_p = 5 + dim; want_i = 1; break;        // map, dist in, out, phi, v.., phi_laplacian, options
+    case KK_FE_INIT: want_p = 5 + dim; want_i = 0; break;         // map, dist1, dist2, v.., rho, phi
     case KK_SCS_SWEEP: want_p = 4 + dim; want_i = 1; break;       // as CollideAndPropagate
     case KK_RESIDENT: want_p = 5; want_i = 5; break;              // map, src a, src b, dst a, dst b, options, steps, tile x, tile y, halo
   }
@@ -1794,7 +1844,7 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   const int prefetch = knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch());
   const int xcd_log2 = knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2());
   const int march = knob("SLF_PAIR_MARCH", slf::pair_default_march());
-  if (m->sc.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
+  if (m->sc.enabled || m->fe.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
   slf::SweepArgs a = {};
   pair_args(k, a);
@@ -1958,6 +2008,37 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       int y0, y1, z0, z1;
       if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
       e = slf::launch_scs_sweep(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, m->block_x, s);
+      break;
+    }
+    case KK_FE_MACRO:
+    case KK_FE_FLUID:
+    case KK_FE_ORDER: {
+      // argument lists of the reference (lb_binary.py:295-308)
+      slf::SweepArgs a = {};
+      a.map = (const void*)k->ptrs[0];
+      a.dist_in = (void*)k->ptrs[1];
+      a.dist_out = (void*)k->ptrs[2];
+      int next = 3;
+      if (k->kind != KK_FE_ORDER) a.rho = (void*)k->ptrs[next++];
+      a.phi = (void*)k->ptrs[next++];
+      if (k->kind != KK_FE_MACRO) {
+        for (int d = 0; d < g.dim; d++) a.v[d] = (void*)k->ptrs[next++];
+        a.lap = (void*)k->ptrs[next++];
+      }
+      if (int rc = sweep_common(k, a)) return rc;
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
+      if (k->kind == KK_FE_MACRO) e = slf::launch_fe_macro(m->sel, prop, g, m->fe, a, y0, y1, z0, z1, s);
+      else e = slf::launch_fe_sweep(m->sel, k->kind == KK_FE_FLUID ? 0 : 1, prop, g, m->fe, a, y0, y1, z0, z1, m->block_x, s);
+      break;
+    }
+    case KK_FE_INIT: {
+      // (map, dist1, dist2, vx, vy[, vz], rho, phi)  -- reference lb_binary.py:107-127
+      const void* v[3] = {(const void*)k->ptrs[3], (const void*)k->ptrs[4], g.dim == 3 ? (const void*)k->ptrs[5] : nullptr};
+      e = slf::launch_fe_init(m->sel, g, m->fe, (void*)k->ptrs[1], (void*)k->ptrs[2], (const void*)k->ptrs[3 + g.dim],
+                              (const void*)k->ptrs[4 + g.dim], v, m->sel.general ? (const void*)k->ptrs[0] : nullptr, s);
       break;
     }
     case KK_SC_INIT: {

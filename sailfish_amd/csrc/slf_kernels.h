@@ -77,6 +77,17 @@ struct ShanChen {
   double accel1[3]; // body-force acceleration on lattice 1 (Physics::accel acts on lattice 0)
 };
 
+// Free-energy binary fluid (slf_fe.hip; reference lb_binary.py:139-372)
+struct FreeEnergy {
+  int enabled;
+  double Gamma, kappa, A;      // mobility, interface and bulk free-energy parameters
+  double tau_a, tau_b;         // relaxation times of the two components (tau0 interpolates with phi)
+  double tau_phi;              // relaxation time of the order-parameter lattice
+  double wall_phase;           // --bc_wall_grad_phase
+  int wall_order;              // --bc_wall_grad_order: 1 | 2
+  int rim[3];                  // per axis: 1 / 2 = zero gradient and Laplacian on the low / high rim layer
+};
+
 struct RowClasses;
 struct SlotTable;
 
@@ -111,6 +122,7 @@ struct SweepArgs {
   void* msend[2];
   const void* mrecv[2];
   void* alpha;         // entropic modules: the alpha field (dense, like rho) or NULL
+  void* lap;           // free-energy modules: the Laplacian of phi (dense, like rho), else unused
 };
 
 // What slf_module_classify_rows() found in a node map, per 64-node x-segment (= one wavefront of a whole-row
@@ -193,6 +205,18 @@ hipError_t launch_scs_sweep(const KernelSelector& sel, Prop prop, const Geometry
                             hipStream_t s);
 hipError_t launch_sc_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist1, void* dist2,
                           const void* rho, const void* phi, const void* const v[3], const void* nodes, hipStream_t s);
+
+// ---- free-energy binary fluid (slf_fe.hip) ----
+// macro pass: a.dist_out = lattice 1 (read), writes a.phi (wetting walls: phi of the helper node minus the constant)
+hipError_t launch_fe_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const FreeEnergy& fe, const SweepArgs& a,
+                           int y0, int y1, int z0, int z1, hipStream_t s);
+// collide-and-stream of the fluid lattice (which = 0: reads phi, writes v and a.lap) or of the order parameter (1: reads them)
+hipError_t launch_fe_sweep(const KernelSelector& sel, int which, Prop prop, const Geometry& g, const FreeEnergy& fe,
+                           const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_fe_init(const KernelSelector& sel, const Geometry& g, const FreeEnergy& fe, void* dist1, void* dist2,
+                          const void* rho, const void* phi, const void* const v[3], const void* map, hipStream_t s);
+// 0 / 1 / 2: FreeEnergyPrepareMacroFields / ...CollideAndPropagateFluid / ...CollideAndPropagateOrderParam, -1: none of them
+int fe_kernel_index(const char* name);
 
 // ---- several steps inside one launch (slf_resident.hip): 2-D lattices ----
 // src / dst: the raw distribution arrays ([0] = the array of the in-place pattern / copy A of the two-copy pattern, [1] =

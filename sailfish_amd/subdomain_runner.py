@@ -29,7 +29,7 @@ from sailfish_amd import halo, hipabi, io, subdomain_connection, util, xface
 from sailfish_amd import node_type as nt
 from sailfish_amd.lb_base import LBMixIn, LBSim
 from sailfish_amd.profile import TimeProfile
-from sailfish_amd.stepqueue import StepPlans
+from sailfish_amd.stepqueue import DirectQueue, StepPlans
 
 
 class GPUBuffer(object):
@@ -206,6 +206,8 @@ class SubdomainRunner(object):
         kw['periodic_local'] = [int(x) for x in local] + [0] * (3 - self.dim)
         kw['periodic_fused'] = fused + [0] * (3 - self.dim)
         self._fused = fused
+        if hasattr(self._sim, 'fill_subdomain_desc'):       # what depends on this subdomain's faces and node map
+            self._sim.fill_subdomain_desc(self, kw)
         # fast path: every real node is a plain fluid node -> the sweep does not read the node map (ghost
         # nodes behind an unconnected, non-periodic face are never pulled from by a fluid-only interior
         # in any way that matters: what they hold is what a wall of excluded nodes would hold)
@@ -1008,7 +1010,7 @@ class SubdomainRunner(object):
         self._init_halo()
         self._prepare_compute_kernels()
         self._init_step_program()
-        self._sim.initial_conditions(self)
+        self._gpu_initial_conditions()
         self.backend.set_iteration(0)
         if self._output is not None:
             self._output.set_fluid_map(self._subdomain.fluid_map())
@@ -1026,6 +1028,10 @@ class SubdomainRunner(object):
                 c.before_main_loop(self._sim, self)
         self.backend.sync_stream(self._calc_stream)
         self.num_fluid_nodes = self._subdomain.num_fluid_nodes
+
+    def _gpu_initial_conditions(self):
+        """The distributions from the macroscopic fields the subdomain's initial_conditions() wrote."""
+        self._sim.initial_conditions(self)
 
     def need_quit(self):
         cfg = self.config
@@ -1348,6 +1354,48 @@ class NNSubdomainRunner(SubdomainRunner):
         """Stepped by a group that runs every sweep of its subdomains on ONE stream, planes shared with the neighbours: the
         order of that stream is all the order the planes need (controller.LocalGroup._serialise_sweeps)."""
         return self._nnx is not None and group is not None and getattr(group, 'single_calc_stream', False) and self._nnx.shared
+
+    # ---- start-up of models whose initial conditions read a field at neighbouring nodes (free energy: the Laplacian and
+    # the gradient of the host's phi) -- reference NNSubdomainRunner._gpu_initial_conditions, subdomain_runner.py:2079-2100
+    _startup_pending = False
+
+    def _startup_needs_fields(self):
+        return bool(getattr(self._sim, 'initial_conditions_need_nn', False))
+
+    def _gpu_initial_conditions(self):
+        """Fills the ghost layer of the fields the initial conditions read -- local periodic images, then one exchange of
+        the fields with the neighbours -- in front of SetInitialConditions.  Shan-Chen models start from every node's own
+        values: nothing is exchanged for them.  Subdomains stepped by a same-process group can only exchange once every one
+        of them has its fields on the device: the group finishes the start-up after the last prepare()
+        (controller.LocalGroup._startup_fields; before_main_loop() hooks of such runners see the arrays before that)."""
+        if not self._startup_needs_fields():
+            return SubdomainRunner._gpu_initial_conditions(self)
+        from sailfish_amd.connector import LocalConnector
+        if self._macro_links and isinstance(self._connector, LocalConnector):
+            self._startup_pending = True
+            return
+        q = DirectQueue(self.backend)
+        self._set_step_state(0)
+        self._program_startup_fields(q)
+        self._program_macro_back(q, 0)
+        self._finish_startup()
+
+    def _program_startup_fields(self, q, group=None):
+        """What _program_macro() does behind the macro pass, for the fields as the host wrote them (parity 0)."""
+        sk, ev = self._calc_stream, self._pev[0]
+        for axis in self._pbc_axes:
+            for k in self._pbc_kernels.macro[1][axis]:
+                q.launch(k, None, sk)
+        if self._macro_links:
+            q.record(ev['macro'], sk)
+            self._program_pack(q, 0, ev['macro'], group, kind='macro')
+
+    def _finish_startup(self):
+        if not getattr(self.config, 'restore_from', '') or not self._startup_pending:
+            SubdomainRunner._gpu_initial_conditions(self)       # (a pending start-up comes after the checkpoint was read)
+        self._startup_pending = False
+        self._step_parity = None
+        self.backend.sync_stream(*self._all_streams())
 
     def _enqueue_plain_step(self, it):
         b = self.backend
