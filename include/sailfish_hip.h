@@ -44,7 +44,8 @@ enum { SLF_AB = 0, SLF_AA = 1 };
  * compressible (rho0 = rho), --incompressible (rho0 = 1), --minimize_roundoff (the arrays hold f_i - w_i, the density
  * variable is rho - 1, rho0 = rho; BGK with fluid and bounce-back nodes only, as in the reference "BGK-like models") */
 enum { SLF_DENSITY_COMPRESSIBLE = 0, SLF_DENSITY_INCOMPRESSIBLE = 1, SLF_DENSITY_ROUNDOFF = 2 };
-enum { SLF_SIM_LBM = 0, SLF_SIM_SHAN_CHEN_BINARY = 1, SLF_SIM_SHAN_CHEN_SINGLE = 2, SLF_SIM_FREE_ENERGY = 3 };
+enum { SLF_SIM_LBM = 0, SLF_SIM_SHAN_CHEN_BINARY = 1, SLF_SIM_SHAN_CHEN_SINGLE = 2, SLF_SIM_FREE_ENERGY = 3,
+       SLF_SIM_SHAN_CHEN_TERNARY = 4 };
 
 /* Node addressing (reference subdomain_runner.py:829-878, kernel_common.mako:140-167).  INDIRECT: the
  * distribution arrays hold the *active* nodes only (dist_stride >= number of active nodes); a dense
@@ -140,7 +141,8 @@ typedef struct slf_module_desc {
                                   neighbour there (SubdomainSpec.enable_local_periodicity, subdomain.py:122-127);
                                   0: the faces of this axis are walls / open / connected to other subdomains */
   int32_t simtype;             /* SLF_SIM_LBM | SLF_SIM_SHAN_CHEN_BINARY (lb_binary.py:375-517) |
-                                  SLF_SIM_SHAN_CHEN_SINGLE (lb_single.py:242-347; coupling constant in sc_G[0]) */
+                                  SLF_SIM_SHAN_CHEN_SINGLE (lb_single.py:242-347; coupling constant in sc_G[0]) |
+                                  SLF_SIM_FREE_ENERGY | SLF_SIM_SHAN_CHEN_TERNARY (lb_ternary.py; fields further down) */
   /* binary Shan-Chen: relaxation time of the second lattice (--tau_phi), coupling constants
    * G11, G12, G21, G22 (lb_binary.py:388-394) and pseudopotential (sym.py:896-908: 0 linear, 1 classic) */
   double tau_phi;
@@ -174,6 +176,15 @@ typedef struct slf_module_desc {
   double bc_wall_grad_phase;
   int32_t bc_wall_grad_order;
   int32_t fe_zero_grad_rim[3];
+  /* simtype = SLF_SIM_SHAN_CHEN_TERNARY (reference lb_ternary.py, templates/models/ternary_shan_chen.mako): three lattices
+   * with the densities rho, phi, theta, relaxed with tau, tau_phi and tau_theta (--tau_theta).  sc3_G[3 k + j] couples
+   * lattice k to the field of lattice j (row-major G11 G12 G13 G21 ... G33; the host passes symmetric pairs); a coupling
+   * that is exactly 0.0 is skipped.  sc_potential as in the binary model.  accel[], accel1[], accel2[]: body-force
+   * accelerations of lattices 0, 1, 2.  BGK; fluid, ghost, unused, propagation-only and full-way bounce-back nodes; direct
+   * addressing; connected x faces through ghost columns (no x-face planes). */
+  double tau_theta;
+  double sc3_G[9];
+  double accel2[3];
   /* model = SLF_ELBM (reference lb_single.py:31-69): f_i += alpha beta (feq_i - f_i) with beta = 1 / (2 visc / cs^2 + 1)
    * and alpha from the entropy equality H(f + alpha (feq - f)) = H(f): 2 where max_i |feq_i / f_i - 1| < 1e-6, the
    * series of PRL 97, 010201 below 0.01, Newton's method otherwise.  entropic_equilibrium (--entropic_equilibrium): the
@@ -371,9 +382,9 @@ int slf_module_poll_invalid(slf_module* m, slf_stream* stream, int32_t out[4]);
 int slf_module_update_node_params(slf_module* m, int first, const double* values, int n, slf_stream* stream);
 /* A body force that changes with time (add_body_force(DynamicValue(...)) of sym.S.time, reference lb_base.py:335-353 +
  * the rendered expression in relaxation_common.mako:body_force): the acceleration is an argument of every sweep launch,
- * so the host sets the value the NEXT launches take -- accel[3] for lattice 0, or lattice 1 of a binary model.  The
- * module must have been created with a body force (has_force, resp. accel1): which instantiation runs was decided
- * there.  Forces that depend on position are not served (they would need a field). */
+ * so the host sets the value the NEXT launches take -- accel[3] for lattice 0, lattice 1 of a binary or ternary model, or
+ * lattice 2 of a ternary one.  For lattice 0 the module must have been created with a body force (has_force): which
+ * instantiation runs was decided there.  Forces that depend on position are not served (they would need a field). */
 int slf_module_set_body_force(slf_module* m, int lattice, const double accel[3]);
 /* Row classes of the node map at `map_dptr` (no counterpart in the reference, whose kernels decode the map in every
  * thread: geo_helpers.mako:146-161, kernel_common.mako:191-201).  Builds, on the device, one class per 64-node
@@ -433,6 +444,18 @@ int slf_module_classify_rows(slf_module* m, const void* map_dptr, slf_stream* st
  * Single-component Shan-Chen modules (SLF_SIM_SHAN_CHEN_SINGLE) keep the single-fluid kernel names; their
  * "CollideAndPropagate" adds the pseudopotential force, and "PrepareMacroFields"(map, dist, rho, options)
  * computes the density field it reads (reference templates/models/lb_single_fluid.mako:129-229).
+ * Ternary Shan-Chen modules (simtype = SLF_SIM_SHAN_CHEN_TERNARY; reference lb_ternary.py:118-143, 220-333) serve the
+ * Shan-Chen names with the ternary argument lists:
+ * "ShanChenPrepareMacroFields"(map, dist1, dist2, dist3, rho, phi, theta, vx, vy[, vz], options): the three densities and
+ * the common velocity of every wet node,
+ * "ShanChenCollideAndPropagate0" / "...1" / "...2"(map, dist_in, dist_out, rho, phi, theta, vx, vy[, vz], options): the
+ * sweep of lattice 0 / 1 / 2,
+ * "ShanChenCollideAndPropagateFused"(map, dist1_in, dist1_out, dist2_in, dist2_out, dist3_in, dist3_out, rho, phi, theta,
+ * vx, vy[, vz], options): the three sweeps in one pass, bit-identical to them (no counterpart in the reference), and
+ * "SetInitialConditions"(map, dist1, dist2, dist3, vx, vy[, vz], rho, phi, theta).
+ * Every other sweep name ("CollideAndPropagate", "ShanChenPrepareDensities", "ShanChenCollideAndPropagateFusedV", the
+ * free-energy names ...) and the binary argument lists fail in such a module with a message that names the simtype;
+ * "ShanChenCollideAndPropagate2" fails the same way in every other module.
  * Free-energy modules (simtype = SLF_SIM_FREE_ENERGY) provide, with the reference's argument lists
  * (templates/models/lb_binary_fluid.mako:130-369, lb_binary.py:295-308):
  * "FreeEnergyPrepareMacroFields"(map, dist1, dist2, rho, phi, options): phi of every node (wetting walls included),

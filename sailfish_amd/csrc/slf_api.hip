@@ -62,7 +62,13 @@ enum KernelKind {
   KK_FE_FLUID,
   KK_FE_ORDER,
   KK_FE_INIT,
-  KK_RESIDENT,               // several steps inside one launch (slf_resident.hip)
+  KK_SC3_MACRO,               // ternary Shan-Chen mixture (slf_sc3.hip)
+  KK_SC3_SWEEP0,              // ... the sweeps of lattices 0, 1, 2 in this order
+  KK_SC3_SWEEP1,
+  KK_SC3_SWEEP2,
+  KK_SC3_FUSED,
+  KK_SC3_INIT,
+  KK_RESIDENT,              // several steps inside one launch (slf_resident.hip)
 };
 
 }  // namespace
@@ -89,6 +95,7 @@ struct slf_module {
   slf::Physics phys;
   slf::ShanChen sc;
   slf::FreeEnergy fe;
+  slf::ShanChen3 sc3;
   int access_pattern;
   int block_x;
   void* node_params;  // device copy, in the module's precision
@@ -988,7 +995,7 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
   if (d->node_addressing == SLF_ADDR_INDIRECT) {
     if (d->fluid_only) { delete m; return fail(SLF_ERR_INVALID, "indirect addressing needs the node map (fluid_only = 0)"); }
     if (d->simtype != SLF_SIM_LBM && d->simtype != SLF_SIM_SHAN_CHEN_BINARY && d->simtype != SLF_SIM_SHAN_CHEN_SINGLE &&
-        d->simtype != SLF_SIM_FREE_ENERGY) {      // (free energy: refused below, with its own message)
+        d->simtype != SLF_SIM_FREE_ENERGY && d->simtype != SLF_SIM_SHAN_CHEN_TERNARY) {      // (free energy, ternary: refused below, with their own messages)
       delete m;
       return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: unknown simtype");
     }
@@ -1202,6 +1209,34 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
       return fail(SLF_ERR_UNSUPPORTED, why);
     }
   }
+  m->sc3 = slf::ShanChen3{};
+  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) {
+    // what slf_sc3.hip implements of the reference's model (lb_ternary.py); everything else is named and refused
+    slf::ShanChen3& t = m->sc3;
+    t.enabled = 1;
+    t.tau_phi = d->tau_phi;
+    t.tau_theta = d->tau_theta;
+    for (int i = 0; i < 9; i++) t.G[i] = d->sc3_G[i];
+    t.potential = d->sc_potential;
+    for (int i = 0; i < 3; i++) { t.accel1[i] = d->accel1[i]; t.accel2[i] = d->accel2[i]; }
+    const char* why = nullptr;
+    if (d->model != SLF_BGK) why = "ternary Shan-Chen: --model other than bgk is not implemented; the BGK collision only";
+    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "ternary Shan-Chen: --node_addressing=indirect is not implemented; direct addressing only";
+    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "ternary Shan-Chen: --incompressible / --minimize_roundoff are not implemented";
+    else if (!(d->tau_phi > 0.5) || !(d->tau_theta > 0.5)) why = "ternary Shan-Chen: tau_phi and tau_theta must be > 0.5";
+    else if (d->sc_potential != 0 && d->sc_potential != 1) why = "ternary Shan-Chen: sc_potential is 0 (linear) or 1 (classic)";
+    for (int i = 0; !why && i < d->n_types; i++) {
+      const int k = d->type_kind[i];
+      if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
+        why = "ternary Shan-Chen: fluid and full-way bounce-back (NTFullBBWall) nodes only; the other boundary conditions "
+              "are not implemented";
+    }
+    // (--regularized / --subgrid / --model=elbm were refused above: single-fluid modules only)
+    if (why) {
+      delete m;
+      return fail(SLF_ERR_UNSUPPORTED, why);
+    }
+  }
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
   // workgroup; longer rows are cut into 256-thread chunks.
   int bx = ((d->lat_nx - 2 + 63) / 64) * 64;
@@ -1393,10 +1428,17 @@ int slf_module_set_body_force(slf_module* m, int lattice, const double accel[3])
     if (!m->phys.has_force) return fail(SLF_ERR_INVALID, "the module was created without a body force (has_force)");
     for (int i = 0; i < 3; i++) m->phys.accel[i] = accel[i];
   } else if (lattice == 1) {
+    if (m->sc3.enabled) {
+      for (int i = 0; i < 3; i++) m->sc3.accel1[i] = accel[i];
+      return SLF_OK;
+    }
     if (m->sc.enabled != 1) return fail(SLF_ERR_INVALID, "lattice 1 exists in binary models only");
     for (int i = 0; i < 3; i++) m->sc.accel1[i] = accel[i];
+  } else if (lattice == 2) {
+    if (!m->sc3.enabled) return fail(SLF_ERR_INVALID, "lattice 2 exists in ternary models (simtype = SLF_SIM_SHAN_CHEN_TERNARY) only");
+    for (int i = 0; i < 3; i++) m->sc3.accel2[i] = accel[i];
   } else {
-    return fail(SLF_ERR_INVALID, "lattice must be 0 or 1");
+    return fail(SLF_ERR_INVALID, "lattice must be 0, 1 or 2");
   }
   return SLF_OK;
 }
@@ -1416,7 +1458,7 @@ static int check_xface_buffers(const slf_module* m, void* send_low, void* send_h
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
   if (send_low || send_high || recv_low || recv_high) {
     const slf::Geometry& g = m->geo;
-    if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || m->fe.enabled || !(g.variant & 8))
+    if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || m->fe.enabled || m->sc3.enabled || !(g.variant & 8))
       return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: D3Q19 single-fluid modules with direct addressing (whole-row kernels) only");
     if (g.wrap[0]) return fail(SLF_ERR_INVALID, "x-face buffers make no sense with x wrapped inside the sweep");
     if (g.lat_nx - 2 > 1024) return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: rows of at most 1024 nodes");
@@ -1451,6 +1493,9 @@ static int check_xface_planes(const slf_module* m, int32_t which, void* send_low
   if (which < 0 || which > 2) return fail(SLF_ERR_INVALID, "x-face planes: 0 / 1 = populations of lattice 0 / 1, 2 = densities");
   if (send_low || send_high || recv_low || recv_high) {
     const slf::Geometry& g = m->geo;
+    if (m->sc3.enabled)
+      return fail(SLF_ERR_UNSUPPORTED, "x-face planes: not implemented for simtype = SLF_SIM_SHAN_CHEN_TERNARY (the planes carry two "
+                                       "lattices and two density fields); connected x faces go through ghost columns and index lists");
     if (m->sel.lattice != 1 || g.indirect || !m->sc.enabled || !(g.variant & 8))
       return fail(SLF_ERR_UNSUPPORTED, "x-face planes: D3Q19 Shan-Chen modules with direct addressing (whole-row kernels)");
     if (m->sc.enabled == 2 && which == 1) return fail(SLF_ERR_INVALID, "x-face planes: the single-component model has one lattice");
@@ -1542,7 +1587,7 @@ int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, 
 // ---- force on bodies by momentum exchange (slf_force.hip) --------------------------------------------------------
 static int check_force_call(const slf_module* m, int n_objects, uint32_t max_links, const char* what) {
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
-  if (m->sc.enabled || m->fe.enabled)
+  if (m->sc.enabled || m->fe.enabled || m->sc3.enabled)
     return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": single-fluid modules only (the force is read off lattice 0 alone)");
   if (n_objects < 0 || n_objects > 65535) return fail(SLF_ERR_INVALID, std::string(what) + ": 0 .. 65535 objects per call");
   if (max_links > 0x7FFFFFFFu) return fail(SLF_ERR_INVALID, std::string(what) + ": fewer than 2^31 links");
@@ -1598,7 +1643,28 @@ int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   else if (!strcmp(name, "ComputeMacroFields")) kk = KK_COMPUTE_MACRO;
   else if (!strcmp(name, "CollideAndPropagateResident")) kk = KK_RESIDENT;
   else if (slf::fe_kernel_index(name) >= 0) kk = (KernelKind)(KK_FE_MACRO + slf::fe_kernel_index(name));   // FreeEnergy...
+  else if (slf::sc3_kernel_index(name) >= 0) kk = KK_SC3_SWEEP2;      // ShanChenCollideAndPropagate2
   else return fail(SLF_ERR_NOT_FOUND, std::string("unknown kernel: ") + name);
+  if (m->sc3.enabled) {
+    // a ternary module: the names it shares with the binary model take the ternary argument lists
+    if (sc_local_velocity)
+      return fail(SLF_ERR_NOT_FOUND, std::string(name) + " does not exist in a module built with simtype = SLF_SIM_SHAN_CHEN_TERNARY "
+                                     "(the fused sweep reads the velocity of the pass in front)");
+    switch (kk) {
+      case KK_SC_MACRO: kk = KK_SC3_MACRO; break;
+      case KK_SC_SWEEP0: kk = KK_SC3_SWEEP0; break;
+      case KK_SC_SWEEP1: kk = KK_SC3_SWEEP1; break;
+      case KK_SC_FUSED: kk = KK_SC3_FUSED; break;
+      case KK_SET_INITIAL_CONDITIONS: kk = KK_SC3_INIT; break;
+      case KK_COLLIDE_AND_PROPAGATE: case KK_COMPUTE_MACRO: case KK_SCS_MACRO: case KK_SCS_SWEEP: case KK_RESIDENT:
+      case KK_FE_MACRO: case KK_FE_FLUID: case KK_FE_ORDER:
+        return fail(SLF_ERR_NOT_FOUND, std::string(name) + " does not exist in a module built with simtype = "
+                                       "SLF_SIM_SHAN_CHEN_TERNARY: single-fluid, binary and free-energy kernels are other modules'");
+      default: break;
+    }
+  } else if (kk == KK_SC3_SWEEP2) {
+    return fail(SLF_ERR_NOT_FOUND, std::string(name) + " only exists in modules built with simtype = SLF_SIM_SHAN_CHEN_TERNARY");
+  }
   if (kk == KK_RESIDENT) {
     // what the resident kernel serves (slf_resident.hip): 2-D single-fluid modules, direct addressing, the standard
     // density formulation, node kinds whose code touches nothing but the node's own populations
@@ -1709,6 +1775,12 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
     case KK_FE_ORDER: want_p = 5 + dim; want_i = 1; break;        // map, dist in, out, phi, v.., phi_laplacian, options
     case KK_FE_INIT: want_p = 5 + dim; want_i = 0; break;         // map, dist1, dist2, v.., rho, phi
     case KK_SCS_SWEEP: want_p = 4 + dim; want_i = 1; break;       // as CollideAndPropagate
+    case KK_SC3_MACRO: want_p = 7 + dim; want_i = 1; break;       // map, dist1, dist2, dist3, rho, phi, theta, v.., options
+    case KK_SC3_SWEEP0:
+    case KK_SC3_SWEEP1:
+    case KK_SC3_SWEEP2: want_p = 6 + dim; want_i = 1; break;      // map, dist in, out, rho, phi, theta, v.., options
+    case KK_SC3_FUSED: want_p = 10 + dim; want_i = 1; break;      // map, 3 x (dist in, out), rho, phi, theta, v.., options
+    case KK_SC3_INIT: want_p = 7 + dim; want_i = 0; break;        // map, dist1, dist2, dist3, v.., rho, phi, theta
     case KK_RESIDENT: want_p = 5; want_i = 5; break;              // map, src a, src b, dst a, dst b, options, steps, tile x, tile y, halo
   }
   if (k->kind == KK_RESIDENT && k->ptrs.size() == 5 && k->ints.size() == 5) {
@@ -1745,6 +1817,10 @@ int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv,
     want_p += 1;
     k->alpha_arg = true;
   }
+  if (k->kind >= KK_SC3_MACRO && k->kind <= KK_SC3_INIT && (k->ptrs.size() != want_p || k->ints.size() != want_i))
+    return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature: in a module built with simtype = "
+                                 "SLF_SIM_SHAN_CHEN_TERNARY the Shan-Chen kernels and SetInitialConditions take the ternary "
+                                 "argument lists (three lattices; rho, phi, theta)");
   if (k->ptrs.size() != want_p || k->ints.size() != want_i)
     return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature");
   k->pair_rows = k->pair_zc = 0;     // new arguments: slf_kernel_set_pair has to look at them again
@@ -1844,7 +1920,7 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   const int prefetch = knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch());
   const int xcd_log2 = knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2());
   const int march = knob("SLF_PAIR_MARCH", slf::pair_default_march());
-  if (m->sc.enabled || m->fe.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
+  if (m->sc.enabled || m->fe.enabled || m->sc3.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
   slf::SweepArgs a = {};
   pair_args(k, a);
@@ -2039,6 +2115,49 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       const void* v[3] = {(const void*)k->ptrs[3], (const void*)k->ptrs[4], g.dim == 3 ? (const void*)k->ptrs[5] : nullptr};
       e = slf::launch_fe_init(m->sel, g, m->fe, (void*)k->ptrs[1], (void*)k->ptrs[2], (const void*)k->ptrs[3 + g.dim],
                               (const void*)k->ptrs[4 + g.dim], v, m->sel.general ? (const void*)k->ptrs[0] : nullptr, s);
+      break;
+    }
+    case KK_SC3_MACRO:
+    case KK_SC3_SWEEP0:
+    case KK_SC3_SWEEP1:
+    case KK_SC3_SWEEP2:
+    case KK_SC3_FUSED: {
+      // argument lists of the reference (lb_ternary.py:220-333); the fused sweep: three (in, out) pairs
+      slf::Sc3Args a = {};
+      a.map = (const void*)k->ptrs[0];
+      int next = 1;
+      if (k->kind == KK_SC3_MACRO) {
+        for (int l = 0; l < 3; l++) a.dist_in[l] = (void*)k->ptrs[next++];
+      } else if (k->kind == KK_SC3_FUSED) {
+        for (int l = 0; l < 3; l++) {
+          a.dist_in[l] = (void*)k->ptrs[next++];
+          a.dist_out[l] = (void*)k->ptrs[next++];
+        }
+      } else {
+        a.dist_in[0] = (void*)k->ptrs[next++];
+        a.dist_out[0] = (void*)k->ptrs[next++];
+      }
+      for (int l = 0; l < 3; l++) a.field[l] = (void*)k->ptrs[next++];
+      for (int d = 0; d < g.dim; d++) a.v[d] = (void*)k->ptrs[next++];
+      a.options = (uint32_t)k->ints[0];
+      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+      if (!m->sel.general) a.map = nullptr;
+      slf::Prop prop;
+      if (int rc = step_prop(k, &prop)) return rc;
+      int y0, y1, z0, z1;
+      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
+      if (k->kind == KK_SC3_MACRO) e = slf::launch_sc3_macro(m->sel, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1, s);
+      else if (k->kind == KK_SC3_FUSED) e = slf::launch_sc3_fused(m->sel, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1, m->block_x, s);
+      else e = slf::launch_sc3_sweep(m->sel, (int)k->kind - (int)KK_SC3_SWEEP0, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1,
+                                     m->block_x, s);
+      break;
+    }
+    case KK_SC3_INIT: {
+      // (map, dist1, dist2, dist3, vx, vy[, vz], rho, phi, theta)  -- reference lb_ternary.py:118-142
+      void* const dist[3] = {(void*)k->ptrs[1], (void*)k->ptrs[2], (void*)k->ptrs[3]};
+      const void* const v[3] = {(const void*)k->ptrs[4], (const void*)k->ptrs[5], g.dim == 3 ? (const void*)k->ptrs[6] : nullptr};
+      const void* const field[3] = {(const void*)k->ptrs[4 + g.dim], (const void*)k->ptrs[5 + g.dim], (const void*)k->ptrs[6 + g.dim]};
+      e = slf::launch_sc3_init(m->sel, g, dist, field, v, s);
       break;
     }
     case KK_SC_INIT: {

@@ -88,6 +88,25 @@ struct FreeEnergy {
   int rim[3];                  // per axis: 1 / 2 = zero gradient and Laplacian on the low / high rim layer
 };
 
+// Ternary Shan-Chen mixture (slf_sc3.hip; reference lb_ternary.py); lattice 0 relaxes with Physics::tau
+struct ShanChen3 {
+  int enabled;
+  double tau_phi, tau_theta;   // relaxation times of lattices 1 and 2
+  double G[9];                 // row-major: G[3 k + j] couples lattice k to the density field of lattice j
+  int potential;               // 0 linear, 1 classic
+  double accel1[3], accel2[3]; // body-force accelerations on lattices 1 and 2 (Physics::accel acts on lattice 0)
+};
+
+// launch arguments of the ternary kernels
+struct Sc3Args {
+  const void* map;             // NULL: fluid-only module
+  void* dist_in[3];            // pass in front, fused sweep: lattices 0, 1, 2 | sweep of one lattice: [0]
+  void* dist_out[3];
+  void* field[3];              // rho, phi, theta
+  void* v[3];
+  uint32_t options;
+};
+
 struct RowClasses;
 struct SlotTable;
 
@@ -217,6 +236,21 @@ hipError_t launch_fe_init(const KernelSelector& sel, const Geometry& g, const Fr
                           const void* rho, const void* phi, const void* const v[3], const void* map, hipStream_t s);
 // 0 / 1 / 2: FreeEnergyPrepareMacroFields / ...CollideAndPropagateFluid / ...CollideAndPropagateOrderParam, -1: none of them
 int fe_kernel_index(const char* name);
+
+// ---- ternary Shan-Chen mixture (slf_sc3.hip) ----
+// pass in front: a.dist_in[0..2] (read) -> a.field[0..2], a.v
+hipError_t launch_sc3_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
+                            const Sc3Args& a, int y0, int y1, int z0, int z1, hipStream_t s);
+// collide-and-stream of lattice `lattice` (a.dist_in[0] -> a.dist_out[0]): reads the three fields and v
+hipError_t launch_sc3_sweep(const KernelSelector& sel, int lattice, Prop prop, const Geometry& g, const Physics& ph,
+                            const ShanChen3& sc, const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+// the three lattices in one pass: a.dist_in[k] -> a.dist_out[k]
+hipError_t launch_sc3_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
+                            const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* const dist[3], const void* const field[3],
+                           const void* const v[3], hipStream_t s);
+// 0: ShanChenCollideAndPropagate2 (the name only this family has), -1: not one of them
+int sc3_kernel_index(const char* name);
 
 // ---- several steps inside one launch (slf_resident.hip): 2-D lattices ----
 // src / dst: the raw distribution arrays ([0] = the array of the in-place pattern / copy A of the two-copy pattern, [1] =

@@ -1,6 +1,7 @@
 // What the sweeps of the models with nearest-neighbour fields share (binary / single-component Shan-Chen: slf_sc.hip; the
-// free-energy binary fluid: slf_fe.hip): a node's row and lane position, the cached read of a field at a neighbouring node,
-// and the loads and stores of one lattice's populations for the three streaming modes.
+// free-energy binary fluid: slf_fe.hip; the ternary Shan-Chen mixture: slf_sc3.hip): a node's row and lane position, the
+// cached read of a field at a neighbouring node, the pseudopotential, and the loads and stores of one lattice's populations
+// for the three streaming modes.
 #pragma once
 #include "slf_dispatch.h"
 #include "slf_rowpush.h"
@@ -46,6 +47,25 @@ __device__ __forceinline__ const SLF_GLOBAL T* sc_neighbour(const T* base, const
   constexpr int ex = L::ex(I);
   const int xs = (ex == 0) ? 0 : (((ex > 0) == forward) ? n.ox.p : n.ox.m);   // x part: per lane
   return at_byte(uniform_base(base + (uint32_t)((int)n.row + off)), (uint32_t)((int)n.xi + xs) * (uint32_t)sizeof(T));
+}
+
+template <class R, int POT>
+__device__ __forceinline__ R sc_psi(R rho) {
+  // sym.py:896-908: linear psi = rho; classic psi = 1 - exp(-rho)
+  if constexpr (POT == 0) return rho;
+  else if constexpr (sizeof(R) == 4) return 1.0f - expf(0.0f - rho);      // the reference's exp() on a float argument
+  else return (R)1 - exp((R)0 - rho);
+}
+
+// The module's potential (a run-time constant of the launch) as a compile-time constant of `body`: ONE wave-uniform
+// branch around a whole block of psi evaluations.  With the choice inside sc_psi() the compiler turned it into a select:
+// every one of the 38 psi values of a node went through the 15-instruction expf sequence and was thrown away again when
+// the potential is linear -- a third of the fused sweep's vector instructions (1577 per wave, the vector ALUs ~80 % busy:
+// profiles/r05/sq_summary_shan_chen_before.txt).
+template <class F>
+__device__ __forceinline__ void sc_with_potential(int potential, F&& body) {
+  if (potential == 0) body(std::integral_constant<int, 0>{});
+  else body(std::integral_constant<int, 1>{});
 }
 
 // INDIRECT (reference subdomain_runner.py:829-878, kernel_common.mako:140-167; serves NNSubdomainRunner too): the

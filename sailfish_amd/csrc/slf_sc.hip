@@ -53,25 +53,6 @@ struct ScParams {
   const R* mrecv[2];       //         densities of the neighbour's last / first column
 };
 
-template <class R, int POT>
-__device__ __forceinline__ R sc_psi(R rho) {
-  // sym.py:896-908: linear psi = rho; classic psi = 1 - exp(-rho)
-  if constexpr (POT == 0) return rho;
-  else if constexpr (sizeof(R) == 4) return 1.0f - expf(0.0f - rho);      // the reference's exp() on a float argument
-  else return (R)1 - exp((R)0 - rho);
-}
-
-// The module's potential (a run-time constant of the launch) as a compile-time constant of `body`: ONE wave-uniform
-// branch around a whole block of psi evaluations.  With the choice inside sc_psi() the compiler turned it into a select:
-// every one of the 38 psi values of a node went through the 15-instruction expf sequence and was thrown away again when
-// the potential is linear -- a third of the fused sweep's vector instructions (1577 per wave, the vector ALUs ~80 % busy:
-// profiles/r05/sq_summary_shan_chen_before.txt).
-template <class F>
-__device__ __forceinline__ void sc_with_potential(int potential, F&& body) {
-  if (potential == 0) body(std::integral_constant<int, 0>{});
-  else body(std::integral_constant<int, 1>{});
-}
-
 // Aligned pull of the populations of BOTH lattices for one (y, z) row in the odd in-place step -- the mirror image of
 // row_push(): node x needs slot opp(i) of node x - e_i; the lane that owns x' loads that slot of (y, z) - e_i(yz) at
 // ITS OWN x' (whole 128-byte lines, every line fetched by exactly one wave) and the value travels one lane along x: a

@@ -14,7 +14,7 @@ SLF_MAX_Q = 27
 SLF_D2Q9, SLF_D3Q19 = 0, 1
 SLF_BGK, SLF_MRT, SLF_ELBM = 0, 1, 2
 SLF_AB, SLF_AA = 0, 1
-SLF_SIM_LBM, SLF_SIM_SHAN_CHEN_BINARY, SLF_SIM_SHAN_CHEN_SINGLE, SLF_SIM_FREE_ENERGY = 0, 1, 2, 3
+SLF_SIM_LBM, SLF_SIM_SHAN_CHEN_BINARY, SLF_SIM_SHAN_CHEN_SINGLE, SLF_SIM_FREE_ENERGY, SLF_SIM_SHAN_CHEN_TERNARY = 0, 1, 2, 3, 4
 (SLF_NK_FLUID, SLF_NK_GHOST, SLF_NK_UNUSED, SLF_NK_PROPAGATION_ONLY, SLF_NK_FULL_BB, SLF_NK_HALF_BB,
  SLF_NK_REGULARIZED_VELOCITY, SLF_NK_EQUILIBRIUM_DENSITY, SLF_NK_EQUILIBRIUM_VELOCITY, SLF_NK_ZOUHE_VELOCITY,
  SLF_NK_ZOUHE_DENSITY, SLF_NK_REGULARIZED_DENSITY, SLF_NK_COPY, SLF_NK_YU_OUTFLOW, SLF_NK_DO_NOTHING,
@@ -65,6 +65,10 @@ class SlfModuleDesc(Structure):
         ('bc_wall_grad_phase', c_double),
         ('bc_wall_grad_order', c_int32),
         ('fe_zero_grad_rim', c_int32 * 3),
+        # ternary Shan-Chen (simtype = SLF_SIM_SHAN_CHEN_TERNARY)
+        ('tau_theta', c_double),
+        ('sc3_G', c_double * 9),
+        ('accel2', c_double * 3),
         ('entropic_equilibrium', c_int32),
         ('entropy_tolerance', c_double),
         ('alpha_tolerance', c_double),
@@ -260,7 +264,7 @@ def make_desc(**kw):
     d.arr_nz = 1
     keep = []
     for k, v in kw.items():
-        if k in ('periodic_fused', 'accel', 'periodic_local', 'sc_G', 'accel1', 'fe_zero_grad_rim'):
+        if k in ('periodic_fused', 'accel', 'periodic_local', 'sc_G', 'accel1', 'fe_zero_grad_rim', 'sc3_G', 'accel2'):
             for i, x in enumerate(v):
                 getattr(d, k)[i] = x
         elif k == 'mrt_rates':

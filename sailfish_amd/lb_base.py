@@ -242,7 +242,8 @@ class LBForcedSim(LBSim):
                                 'difference method (BGK only)')
 
     def add_body_force(self, force, grid=0, accel=True):
-        """Adds a constant global acceleration (accel=True) acting on the fluid."""
+        """Adds a global acceleration (accel=True) acting on lattice `grid`: a constant one on any lattice of the model
+        (0, 1 in binary models, 0, 1, 2 in ternary ones), a time-dependent one (DynamicValue) on lattice 0 only."""
         dim = self.grids[0].dim
         assert len(force) == dim
         if isinstance(force, nt.DynamicValue):
@@ -252,16 +253,19 @@ class LBForcedSim(LBSim):
             if force.space_dependent():
                 self.config.space_dependence = True
                 raise NotImplementedError('body forces that depend on position are not supported by the HIP backend')
+            # ... and the host evaluates it for lattice 0 only (body_force_at): lattices 1 and 2 of the binary and ternary
+            # models take constant accelerations
             if not accel or grid != 0:
-                raise NotImplementedError('time-dependent body forces: accelerations on lattice 0')
+                raise NotImplementedError('time-dependent body forces: accelerations on lattice 0 only (lattices 1 and 2 '
+                                          'of the binary and ternary models take constant accelerations)')
             if force.time_dependent():
                 self.config.time_dependence = True
             self._symbolic_forces.append(force)
             return
         if not accel:
             raise NotImplementedError('force (rather than acceleration) fields are not supported by the HIP backend')
-        if grid not in (0, 1):
-            raise NotImplementedError('the HIP backend handles body forces on lattices 0 and 1')
+        if grid not in range(max(2, len(self.grids))):
+            raise NotImplementedError('the HIP backend handles body forces on lattices 0 and 1 (and 2 in ternary models)')
         self._forces.setdefault(grid, {}).setdefault(accel, np.zeros(dim, np.float64))
         self._forces[grid][accel] = self._forces[grid][accel] + np.float64(force)
 
@@ -298,3 +302,6 @@ class LBForcedSim(LBSim):
             if len(self.grids) < 2:
                 raise ValueError('add_body_force(grid=1) on a model with a single lattice')
             kw['accel1'] = list(f1) + [0.0] * (3 - len(f1))
+        f2 = self._forces.get(2, {}).get(True)
+        if f2 is not None and np.any(f2 != 0.0):
+            kw['accel2'] = list(f2) + [0.0] * (3 - len(f2))

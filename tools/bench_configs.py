@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -250,6 +250,31 @@ def main():
     res.append(run('4: binary Shan-Chen D3Q19 256^3', SeparationSim, LBGeometry3D,
                    dict(lat_nx=256, lat_ny=256, lat_nz=256, access_pattern='AA', max_iters=int(1500 * it),
                         benchmark_sample_from=int(500 * it)), 516))
+    # config 12 (only with --only): ternary Shan-Chen 256^3, all six couplings non-zero.  12a: the reference's pass + three
+    # sweeps (SLF_SC_FUSED=0; from the argument lists: 228 B read + 24 written by the pass, 3 x (76 + 12 + 12 read, 76
+    # written) by the sweeps: about 780 B per node update), 12b: pass + ONE fused sweep (about 732 B); two-copy and in-place each
+    if only & set(('12a', '12b')):
+        import numpy as np
+        from sailfish_amd.lb_ternary import LBTernaryFluidShanChen
+
+        class TernaryBox(PeriodicBox):
+            def initial_conditions(self, sim, hx, hy, hz):
+                rng = np.random.RandomState(11)
+                for field, base in ((sim.rho, 1.0), (sim.phi, 0.7), (sim.theta, 0.5)):
+                    field[:] = base + 0.01 * rng.rand(*field.shape)
+
+        class TernarySim(LBTernaryFluidShanChen):
+            subdomain = TernaryBox
+
+        for cid, mode, nbytes in (('12a', '0', 780), ('12b', '2', 732)):
+            for pattern in ('AB', 'AA'):
+                os.environ['SLF_SC_FUSED'] = mode
+                res.append(run('%s: ternary Shan-Chen D3Q19 256^3, %s (%s)' % (
+                    cid, 'pass + three sweeps' if mode == '0' else 'pass + fused sweep', pattern), TernarySim, LBGeometry3D,
+                    dict(lat_nx=256, lat_ny=256, lat_nz=256, periodic_x=True, periodic_y=True, periodic_z=True, grid='D3Q19',
+                         visc=1.0 / 6.0, tau_phi=0.9, tau_theta=1.1, G11=-0.1, G12=0.3, G13=0.25, G22=-0.09, G23=0.35, G33=-0.06,
+                         access_pattern=pattern, max_iters=int(600 * it), benchmark_sample_from=int(200 * it)), nbytes))
+                os.environ.pop('SLF_SC_FUSED', None)
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
