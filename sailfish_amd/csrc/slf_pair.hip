@@ -36,6 +36,14 @@
 //            (SLF_PAIR_XCD_LOG2 limits the shift; 0: strips as they come, neighbours always on different XCDs);
 //   march    SLF_PAIR_MARCH=1: odd strips walk the rows downwards (y0 + TY .. y0 - 1), even strips upwards, so that both
 //            neighbours touch the two rows they share at the same end of the march (upwards everywhere: four rows apart).
+//
+// Strip height.  TY 2 is the default, TY 4 is kept (SLF_PAIR_ROWS=4).  Two-row strips load and collide two rows of phase A
+// per own row where four-row strips need 1.5, but with the placement above the second read of a shared row is an L2 hit,
+// and 119 VGPRs give four waves per SIMD and two workgroups per CU where 197 give two and one.  Two two-row strips joined
+// in one workgroup of sixteen waves, handing each other the post-collision values of their seam rows through LDS instead
+// of colliding them twice (TY 4's row count at TY 2's registers), were built, were bit-identical and ran 18 % slower than
+// separate two-row strips: one barrier couples all sixteen waves of a CU three times per plane.  Not kept
+// (profiles/NOTES.md).
 #include "slf_dispatch.h"
 #include "slf_rowpush.h"
 
@@ -280,9 +288,11 @@ __global__ void __launch_bounds__(512, TY == 2 ? 4 : 2) pair_row_kernel(const Sw
 
 }  // namespace
 
-// Four-row strips where the box allows them: with the next row in flight under the collision they are what the bytes say
-// (reads 1.5 x 66/64 against 2 x 66/64), profiles/NOTES.md; two-row strips only need an even ny.
-int pair_default_rows(const Geometry& g) { return (g.lat_ny - 2) % 4 == 0 ? 4 : 2; }
+// Two-row strips, whatever the box (they only need an even ny).  By the bytes four-row strips read less (1.5 x 66/64 arrays
+// against 2 x 66/64), but with neighbouring strips on one XCD most of a strip's halo rows come from the L2, two-row strips
+// gain twice as much from that, and their four waves per SIMD (119 VGPRs against 197) hide more of what is left:
+// measured at 512^3 and 256^3, profiles/NOTES.md.  SLF_PAIR_ROWS=4 still selects four-row strips.
+int pair_default_rows(const Geometry&) { return 2; }
 int pair_default_zchunk(const Geometry&) { return 64; }
 int pair_default_prefetch() { return 1; }
 int pair_default_xcd_log2() { return 5; }
