@@ -10,12 +10,9 @@
 #include <vector>
 
 #include "../../include/sailfish_hip.h"
+#include "slf_bind.h"
 #include "slf_kernels.h"
 #include "slf_node.h"
-
-#ifndef SLF_DEFAULT_VARIANT
-#define SLF_DEFAULT_VARIANT 11
-#endif
 
 namespace {
 
@@ -36,41 +33,6 @@ int hip_fail(hipError_t e, const char* what) {
     if (_e != hipSuccess) return hip_fail(_e, #call); \
   } while (0)
 
-enum KernelKind {
-  KK_COLLIDE_AND_PROPAGATE,
-  KK_SET_INITIAL_CONDITIONS,
-  KK_PBC,
-  KK_PBC_SWAP,
-  KK_MACRO_PBC,
-  KK_COLLECT_SPARSE,
-  KK_DISTRIBUTE_SPARSE,
-  KK_COLLECT_BOX,
-  KK_DISTRIBUTE_BOX,
-  KK_COLLECT_FACE_SWAP,       // reference argument lists (kernel_utils.mako): ...ContinuousDataWithSwap
-  KK_DISTRIBUTE_FACE_SWAP,
-  KK_COLLECT_MACRO_FACE,      // ...ContinuousMacroData
-  KK_DISTRIBUTE_MACRO_FACE,
-  KK_COMPUTE_MACRO,
-  KK_SC_MACRO,
-  KK_SC_SWEEP0,
-  KK_SC_SWEEP1,
-  KK_SC_FUSED,
-  KK_SC_INIT,
-  KK_SCS_MACRO,
-  KK_SCS_SWEEP,
-  KK_FE_MACRO,                // free-energy binary fluid (slf_fe.hip); the three in the order of slf::fe_kernel_index()
-  KK_FE_FLUID,
-  KK_FE_ORDER,
-  KK_FE_INIT,
-  KK_SC3_MACRO,               // ternary Shan-Chen mixture (slf_sc3.hip)
-  KK_SC3_SWEEP0,              // ... the sweeps of lattices 0, 1, 2 in this order
-  KK_SC3_SWEEP1,
-  KK_SC3_SWEEP2,
-  KK_SC3_FUSED,
-  KK_SC3_INIT,
-  KK_RESIDENT,              // several steps inside one launch (slf_resident.hip)
-};
-
 }  // namespace
 
 struct slf_ctx {
@@ -88,16 +50,8 @@ struct slf_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
 };
-struct slf_module {
+struct slf_module : slf::ModuleConfig {   // sel, geo, phys, sc, fe, sc3, access_pattern, block_x, n_node_params (slf_bind.h)
   slf_ctx* ctx;
-  slf::KernelSelector sel;
-  slf::Geometry geo;
-  slf::Physics phys;
-  slf::ShanChen sc;
-  slf::FreeEnergy fe;
-  slf::ShanChen3 sc3;
-  int access_pattern;
-  int block_x;
   void* node_params;  // device copy, in the module's precision
   uint32_t* status;   // device {flag, x, y, z} of the on-GPU invalid value check
   void* xsend[2];     // x-face buffers (slf_module_set_xface_buffers), NULL = unused
@@ -108,7 +62,7 @@ struct slf_module {
   void* rows_mem;         // one device allocation behind the tables of `rows`
   slf::SlotTable slots;   // indirect addressing: slot -> node, built from the `nodes` table of the first launch that names it
   void* slots_mem;
-  int n_node_params, precision;
+  int precision;
   // slf_module_update_node_params: pinned staging buffers for long updates, each with the event of its last copy
   void* stage[4];
   hipEvent_t stage_ev[4];
@@ -117,14 +71,12 @@ struct slf_module {
 };
 struct slf_kernel {
   slf_module* mod;
-  KernelKind kind;
-  std::vector<unsigned long long> ptrs;  // 'P' args in order
-  std::vector<long long> ints;           // 'i' args in order
+  const slf::KernelRow* row;   // of slf::KERNEL_TABLE (slf_kernel_get)
+  slf::KernelKind kind;        // = row->kind
+  slf::BoundArgs args;         // slf_kernel_set_args
   int needs_iteration;
   uint32_t iteration;
   bool bound;
-  bool sc_local_velocity;   // ShanChenPrepareDensities / ShanChenCollideAndPropagateFusedV
-  bool alpha_arg = false;   // CollideAndPropagate of an entropic module: the last pointer is the alpha field
   int pair_rows = 0, pair_zc = 0;   // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); 0: single steps
   int pair_prefetch = 0;            // ... with this load path in phase A (SLF_PAIR_PREFETCH)
   int pair_xcd_log2 = 0, pair_march = 0;      // ... this strip placement and row order (SLF_PAIR_XCD_LOG2, SLF_PAIR_MARCH)
@@ -963,306 +915,21 @@ int slf_event_elapsed_ms(slf_event* start, slf_event* end, float* ms) {
 
 int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) {
   if (!ctx || !d || !out) return fail(SLF_ERR_INVALID, "NULL argument");
-  if (d->struct_size != sizeof(slf_module_desc)) return fail(SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
-  if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19) return fail(SLF_ERR_UNSUPPORTED, "unsupported lattice");
-  if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
-    return fail(SLF_ERR_UNSUPPORTED, "unsupported collision model");
-  if (d->precision != 4 && d->precision != 8) return fail(SLF_ERR_UNSUPPORTED, "precision must be 4 or 8");
-  if (d->access_pattern != SLF_AB && d->access_pattern != SLF_AA)
-    return fail(SLF_ERR_UNSUPPORTED, "unsupported access pattern");
-  const int dim = d->lattice == SLF_D2Q9 ? 2 : 3;
-  if (d->envelope != 1) return fail(SLF_ERR_UNSUPPORTED, "envelope size must be 1");
-  if (d->lat_nx < 3 || d->lat_ny < 3 || (dim == 3 && d->lat_nz < 3) || (dim == 2 && d->lat_nz != 1))
-    return fail(SLF_ERR_INVALID, "bad lattice size");
-  if (d->arr_nx < d->lat_nx || d->arr_ny < d->lat_ny || d->arr_nz < d->lat_nz)
-    return fail(SLF_ERR_INVALID, "padded size smaller than lattice size");
-  if (d->tau <= 0.5 && d->relaxation_enabled) return fail(SLF_ERR_INVALID, "tau must be > 0.5");
-  if (d->n_types < 0 || d->n_types > SLF_MAX_NODE_TYPES) return fail(SLF_ERR_INVALID, "too many node types");
-  const unsigned long long total = (unsigned long long)d->arr_nx * d->arr_ny * d->arr_nz;
-  if (total >= 0xFFFFFFFFull || d->dist_stride >= 0xFFFFFFFFull)
-    return fail(SLF_ERR_UNSUPPORTED, "subdomain too large for 32-bit node indices");
-
-  slf_module* m = new slf_module;
+  slf::ModuleConfig cfg;
+  const char* why = nullptr;
+  if (int rc = slf::module_config(d, &cfg, &why)) return fail(rc, why);
+  slf_module* m = new slf_module();     // everything the configuration does not hold: zero / NULL
+  static_cast<slf::ModuleConfig&>(*m) = cfg;
   m->ctx = ctx;
-  m->sel.lattice = d->lattice;
-  m->sel.model = d->model;
-  m->sel.precision = d->precision;
-  m->sel.general = !d->fluid_only;
-  if (d->node_addressing != SLF_ADDR_DIRECT && d->node_addressing != SLF_ADDR_INDIRECT) {
-    delete m;
-    return fail(SLF_ERR_INVALID, "node_addressing must be SLF_ADDR_DIRECT or SLF_ADDR_INDIRECT");
-  }
-  if (d->node_addressing == SLF_ADDR_INDIRECT) {
-    if (d->fluid_only) { delete m; return fail(SLF_ERR_INVALID, "indirect addressing needs the node map (fluid_only = 0)"); }
-    if (d->simtype != SLF_SIM_LBM && d->simtype != SLF_SIM_SHAN_CHEN_BINARY && d->simtype != SLF_SIM_SHAN_CHEN_SINGLE &&
-        d->simtype != SLF_SIM_FREE_ENERGY && d->simtype != SLF_SIM_SHAN_CHEN_TERNARY) {      // (free energy, ternary: refused below, with their own messages)
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: unknown simtype");
-    }
-  }
-  m->access_pattern = d->access_pattern;
-  slf::Geometry& g = m->geo;
-  g.dim = dim;
-  g.lat_nx = d->lat_nx; g.lat_ny = d->lat_ny; g.lat_nz = d->lat_nz;
-  g.arr_nx = d->arr_nx; g.arr_ny = d->arr_ny; g.arr_nz = d->arr_nz;
-  g.arr_nxy = d->arr_nx * d->arr_ny;
-  g.dist_size = (uint32_t)(d->dist_stride ? d->dist_stride : total);
-  if (d->node_addressing == SLF_ADDR_INDIRECT) {
-    // the stride is the number of active-node slots: the caller's business (it owns the address table)
-    if (d->dist_stride == 0) { delete m; return fail(SLF_ERR_INVALID, "indirect addressing: dist_stride (number of slots) must be given"); }
-  } else if (g.dist_size < total) {
-    delete m;
-    return fail(SLF_ERR_INVALID, "dist_stride smaller than the subdomain");
-  }
-  for (int i = 0; i < 3; i++) {
-    g.wrap[i] = (i < dim) ? (d->periodic_fused[i] != 0) : 0;
-    g.axis_mode[i] = g.wrap[i] ? 2 : ((i < dim && d->periodic_local[i]) ? 1 : 0);
-  }
-  g.type_mask = d->nt_type_mask;
-  g.param_shift = d->nt_misc_shift;
-  g.param_mask = (1u << d->nt_param_shift) - 1u;
-  g.orient_shift = d->nt_misc_shift + d->nt_param_shift + d->nt_scratch_shift;
-  g.type_lut = 0;
-  m->phys.tms_mask = 0;
-  for (int i = 0; i < d->n_types; i++) {
-    int k = d->type_kind[i];
-    if (k < 0 || k >= slf::NK_COUNT) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "node type kind not supported by the HIP backend");
-    }
-    if (k == SLF_NK_WALL_TMS) {      // inside the kernels: a half-way bounce-back type with a flag (slf_kernels.h)
-      m->phys.tms_mask |= 1u << i;
-      k = slf::NK_HALF_BB;
-    }
-    g.type_lut |= (unsigned long long)k << (4 * i);
-  }
-  for (int i = 0; i < d->n_types; i++) {
-    const int k = d->type_kind[i];
-    if ((k == SLF_NK_COPY || k == SLF_NK_YU_OUTFLOW) && d->access_pattern != SLF_AB) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "NTCopy / NTYuOutflow nodes read neighbouring nodes of the input lattice: "
-                                       "two-copy (AB) access pattern only, as in the reference (boundary.mako:626-628)");
-    }
-  }
-  for (int i = 0; i < d->n_types; i++) {
-    if (d->type_kind[i] == SLF_NK_DO_NOTHING && d->access_pattern != SLF_AB && d->node_addressing == SLF_ADDR_INDIRECT) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "NTDoNothing nodes of the in-place (AA) pattern keep their unknown populations in the ghost "
-                                       "nodes behind them, which own no slot under indirect addressing (the reference indexes "
-                                       "nodes[] unguarded there, boundary.mako:862-876 with propagation.mako:93-99)");
-    }
-  }
-  g.bc_level = 0;
-  for (int i = 0; i < d->n_types; i++) {
-    const int k = d->type_kind[i];
-    const bool plain = k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-                       k == SLF_NK_FULL_BB;
-    const int level = (k == SLF_NK_COPY || k == SLF_NK_YU_OUTFLOW || k == SLF_NK_DO_NOTHING || k == SLF_NK_SLIP) ? 2 : (plain ? 0 : 1);
-    if (level > g.bc_level) g.bc_level = level;
-  }
-  if (const char* ev = getenv("SLF_BC_LEVEL")) {      // tests: force the full instantiation
-    if (atoi(ev) > g.bc_level) g.bc_level = atoi(ev);
-  }
-  g.x_ghost_unused = 0;
-  g.use_link_tags = d->use_link_tags;
-  g.indirect = d->node_addressing == SLF_ADDR_INDIRECT;
-  g.variant = SLF_DEFAULT_VARIANT;
-  if (d->sparse_geometry) g.variant |= 64;
-  if (const char* ev = getenv("SLF_VARIANT")) g.variant = atoi(ev);
-  slf::Physics& ph = m->phys;
-  ph.tau = d->tau;
-  ph.visc = d->visc;
-  for (int i = 0; i < 3; i++) ph.accel[i] = d->accel[i];
-  for (int i = 0; i < 27; i++) ph.mrt_rates[i] = d->mrt_rates[i];
-  ph.incompressible = d->incompressible;
-  ph.has_force = d->has_force;
-  ph.relaxation_enabled = d->relaxation_enabled;
-  ph.force_edm = d->force_implementation == SLF_FORCE_EDM;
-  if (ph.force_edm && d->model != SLF_BGK) {
-    delete m;
-    return fail(SLF_ERR_UNSUPPORTED, "the exact difference method (force_implementation = EDM) needs the BGK collision");
-  }
-  ph.regularized = d->regularized != 0;
-  ph.subgrid = d->subgrid;
-  ph.smagorinsky_const = d->smagorinsky_const;
-  if (d->subgrid != SLF_SUBGRID_NONE && d->subgrid != SLF_SUBGRID_LES_SMAGORINSKY) {
-    delete m;
-    return fail(SLF_ERR_INVALID, "subgrid must be one of SLF_SUBGRID_*");
-  }
-  if (ph.regularized || ph.subgrid) {
-    // the options of the BGK relaxation preamble (relaxation_common.mako:166-237).  The reference's MRT relaxation does not
-    // call the preamble (its kernels would silently ignore both flags); here that is an error, as are the combinations the
-    // preamble's expressions were never written for
-    if (d->model != SLF_BGK || d->simtype != SLF_SIM_LBM || d->incompressible == SLF_DENSITY_ROUNDOFF || ph.force_edm) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "regularized / subgrid: single-fluid BGK modules, standard or incompressible density "
-                                       "model, Guo forcing or no body force");
-    }
-    if (ph.subgrid && !(d->smagorinsky_const > 0.0)) {
-      delete m;
-      return fail(SLF_ERR_INVALID, "subgrid = les-smagorinsky needs smagorinsky_const > 0");
-    }
-    g.variant = 0;       // per-node kernels: the tuned / whole-row ones implement the plain collision
-  }
-  if (ph.tms_mask && d->fluid_only) {
-    delete m;
-    return fail(SLF_ERR_UNSUPPORTED, "NTWallTMS nodes are node types: the module must read the node map (fluid_only = 0)");
-  }
-  if (ph.tms_mask) g.variant = 0;       // Tamm-Mott-Smith walls: the per-node kernels and the slot sweep carry their code
-  ph.entropic_equilibrium = d->entropic_equilibrium != 0;
-  ph.entropy_tolerance = d->entropy_tolerance;
-  ph.alpha_tolerance = d->alpha_tolerance;
-  if (ph.entropic_equilibrium && d->model != SLF_ELBM) {
-    delete m;
-    return fail(SLF_ERR_INVALID, "entropic_equilibrium needs model = SLF_ELBM");
-  }
-  if (d->model == SLF_ELBM) {
-    // what ELBM_relaxate (relaxation.mako:56-97) was written for, and what this library has fixtures for (regularized /
-    // subgrid, the options of the BGK preamble it never runs, were refused above)
-    const char* why = nullptr;
-    bool rates = false;            // a host that filled in MRT relaxation rates expects them to act
-    for (int i = 0; i < 27; i++) rates = rates || d->mrt_rates[i] != 0.0;
-    if (rates) why = "elbm: MRT relaxation rates are set (mrt_rates must be all zero: the entropic collision has one rate)";
-    else if (d->simtype != SLF_SIM_LBM) why = "elbm: single-fluid modules only (the Shan-Chen models use the BGK collision)";
-    else if (d->incompressible == SLF_DENSITY_ROUNDOFF) why = "elbm: minimize_roundoff stores f_i - w_i, the entropy needs the populations themselves";
-    else if (d->incompressible == SLF_DENSITY_INCOMPRESSIBLE && ph.entropic_equilibrium)
-      why = "elbm: the product-form equilibrium (entropic_equilibrium) is compressible; not with the incompressible density model";
-    else if (d->has_force) why = "elbm: body forces under the entropic collision are not served";
-    else if (!(d->entropy_tolerance > 0.0) || !(d->alpha_tolerance >= 0.0)) why = "elbm: entropy_tolerance must be > 0 and alpha_tolerance >= 0";
-    if (why) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, why);
-    }
-    g.variant = 0;       // per-node kernels only
-  }
-  if (d->incompressible == SLF_DENSITY_ROUNDOFF) {
-    // --minimize_roundoff: "BGK-like models" in the reference (lb_base.py:72-76); here BGK, single fluid, fluid and
-    // bounce-back nodes, through the per-node kernels (slf_node.h: macro_roundoff, bgk_relax_roundoff)
-    bool ok = d->model == SLF_BGK && d->simtype == SLF_SIM_LBM;
-    for (int i = 0; ok && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      ok = k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-           k == SLF_NK_FULL_BB || k == SLF_NK_HALF_BB || k == SLF_NK_WALL_TMS || k == SLF_NK_EQUILIBRIUM_DENSITY ||
-           k == SLF_NK_EQUILIBRIUM_VELOCITY;
-    }
-    if (!ok) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, "minimize_roundoff: BGK single-fluid modules with fluid, bounce-back, TMS wall and equilibrium "
-                                       "density / velocity nodes only (the reference's regularized and Zou-He expressions are "
-                                       "inconsistent under the option)");
-    }
-    g.variant = 0;       // no tuned / whole-row kernels: they implement the standard formulation
-  } else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE && d->incompressible != SLF_DENSITY_INCOMPRESSIBLE) {
-    delete m;
-    return fail(SLF_ERR_INVALID, "incompressible must be one of SLF_DENSITY_*");
-  }
-  m->sc.enabled = (d->simtype == SLF_SIM_SHAN_CHEN_BINARY) ? 1 : ((d->simtype == SLF_SIM_SHAN_CHEN_SINGLE) ? 2 : 0);
-  m->sc.tau_phi = d->tau_phi;
-  for (int i = 0; i < 4; i++) m->sc.G[i] = d->sc_G[i];
-  m->sc.potential = d->sc_potential;
-  for (int i = 0; i < 3; i++) m->sc.accel1[i] = d->accel1[i];
-  if (m->sc.enabled) {
-    if (d->model != SLF_BGK) { delete m; return fail(SLF_ERR_UNSUPPORTED, "Shan-Chen modules use the BGK collision"); }
-    if (m->sc.enabled == 1 && d->tau_phi <= 0.5) { delete m; return fail(SLF_ERR_INVALID, "tau_phi must be > 0.5"); }
-    if (m->sc.enabled == 2) m->sc.tau_phi = d->tau;
-    for (int i = 0; i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-            k == SLF_NK_FULL_BB)) {
-        delete m;
-        return fail(SLF_ERR_UNSUPPORTED, "Shan-Chen modules support fluid and full-way bounce-back nodes only");
-      }
-    }
-  }
-  m->fe = slf::FreeEnergy{};
-  if (d->simtype == SLF_SIM_FREE_ENERGY) {
-    // what slf_fe.hip implements of the reference's model (lb_binary.py:139-372); everything else is named and refused
-    slf::FreeEnergy& fe = m->fe;
-    fe.enabled = 1;
-    fe.Gamma = d->fe_Gamma; fe.kappa = d->fe_kappa; fe.A = d->fe_A;
-    fe.tau_a = d->fe_tau_a; fe.tau_b = d->fe_tau_b; fe.tau_phi = d->tau_phi;
-    fe.wall_phase = d->bc_wall_grad_phase;
-    fe.wall_order = d->bc_wall_grad_order;
-    for (int i = 0; i < 3; i++) fe.rim[i] = d->fe_zero_grad_rim[i];
-    const char* why = nullptr;
-    if (d->model == SLF_MRT) why = "free energy: --model=mrt (the FE-MRT collision, relaxation.mako:15-54) is not implemented; BGK only";
-    else if (d->model != SLF_BGK) why = "free energy: the BGK collision only";
-    else if (d->has_force || d->accel1[0] != 0.0 || d->accel1[1] != 0.0 || d->accel1[2] != 0.0)
-      why = "free energy: body forces (free_energy_external_force, use_force_for_equilibrium) are not implemented";
-    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "free energy: indirect addressing is not implemented; direct addressing only";
-    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "free energy: --incompressible / --minimize_roundoff are not implemented";
-    else if (!(d->fe_tau_a > 0.5) || !(d->fe_tau_b > 0.5) || !(d->tau_phi > 0.5)) why = "free energy: tau_a, tau_b and tau_phi must be > 0.5";
-    else if (d->bc_wall_grad_order != 1 && d->bc_wall_grad_order != 2) why = "free energy: bc_wall_grad_order must be 1 or 2";
-    for (int i = 0; !why && i < 3; i++) {
-      if (d->fe_zero_grad_rim[i] < 0 || d->fe_zero_grad_rim[i] > 2) why = "free energy: fe_zero_grad_rim entries are 0, 1 (low rim) or 2 (high rim)";
-    }
-    for (int i = 0; !why && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (k == SLF_NK_HALF_BB) why = "free energy: NTHalfBBWall wetting walls are not implemented; full-way bounce-back walls only";
-      else if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
-        why = "free energy: fluid and full-way bounce-back (NTFullBBWall) nodes only; NTGuoDensity and the other boundary "
-              "conditions are not implemented";
-    }
-    // (--regularized / --subgrid were refused above: single-fluid modules only)
-    if (why) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, why);
-    }
-  }
-  m->sc3 = slf::ShanChen3{};
-  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) {
-    // what slf_sc3.hip implements of the reference's model (lb_ternary.py); everything else is named and refused
-    slf::ShanChen3& t = m->sc3;
-    t.enabled = 1;
-    t.tau_phi = d->tau_phi;
-    t.tau_theta = d->tau_theta;
-    for (int i = 0; i < 9; i++) t.G[i] = d->sc3_G[i];
-    t.potential = d->sc_potential;
-    for (int i = 0; i < 3; i++) { t.accel1[i] = d->accel1[i]; t.accel2[i] = d->accel2[i]; }
-    const char* why = nullptr;
-    if (d->model != SLF_BGK) why = "ternary Shan-Chen: --model other than bgk is not implemented; the BGK collision only";
-    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "ternary Shan-Chen: --node_addressing=indirect is not implemented; direct addressing only";
-    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "ternary Shan-Chen: --incompressible / --minimize_roundoff are not implemented";
-    else if (!(d->tau_phi > 0.5) || !(d->tau_theta > 0.5)) why = "ternary Shan-Chen: tau_phi and tau_theta must be > 0.5";
-    else if (d->sc_potential != 0 && d->sc_potential != 1) why = "ternary Shan-Chen: sc_potential is 0 (linear) or 1 (classic)";
-    for (int i = 0; !why && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
-        why = "ternary Shan-Chen: fluid and full-way bounce-back (NTFullBBWall) nodes only; the other boundary conditions "
-              "are not implemented";
-    }
-    // (--regularized / --subgrid / --model=elbm were refused above: single-fluid modules only)
-    if (why) {
-      delete m;
-      return fail(SLF_ERR_UNSUPPORTED, why);
-    }
-  }
-  // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
-  // workgroup; longer rows are cut into 256-thread chunks.
-  int bx = ((d->lat_nx - 2 + 63) / 64) * 64;
-  if (bx > 1024) bx = 256;
-  const char* env = getenv("SLF_BLOCK_X");
-  if (env && atoi(env) >= 64 && atoi(env) <= 1024 && atoi(env) % 64 == 0) bx = atoi(env);
-  m->block_x = bx;
-  m->node_params = nullptr;
-  m->status = nullptr;
-  m->xsend[0] = m->xsend[1] = m->xrecv[0] = m->xrecv[1] = nullptr;
-  for (int w = 0; w < 3; w++) m->sc_send[w][0] = m->sc_send[w][1] = m->sc_recv[w][0] = m->sc_recv[w][1] = nullptr;
-  m->rows = slf::RowClasses{};
-  m->rows_mem = nullptr;
-  m->slots = slf::SlotTable{};
-  m->slots_mem = nullptr;
-  m->n_node_params = d->n_node_params > 0 ? d->n_node_params : 0;
   m->precision = d->precision;
-  for (int i = 0; i < 4; i++) { m->stage[i] = nullptr; m->stage_ev[i] = nullptr; m->stage_bytes[i] = 0; }
-  m->stage_next = 0;
+  auto bail = [m](hipError_t e, const char* what) {      // frees what has been allocated by then
+    slf_module_destroy(m);
+    return hip_fail(e, what);
+  };
   const int np = d->n_node_params > 0 ? d->n_node_params : 1;
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = hipMalloc(&m->node_params, (size_t)np * d->precision);
-  if (e != hipSuccess) {
-    delete m;
-    return hip_fail(e, "hipMalloc(node_params)");
-  }
+  if (e != hipSuccess) return bail(e, "hipMalloc(node_params)");
   if (d->precision == 4) {
     std::vector<float> tmp(np, 0.0f);
     for (int i = 0; i < d->n_node_params; i++) tmp[i] = (float)d->node_params[i];
@@ -1272,19 +939,10 @@ int slf_module_create(slf_ctx* ctx, const slf_module_desc* d, slf_module** out) 
     for (int i = 0; i < d->n_node_params; i++) tmp[i] = d->node_params[i];
     e = hipMemcpy(m->node_params, tmp.data(), np * sizeof(double), hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) {
-    hipFree(m->node_params);
-    delete m;
-    return hip_fail(e, "hipMemcpy(node_params)");
-  }
+  if (e != hipSuccess) return bail(e, "hipMemcpy(node_params)");
   e = hipMalloc((void**)&m->status, 4 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(m->status, 0, 4 * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    hipFree(m->node_params);
-    if (m->status) hipFree(m->status);
-    delete m;
-    return hip_fail(e, "hipMalloc(status)");
-  }
+  if (e != hipSuccess) return bail(e, "hipMalloc(status)");
   *out = m;
   return SLF_OK;
 }
@@ -1618,98 +1276,13 @@ int slf_force_objects(slf_module* m, const void* dist, const uint32_t* idx, cons
 
 int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   if (!m || !name || !out) return fail(SLF_ERR_INVALID, "NULL argument");
-  KernelKind kk;
-  bool sc_local_velocity = false;
-  if (!strcmp(name, "CollideAndPropagate")) kk = (m->sc.enabled == 2) ? KK_SCS_SWEEP : KK_COLLIDE_AND_PROPAGATE;
-  else if (!strcmp(name, "PrepareMacroFields")) kk = KK_SCS_MACRO;
-  else if (!strcmp(name, "SetInitialConditions")) kk = m->fe.enabled ? KK_FE_INIT : ((m->sc.enabled == 1) ? KK_SC_INIT : KK_SET_INITIAL_CONDITIONS);
-  else if (!strcmp(name, "ShanChenPrepareMacroFields")) kk = KK_SC_MACRO;
-  else if (!strcmp(name, "ShanChenCollideAndPropagate0")) kk = KK_SC_SWEEP0;
-  else if (!strcmp(name, "ShanChenCollideAndPropagate1")) kk = KK_SC_SWEEP1;
-  else if (!strcmp(name, "ShanChenCollideAndPropagateFused")) kk = KK_SC_FUSED;
-  else if (!strcmp(name, "ShanChenPrepareDensities")) { kk = KK_SC_MACRO; sc_local_velocity = true; }
-  else if (!strcmp(name, "ShanChenCollideAndPropagateFusedV")) { kk = KK_SC_FUSED; sc_local_velocity = true; }
-  else if (!strcmp(name, "ApplyPeriodicBoundaryConditions")) kk = KK_PBC;
-  else if (!strcmp(name, "ApplyPeriodicBoundaryConditionsWithSwap")) kk = KK_PBC_SWAP;
-  else if (!strcmp(name, "ApplyMacroPeriodicBoundaryConditions")) kk = KK_MACRO_PBC;
-  else if (!strcmp(name, "CollectSparseData")) kk = KK_COLLECT_SPARSE;
-  else if (!strcmp(name, "DistributeSparseData")) kk = KK_DISTRIBUTE_SPARSE;
-  else if (!strcmp(name, "CollectContinuousData")) kk = KK_COLLECT_BOX;
-  else if (!strcmp(name, "DistributeContinuousData")) kk = KK_DISTRIBUTE_BOX;
-  else if (!strcmp(name, "CollectContinuousDataWithSwap")) kk = KK_COLLECT_FACE_SWAP;
-  else if (!strcmp(name, "DistributeContinuousDataWithSwap")) kk = KK_DISTRIBUTE_FACE_SWAP;
-  else if (!strcmp(name, "CollectContinuousMacroData")) kk = KK_COLLECT_MACRO_FACE;
-  else if (!strcmp(name, "DistributeContinuousMacroData")) kk = KK_DISTRIBUTE_MACRO_FACE;
-  else if (!strcmp(name, "ComputeMacroFields")) kk = KK_COMPUTE_MACRO;
-  else if (!strcmp(name, "CollideAndPropagateResident")) kk = KK_RESIDENT;
-  else if (slf::fe_kernel_index(name) >= 0) kk = (KernelKind)(KK_FE_MACRO + slf::fe_kernel_index(name));   // FreeEnergy...
-  else if (slf::sc3_kernel_index(name) >= 0) kk = KK_SC3_SWEEP2;      // ShanChenCollideAndPropagate2
-  else return fail(SLF_ERR_NOT_FOUND, std::string("unknown kernel: ") + name);
-  if (m->sc3.enabled) {
-    // a ternary module: the names it shares with the binary model take the ternary argument lists
-    if (sc_local_velocity)
-      return fail(SLF_ERR_NOT_FOUND, std::string(name) + " does not exist in a module built with simtype = SLF_SIM_SHAN_CHEN_TERNARY "
-                                     "(the fused sweep reads the velocity of the pass in front)");
-    switch (kk) {
-      case KK_SC_MACRO: kk = KK_SC3_MACRO; break;
-      case KK_SC_SWEEP0: kk = KK_SC3_SWEEP0; break;
-      case KK_SC_SWEEP1: kk = KK_SC3_SWEEP1; break;
-      case KK_SC_FUSED: kk = KK_SC3_FUSED; break;
-      case KK_SET_INITIAL_CONDITIONS: kk = KK_SC3_INIT; break;
-      case KK_COLLIDE_AND_PROPAGATE: case KK_COMPUTE_MACRO: case KK_SCS_MACRO: case KK_SCS_SWEEP: case KK_RESIDENT:
-      case KK_FE_MACRO: case KK_FE_FLUID: case KK_FE_ORDER:
-        return fail(SLF_ERR_NOT_FOUND, std::string(name) + " does not exist in a module built with simtype = "
-                                       "SLF_SIM_SHAN_CHEN_TERNARY: single-fluid, binary and free-energy kernels are other modules'");
-      default: break;
-    }
-  } else if (kk == KK_SC3_SWEEP2) {
-    return fail(SLF_ERR_NOT_FOUND, std::string(name) + " only exists in modules built with simtype = SLF_SIM_SHAN_CHEN_TERNARY");
-  }
-  if (kk == KK_RESIDENT) {
-    // what the resident kernel serves (slf_resident.hip): 2-D single-fluid modules, direct addressing, the standard
-    // density formulation, node kinds whose code touches nothing but the node's own populations
-    const slf::Geometry& g = m->geo;
-    if (g.dim != 2 || m->sc.enabled || m->fe.enabled || g.indirect || m->phys.incompressible == SLF_DENSITY_ROUNDOFF || m->phys.regularized ||
-        m->phys.subgrid || m->sel.model == SLF_ELBM)
-      return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: 2-D single-fluid modules with direct addressing and the "
-                                       "standard density formulation only");
-    if (g.axis_mode[0] == 1 || g.axis_mode[1] == 1)
-      return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: periodic axes must be wrapped in-sweep (periodic_fused)");
-    for (int t = 0; t < 16; t++) {
-      const int kind = slf::type_kind(g.type_lut, (uint32_t)t);
-      if (kind == slf::NK_HALF_BB || kind == slf::NK_COPY || kind == slf::NK_YU_OUTFLOW || kind == slf::NK_DO_NOTHING)
-        return fail(SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: half-way bounce-back, TMS wall, outflow and do-nothing nodes read / "
-                                         "write memory from their node code");
-    }
-  }
-  if (kk == KK_SCS_MACRO && m->sc.enabled != 2)
-    return fail(SLF_ERR_NOT_FOUND, "PrepareMacroFields only exists in single-component Shan-Chen modules");
-  if ((kk == KK_SC_MACRO || kk == KK_SC_SWEEP0 || kk == KK_SC_SWEEP1 || kk == KK_SC_FUSED) && m->sc.enabled != 1)
-    return fail(SLF_ERR_NOT_FOUND, "Shan-Chen kernels only exist in modules built with simtype = SLF_SIM_SHAN_CHEN_BINARY");
-  if ((kk == KK_COLLIDE_AND_PROPAGATE || kk == KK_COMPUTE_MACRO) && m->sc.enabled == 1)
-    return fail(SLF_ERR_NOT_FOUND, "single-fluid kernels do not exist in a Shan-Chen module");
-  if ((kk == KK_FE_MACRO || kk == KK_FE_FLUID || kk == KK_FE_ORDER) && !m->fe.enabled)
-    return fail(SLF_ERR_NOT_FOUND, "FreeEnergy... kernels only exist in modules built with simtype = SLF_SIM_FREE_ENERGY");
-  if ((kk == KK_COLLIDE_AND_PROPAGATE || kk == KK_COMPUTE_MACRO) && m->fe.enabled)
-    return fail(SLF_ERR_NOT_FOUND, "single-fluid kernels do not exist in a free-energy module");
-  if ((kk == KK_PBC || kk == KK_PBC_SWAP) && m->geo.indirect)
-    return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: periodic boundaries are wrapped inside the sweep "
-                                     "(periodic_fused), there are no ghost-layer PBC kernels");
-  if (kk == KK_PBC_SWAP && m->access_pattern != SLF_AA)
-    return fail(SLF_ERR_NOT_FOUND, "ApplyPeriodicBoundaryConditionsWithSwap only exists for the AA access pattern");
-  if ((kk == KK_COLLECT_FACE_SWAP || kk == KK_DISTRIBUTE_FACE_SWAP) && m->access_pattern != SLF_AA)
-    return fail(SLF_ERR_NOT_FOUND, "Collect / DistributeContinuousDataWithSwap only exist for the AA access pattern "
-                                   "(reference kernel_utils.mako:536, 638, 700, 786)");
-  if ((kk == KK_COLLECT_FACE_SWAP || kk == KK_DISTRIBUTE_FACE_SWAP || kk == KK_COLLECT_MACRO_FACE ||
-       kk == KK_DISTRIBUTE_MACRO_FACE) && m->geo.indirect)
-    return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: halo through index lists (Collect / DistributeSparseData)");
-  slf_kernel* k = new slf_kernel;
+  const slf::KernelRow* row = nullptr;
+  std::string why;
+  if (int rc = slf::resolve(*m, name, &row, &why)) return fail(rc, why);
+  slf_kernel* k = new slf_kernel();
   k->mod = m;
-  k->kind = kk;
-  k->needs_iteration = 0;
-  k->iteration = 0;
-  k->bound = false;
-  k->sc_local_velocity = sc_local_velocity;
+  k->row = row;
+  k->kind = row->kind;
   *out = k;
   return SLF_OK;
 }
@@ -1719,120 +1292,47 @@ int slf_kernel_destroy(slf_kernel* k) {
   return SLF_OK;
 }
 
+// CollideAndPropagateResident: what its integer arguments (options, steps, tile x, tile y, halo) and arrays must satisfy
+static int check_resident_args(const slf_module* m, const slf::BoundArgs& b, int needs_iteration) {
+  const slf::SweepArgs& a = b.sweep;      // dist_in / dist_in2: source a / b, dist_out / dist_out2: destination a / b
+  const bool aa = m->access_pattern == SLF_AA;
+  const int steps = (int)b.ints[1], tx = (int)b.ints[2], ty = (int)b.ints[3], halo = (int)b.ints[4];
+  if (!needs_iteration) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident needs the iteration argument (its first step)");
+  if (steps < 1 || tx < 1 || ty < 1 || halo < 1) return fail(SLF_ERR_INVALID, "steps, tile and halo must be positive");
+  if (!a.dist_in || !a.dist_out || (!aa && (!a.dist_in2 || !a.dist_out2)))
+    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination arrays (both copies of the two-copy pattern)");
+  if (a.dist_in == a.dist_out || (!aa && a.dist_in2 == a.dist_out2))
+    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination must be different buffers");
+  // the halo that `steps` steps need depends on the parity of the first one: the worse of the two must fit
+  const int need = std::max(slf::resident_halo(aa, 0, steps), slf::resident_halo(aa, 1, steps));
+  if (halo < need) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: halo too small for this many steps");
+  const long long nw = (long long)(tx + 2 * halo) * (long long)(ty + 2 * halo);
+  if (nw > 2 * 1024) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window larger than 2048 nodes");
+  const int q = 9;
+  // the window (dynamic LDS) + the kernel's own tables (static: the list of a window's boundary-condition nodes,
+  // slf_resident.hip) share the 160 KiB of a workgroup
+  if (slf::resident_lds_bytes(q, m->sel.precision, aa, tx + 2 * halo, ty + 2 * halo) + 4352 > 160 * 1024)
+    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window does not fit the 160 KiB of LDS");
+  return SLF_OK;
+}
+
 int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv, int argc, int needs_iteration) {
   if (!k || !fmt || (!argv && argc > 0)) return fail(SLF_ERR_INVALID, "NULL argument");
-  if ((int)strlen(fmt) != argc) return fail(SLF_ERR_INVALID, "format / argc mismatch");
-  k->ptrs.clear();
-  k->ints.clear();
-  for (int i = 0; i < argc; i++) {
-    switch (fmt[i]) {
-      case 'P': k->ptrs.push_back(*(const unsigned long long*)argv[i]); break;
-      case 'i': k->ints.push_back(*(const int32_t*)argv[i]); break;
-      default: return fail(SLF_ERR_INVALID, std::string("unsupported format char: ") + fmt[i]);
-    }
+  slf::BoundArgs b;
+  std::string why;
+  if (int rc = slf::bind(*k->mod, *k->row, fmt, argv, argc, &b, &why)) return fail(rc, why);
+  if (k->kind == slf::KK_RESIDENT) {
+    if (int rc = check_resident_args(k->mod, b, needs_iteration)) return rc;
   }
-  const int dim = k->mod->geo.dim;
-  size_t want_p = 0, want_i = 0;
-  switch (k->kind) {
-    case KK_COLLIDE_AND_PROPAGATE:
-    case KK_COMPUTE_MACRO: want_p = 4 + dim; want_i = 1; break;   // map, dist_in, dist_out, rho, v.., options [, alpha]
-    case KK_SET_INITIAL_CONDITIONS: want_p = 3 + dim; want_i = 0; break;  // dist, v.., rho, map
-    case KK_PBC:
-    case KK_PBC_SWAP:
-    case KK_MACRO_PBC: want_p = 1; want_i = 1; break;             // dist|field, axis
-    case KK_COLLECT_SPARSE:
-    case KK_DISTRIBUTE_SPARSE: want_p = 3; want_i = 1; break;     // idx_array, dist, buffer, n
-    case KK_COLLECT_BOX:
-    case KK_DISTRIBUTE_BOX:                                       // dist, buffer, dirs, base, col_stride, ncols, row_stride, nrows
-      want_p = 2;                                                 // [, buffer stride between directions, between rows]
-      want_i = (k->ints.size() == 8) ? 8 : 6;
-      // ... or the reference's own argument list (kernel_utils.mako:526-543, 629-645, 692-708, 777-793):
-      // 3-D (dist, face, base_gx, base_other, max_lx, max_other, buffer), 2-D (dist, face, base_gx, max_lx, buffer)
-      if (k->ints.size() == (dim == 3 ? 5u : 3u)) {
-        want_i = k->ints.size();
-        if (strcmp(fmt, dim == 3 ? "PiiiiiP" : "PiiiP")) return fail(SLF_ERR_INVALID, "reference form: the buffer is the last argument");
-        if (k->mod->geo.indirect) return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: halo through index lists");
-      }
-      break;
-    case KK_COLLECT_FACE_SWAP:
-    case KK_DISTRIBUTE_FACE_SWAP:                                 // as the reference form above
-      want_p = 2; want_i = dim == 3 ? 5 : 3;
-      if (strcmp(fmt, dim == 3 ? "PiiiiiP" : "PiiiP")) return fail(SLF_ERR_INVALID, "arguments: (dist, face, base_gx[, base_other], max_lx[, max_other], buffer)");
-      break;
-    case KK_COLLECT_MACRO_FACE:
-    case KK_DISTRIBUTE_MACRO_FACE:                                // 3-D (field, face, base_gx, base_other, max_lx, max_other, buffer)
-      want_p = 2; want_i = dim == 3 ? 5 : 3;                      // 2-D (field, base_gx, max_lx, gy, buffer)   kernel_utils.mako:839-953
-      if (strcmp(fmt, dim == 3 ? "PiiiiiP" : "PiiiP")) return fail(SLF_ERR_INVALID, "arguments: (field, [face,] base_gx, ..., buffer)");
-      break;
-    case KK_SC_MACRO:
-    case KK_SC_SWEEP0:
-    case KK_SC_SWEEP1: want_p = 5 + dim; want_i = 1; break;       // map, dist, dist, rho, phi, v.., options
-    case KK_SC_FUSED: want_p = 7 + dim; want_i = 1; break;        // map, dist0 in, out, dist1 in, out, rho, phi, v.., options
-    case KK_SC_INIT: want_p = 5 + dim; want_i = 0; break;         // map, dist1, dist2, v.., rho, phi
-    case KK_SCS_MACRO: want_p = 3; want_i = 1; break;             // map, dist, rho, options
-    case KK_FE_MACRO: want_p = 5; want_i = 1; break;              // map, dist1, dist2, rho, phi, options
-    case KK_FE_FLUID: want_p = 6 + dim; want_i = 1; break;        // map, dist in, out, rho, phi, v.., phi_laplacian, options
-    case KK_FE_ORDER: want_p = 5 + dim; want_i = 1; break;        // map, dist in, out, phi, v.., phi_laplacian, options
-    case KK_FE_INIT: want_p = 5 + dim; want_i = 0; break;         // map, dist1, dist2, v.., rho, phi
-    case KK_SCS_SWEEP: want_p = 4 + dim; want_i = 1; break;       // as CollideAndPropagate
-    case KK_SC3_MACRO: want_p = 7 + dim; want_i = 1; break;       // map, dist1, dist2, dist3, rho, phi, theta, v.., options
-    case KK_SC3_SWEEP0:
-    case KK_SC3_SWEEP1:
-    case KK_SC3_SWEEP2: want_p = 6 + dim; want_i = 1; break;      // map, dist in, out, rho, phi, theta, v.., options
-    case KK_SC3_FUSED: want_p = 10 + dim; want_i = 1; break;      // map, 3 x (dist in, out), rho, phi, theta, v.., options
-    case KK_SC3_INIT: want_p = 7 + dim; want_i = 0; break;        // map, dist1, dist2, dist3, v.., rho, phi, theta
-    case KK_RESIDENT: want_p = 5; want_i = 5; break;              // map, src a, src b, dst a, dst b, options, steps, tile x, tile y, halo
-  }
-  if (k->kind == KK_RESIDENT && k->ptrs.size() == 5 && k->ints.size() == 5) {
-    const bool aa = k->mod->access_pattern == SLF_AA;
-    const int steps = (int)k->ints[1], tx = (int)k->ints[2], ty = (int)k->ints[3], halo = (int)k->ints[4];
-    if (!needs_iteration) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident needs the iteration argument (its first step)");
-    if (steps < 1 || tx < 1 || ty < 1 || halo < 1) return fail(SLF_ERR_INVALID, "steps, tile and halo must be positive");
-    if (!k->ptrs[1] || !k->ptrs[3] || (!aa && (!k->ptrs[2] || !k->ptrs[4])))
-      return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination arrays (both copies of the two-copy pattern)");
-    if (k->ptrs[1] == k->ptrs[3] || (!aa && k->ptrs[2] == k->ptrs[4]))
-      return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination must be different buffers");
-    // the halo that `steps` steps need depends on the parity of the first one: the worse of the two must fit
-    const int need = std::max(slf::resident_halo(aa, 0, steps), slf::resident_halo(aa, 1, steps));
-    if (halo < need) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: halo too small for this many steps");
-    const long long nw = (long long)(tx + 2 * halo) * (long long)(ty + 2 * halo);
-    if (nw > 2 * 1024) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window larger than 2048 nodes");
-    const int q = 9;
-    // the window (dynamic LDS) + the kernel's own tables (static: the list of a window's boundary-condition nodes,
-    // slf_resident.hip) share the 160 KiB of a workgroup
-    if (slf::resident_lds_bytes(q, k->mod->sel.precision, aa, tx + 2 * halo, ty + 2 * halo) + 4352 > 160 * 1024)
-      return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window does not fit the 160 KiB of LDS");
-  }
-  if (k->mod->geo.indirect && (k->kind == KK_SC_FUSED || k->sc_local_velocity))
-    return fail(SLF_ERR_UNSUPPORTED, "indirect addressing: the binary model runs the reference's pass and its two per-lattice sweeps");
-  if (k->mod->geo.indirect && (k->kind == KK_COLLIDE_AND_PROPAGATE || k->kind == KK_COMPUTE_MACRO ||
-                               k->kind == KK_SET_INITIAL_CONDITIONS || k->kind == KK_SC_MACRO ||
-                               k->kind == KK_SC_SWEEP0 || k->kind == KK_SC_SWEEP1 || k->kind == KK_SC_INIT ||
-                               k->kind == KK_SCS_MACRO || k->kind == KK_SCS_SWEEP))
-    want_p += 1;   // leading `nodes` table (reference _add_indirect_args, subdomain_runner.py:1153-1157)
-  k->alpha_arg = false;
-  if (k->kind == KK_COLLIDE_AND_PROPAGATE && k->mod->sel.model == SLF_ELBM && k->ptrs.size() == want_p + 1 &&
-      fmt[argc - 1] == 'P') {
-    // entropic modules: the alpha field, the LAST argument (reference lb_single.py:129-133: behind the options word)
-    want_p += 1;
-    k->alpha_arg = true;
-  }
-  if (k->kind >= KK_SC3_MACRO && k->kind <= KK_SC3_INIT && (k->ptrs.size() != want_p || k->ints.size() != want_i))
-    return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature: in a module built with simtype = "
-                                 "SLF_SIM_SHAN_CHEN_TERNARY the Shan-Chen kernels and SetInitialConditions take the ternary "
-                                 "argument lists (three lattices; rho, phi, theta)");
-  if (k->ptrs.size() != want_p || k->ints.size() != want_i)
-    return fail(SLF_ERR_INVALID, "argument list does not match the kernel's signature");
+  k->args = b;
   k->pair_rows = k->pair_zc = 0;     // new arguments: slf_kernel_set_pair has to look at them again
   k->needs_iteration = needs_iteration;
   k->bound = true;
-  if (k->kind == KK_COLLIDE_AND_PROPAGATE && k->mod->geo.indirect && !k->ptrs.empty() &&
-      k->mod->phys.incompressible != SLF_DENSITY_ROUNDOFF && !k->mod->phys.regularized && !k->mod->phys.subgrid &&
-      k->mod->sel.model != SLF_ELBM) {
+  if (b.build_slots) {
     // indirect addressing: the sweep is launched over the slots (slot_sweep_kernel); the slot -> node table of this
     // `nodes` argument is built here, once (a launch may be recorded into a graph, where nothing can be allocated)
     SLF_HIP(hipSetDevice(k->mod->ctx->device));
-    slot_table_for(k->mod, (const void*)k->ptrs[0], (hipStream_t)0);
+    slot_table_for(k->mod, b.sweep.nodes, (hipStream_t)0);
   }
   return SLF_OK;
 }
@@ -1845,51 +1345,57 @@ int slf_kernel_set_iteration(slf_kernel* k, uint32_t iteration) {
 
 namespace {
 
-// What the four sweep cases of slf_kernel_launch share.  Each returns SLF_OK or the failure it has recorded.
+// What the sweep cases of slf_kernel_launch share.  Each returns SLF_OK or the failure it has recorded.
 
-// the propagation step of this launch, from the module's access pattern and the kernel's iteration
-int step_prop(const slf_kernel* k, slf::Prop* prop) {
-  *prop = slf::PROP_AB;
+// where and how a sweep runs: the propagation step of this launch, from the module's access pattern and the kernel's
+// iteration, and the rows [y0, y1) x [z0, z1): the region, or all real nodes (whole_box: the kernel takes no region)
+struct SweepShape {
+  slf::Prop prop;
+  int y0, y1, z0, z1;
+};
+int sweep_shape(const slf_kernel* k, const slf_region* region, bool whole_box, SweepShape* sh) {
+  const slf::Geometry& g = k->mod->geo;
+  sh->prop = slf::PROP_AB;
   if (k->mod->access_pattern == SLF_AA) {
     if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-    *prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
+    sh->prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
   }
-  return SLF_OK;
-}
-
-// the rows [y0, y1) x [z0, z1) to sweep: the region, or all real nodes
-int sweep_region(const slf::Geometry& g, const slf_region* region, int* y0, int* y1, int* z0, int* z1) {
-  *y0 = 1; *y1 = g.lat_ny - 1; *z0 = 1; *z1 = g.lat_nz - 1;
-  if (g.dim == 2) { *z0 = 0; *z1 = 1; }
-  if (region) {
-    *y0 = region->y0; *y1 = region->y1;
-    if (g.dim == 3) { *z0 = region->z0; *z1 = region->z1; }
-    if (*y0 < 1 || *y1 > g.lat_ny - 1 || *y0 > *y1 || (g.dim == 3 && (*z0 < 1 || *z1 > g.lat_nz - 1 || *z0 > *z1)))
+  sh->y0 = 1; sh->y1 = g.lat_ny - 1; sh->z0 = 1; sh->z1 = g.lat_nz - 1;
+  if (g.dim == 2) { sh->z0 = 0; sh->z1 = 1; }
+  if (region && !whole_box) {
+    sh->y0 = region->y0; sh->y1 = region->y1;
+    if (g.dim == 3) { sh->z0 = region->z0; sh->z1 = region->z1; }
+    if (sh->y0 < 1 || sh->y1 > g.lat_ny - 1 || sh->y0 > sh->y1 ||
+        (g.dim == 3 && (sh->z0 < 1 || sh->z1 > g.lat_nz - 1 || sh->z0 > sh->z1)))
       return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
   }
   return SLF_OK;
 }
 
-// the module's tables and the options word (first integer argument) into the launch arguments; a.map is set by now
+// the module's tables into the launch arguments; the bound ones (map, options, ...) are in `a` by now
 int sweep_common(const slf_kernel* k, slf::SweepArgs& a) {
   a.node_params = k->mod->node_params;
   a.status = k->mod->status;
-  a.options = (uint32_t)k->ints[0];
   if (k->mod->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+  return SLF_OK;
+}
+
+int nodes_given(const slf_kernel* k) {
+  if (k->mod->geo.indirect && !k->args.sweep.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
   return SLF_OK;
 }
 
 // the launch arguments of a pair sweep (slf_kernel_set_pair) from the bound arguments of a CollideAndPropagate kernel
 void pair_args(const slf_kernel* k, slf::SweepArgs& a) {
   const slf_module* m = k->mod;
-  const int b0 = m->geo.indirect ? 1 : 0;
-  a.nodes = m->geo.indirect ? (const void*)k->ptrs[0] : nullptr;
-  a.map = (const void*)k->ptrs[b0 + 0];
-  a.dist_in = (void*)k->ptrs[b0 + 1];
-  a.dist_out = (void*)k->ptrs[b0 + 2];
+  const slf::SweepArgs& b = k->args.sweep;
+  a.nodes = b.nodes;
+  a.map = b.map;
+  a.dist_in = b.dist_in;
+  a.dist_out = b.dist_out;
   a.node_params = m->node_params;
   a.status = m->status;
-  a.options = (uint32_t)k->ints[0];
+  a.options = b.options;
   for (int f = 0; f < 2; f++) {
     a.xsend[f] = m->xsend[f];
     a.xrecv[f] = m->xrecv[f];
@@ -1900,7 +1406,7 @@ void pair_args(const slf_kernel* k, slf::SweepArgs& a) {
 
 int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk) {
   if (!k) return fail(SLF_ERR_INVALID, "kernel is NULL");
-  if (k->kind != KK_COLLIDE_AND_PROPAGATE)
+  if (k->kind != slf::KK_COLLIDE_AND_PROPAGATE)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: CollideAndPropagate kernels of single-fluid modules only");
   if (!k->bound) return fail(SLF_ERR_INVALID, "pair sweep: set the kernel arguments first (source and destination are checked)");
   if (rows_per_strip < 0 || planes_per_chunk < 0) return fail(SLF_ERR_INVALID, "pair sweep: negative strip / chunk size");
@@ -1920,7 +1426,7 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   const int prefetch = knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch());
   const int xcd_log2 = knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2());
   const int march = knob("SLF_PAIR_MARCH", slf::pair_default_march());
-  if (m->sc.enabled || m->fe.enabled || m->sc3.enabled || m->sel.lattice != SLF_D3Q19 || k->alpha_arg)
+  if (m->sc.enabled || m->fe.enabled || m->sc3.enabled || m->sel.lattice != SLF_D3Q19 || k->args.alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
   slf::SweepArgs a = {};
   pair_args(k, a);
@@ -1939,12 +1445,16 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
   if (!k->bound) return fail(SLF_ERR_INVALID, "kernel arguments not set");
   slf_module* m = k->mod;
   const slf::Geometry& g = m->geo;
+  const slf::KernelKind kk = k->kind;
+  const slf::BoundArgs& b = k->args;
   SLF_HIP(hipSetDevice(m->ctx->device));   // several contexts may live in one process (one per GPU): launch on ours
   hipStream_t s = native(stream);
   hipError_t e = hipSuccess;
-  switch (k->kind) {
-    case KK_COLLIDE_AND_PROPAGATE:
-    case KK_COMPUTE_MACRO: {
+  slf::SweepArgs a = b.sweep;     // the sweeps: the bound arguments, then the module state that may have changed since
+  SweepShape sh;
+  switch (kk) {
+    case slf::KK_COLLIDE_AND_PROPAGATE:
+    case slf::KK_COMPUTE_MACRO: {
       if (k->pair_rows) {
         // two steps per launch: whatever has changed since slf_kernel_set_pair accepted (a body force, face buffers)
         // is an error here, never a quiet single step
@@ -1959,313 +1469,127 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
         }
         break;
       }
-      slf::SweepArgs a = {};
-      const int b0 = g.indirect ? 1 : 0;
-      a.nodes = g.indirect ? (const void*)k->ptrs[0] : nullptr;
-      a.map = (const void*)k->ptrs[b0 + 0];
-      a.dist_in = (void*)k->ptrs[b0 + 1];
-      a.dist_out = (void*)k->ptrs[b0 + 2];
-      a.rho = (void*)k->ptrs[b0 + 3];
-      a.phi = nullptr;
-      a.v[0] = (void*)k->ptrs[b0 + 4];
-      a.v[1] = (void*)k->ptrs[b0 + 5];
-      a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 6] : nullptr;
-      a.alpha = k->alpha_arg ? (void*)k->ptrs.back() : nullptr;
       for (int f = 0; f < 2; f++) {
         a.xsend[f] = m->xsend[f];
         a.xrecv[f] = m->xrecv[f];
       }
       a.rows = m->rows.map ? &m->rows : nullptr;
       if (int rc = sweep_common(k, a)) return rc;
-      if (g.indirect && !a.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
+      if (int rc = nodes_given(k)) return rc;
       // (the slot table is built when the arguments are bound, slf_kernel_set_args: a launch may be part of a graph capture)
-      if (g.indirect && k->kind == KK_COLLIDE_AND_PROPAGATE && m->slots.nodes == a.nodes) a.slots = &m->slots;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      if (k->kind == KK_COMPUTE_MACRO) {
-        e = slf::launch_macro(m->sel, prop, g, m->phys, a, s);
-        break;
-      }
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      e = slf::launch_sweep(m->sel, prop, g, m->phys, a, y0, y1, z0, z1, m->block_x, s);
+      if (g.indirect && kk == slf::KK_COLLIDE_AND_PROPAGATE && m->slots.nodes == a.nodes) a.slots = &m->slots;
+      if (int rc = sweep_shape(k, region, kk == slf::KK_COMPUTE_MACRO, &sh)) return rc;
+      if (kk == slf::KK_COMPUTE_MACRO) e = slf::launch_macro(m->sel, sh.prop, g, m->phys, a, s);
+      else e = slf::launch_sweep(m->sel, sh.prop, g, m->phys, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
       break;
     }
-    case KK_SC_MACRO:
-    case KK_SC_SWEEP0:
-    case KK_SC_SWEEP1: {
-      slf::SweepArgs a = {};
-      const int b0 = g.indirect ? 1 : 0;     // indirect: (nodes, map, dist, dist, rho, phi, v.., options), lb_binary.py:457-465
-      a.nodes = g.indirect ? (const void*)k->ptrs[0] : nullptr;
-      if (g.indirect && !a.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
-      a.map = (const void*)k->ptrs[b0 + 0];
-      a.dist_in = (void*)k->ptrs[b0 + 1];
-      a.dist_out = (void*)k->ptrs[b0 + 2];
-      a.rho = (void*)k->ptrs[b0 + 3];
-      a.phi = (void*)k->ptrs[b0 + 4];
-      a.v[0] = (void*)k->ptrs[b0 + 5];
-      a.v[1] = (void*)k->ptrs[b0 + 6];
-      a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 7] : nullptr;
-      a.sc_local_velocity = k->sc_local_velocity;
+    case slf::KK_SC_MACRO:
+    case slf::KK_SC_SWEEP0:
+    case slf::KK_SC_SWEEP1:
+    case slf::KK_SC_FUSED:
+    case slf::KK_SCS_MACRO:
+    case slf::KK_SCS_SWEEP: {
+      if (int rc = nodes_given(k)) return rc;
       sc_planes_of(m, a);
       if (int rc = sweep_common(k, a)) return rc;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      if (k->kind == KK_SC_MACRO) e = slf::launch_sc_macro(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, s);
-      else e = slf::launch_sc_sweep(m->sel, k->kind == KK_SC_SWEEP0 ? 0 : 1, prop, g, m->phys, m->sc, a, y0, y1, z0, z1,
+      if (int rc = sweep_shape(k, region, kk == slf::KK_SCS_MACRO, &sh)) return rc;
+      if (kk == slf::KK_SC_MACRO) e = slf::launch_sc_macro(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, s);
+      else if (kk == slf::KK_SC_FUSED) e = slf::launch_sc_fused(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
+      else if (kk == slf::KK_SCS_MACRO) e = slf::launch_scs_macro(m->sel, sh.prop, g, m->phys, m->sc, a, s);
+      else if (kk == slf::KK_SCS_SWEEP) e = slf::launch_scs_sweep(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
+      else e = slf::launch_sc_sweep(m->sel, kk == slf::KK_SC_SWEEP0 ? 0 : 1, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1,
                                     m->block_x, s);
       break;
     }
-    case KK_SC_FUSED: {
-      slf::SweepArgs a = {};
-      a.map = (const void*)k->ptrs[0];
-      a.dist_in = (void*)k->ptrs[1];
-      a.dist_out = (void*)k->ptrs[2];
-      a.dist_in2 = (void*)k->ptrs[3];
-      a.dist_out2 = (void*)k->ptrs[4];
-      a.rho = (void*)k->ptrs[5];
-      a.phi = (void*)k->ptrs[6];
-      a.v[0] = (void*)k->ptrs[7];
-      a.v[1] = (void*)k->ptrs[8];
-      a.v[2] = g.dim == 3 ? (void*)k->ptrs[9] : nullptr;
-      a.sc_local_velocity = k->sc_local_velocity;
-      sc_planes_of(m, a);
+    case slf::KK_FE_MACRO:
+    case slf::KK_FE_FLUID:
+    case slf::KK_FE_ORDER: {
       if (int rc = sweep_common(k, a)) return rc;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      e = slf::launch_sc_fused(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, m->block_x, s);
+      if (int rc = sweep_shape(k, region, false, &sh)) return rc;
+      if (kk == slf::KK_FE_MACRO) e = slf::launch_fe_macro(m->sel, sh.prop, g, m->fe, a, sh.y0, sh.y1, sh.z0, sh.z1, s);
+      else e = slf::launch_fe_sweep(m->sel, kk == slf::KK_FE_FLUID ? 0 : 1, sh.prop, g, m->fe, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
       break;
     }
-    case KK_RESIDENT: {
-      slf::SweepArgs a = {};
-      a.map = (const void*)k->ptrs[0];
-      a.node_params = m->node_params;
-      a.status = m->status;
-      a.options = (uint32_t)k->ints[0] & ~1u;       // no field output from inside a stretch of resident steps
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-      const void* src[2] = {(const void*)k->ptrs[1], (const void*)k->ptrs[2]};
-      void* dst[2] = {(void*)k->ptrs[3], (void*)k->ptrs[4]};
-      e = slf::launch_resident(m->sel, m->access_pattern == SLF_AA, g, m->phys, a, src, dst, (int)k->iteration, (int)k->ints[1],
-                               (int)k->ints[2], (int)k->ints[3], (int)k->ints[4], s);
-      break;
-    }
-    case KK_SCS_MACRO:
-    case KK_SCS_SWEEP: {
-      slf::SweepArgs a = {};
-      const int b0 = g.indirect ? 1 : 0;     // indirect: the `nodes` table leads the list (reference _add_indirect_args)
-      a.nodes = g.indirect ? (const void*)k->ptrs[0] : nullptr;
-      if (g.indirect && !a.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
-      a.map = (const void*)k->ptrs[b0 + 0];
-      a.dist_in = (void*)k->ptrs[b0 + 1];
-      a.phi = nullptr;
-      if (k->kind == KK_SCS_MACRO) {
-        a.dist_out = nullptr;
-        a.rho = (void*)k->ptrs[b0 + 2];
-        a.v[0] = a.v[1] = a.v[2] = nullptr;
-      } else {
-        a.dist_out = (void*)k->ptrs[b0 + 2];
-        a.rho = (void*)k->ptrs[b0 + 3];
-        a.v[0] = (void*)k->ptrs[b0 + 4];
-        a.v[1] = (void*)k->ptrs[b0 + 5];
-        a.v[2] = g.dim == 3 ? (void*)k->ptrs[b0 + 6] : nullptr;
-      }
-      sc_planes_of(m, a);
-      if (int rc = sweep_common(k, a)) return rc;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      if (k->kind == KK_SCS_MACRO) {
-        e = slf::launch_scs_macro(m->sel, prop, g, m->phys, m->sc, a, s);
-        break;
-      }
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      e = slf::launch_scs_sweep(m->sel, prop, g, m->phys, m->sc, a, y0, y1, z0, z1, m->block_x, s);
-      break;
-    }
-    case KK_FE_MACRO:
-    case KK_FE_FLUID:
-    case KK_FE_ORDER: {
-      // argument lists of the reference (lb_binary.py:295-308)
-      slf::SweepArgs a = {};
-      a.map = (const void*)k->ptrs[0];
-      a.dist_in = (void*)k->ptrs[1];
-      a.dist_out = (void*)k->ptrs[2];
-      int next = 3;
-      if (k->kind != KK_FE_ORDER) a.rho = (void*)k->ptrs[next++];
-      a.phi = (void*)k->ptrs[next++];
-      if (k->kind != KK_FE_MACRO) {
-        for (int d = 0; d < g.dim; d++) a.v[d] = (void*)k->ptrs[next++];
-        a.lap = (void*)k->ptrs[next++];
-      }
-      if (int rc = sweep_common(k, a)) return rc;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      if (k->kind == KK_FE_MACRO) e = slf::launch_fe_macro(m->sel, prop, g, m->fe, a, y0, y1, z0, z1, s);
-      else e = slf::launch_fe_sweep(m->sel, k->kind == KK_FE_FLUID ? 0 : 1, prop, g, m->fe, a, y0, y1, z0, z1, m->block_x, s);
-      break;
-    }
-    case KK_FE_INIT: {
-      // (map, dist1, dist2, vx, vy[, vz], rho, phi)  -- reference lb_binary.py:107-127
-      const void* v[3] = {(const void*)k->ptrs[3], (const void*)k->ptrs[4], g.dim == 3 ? (const void*)k->ptrs[5] : nullptr};
-      e = slf::launch_fe_init(m->sel, g, m->fe, (void*)k->ptrs[1], (void*)k->ptrs[2], (const void*)k->ptrs[3 + g.dim],
-                              (const void*)k->ptrs[4 + g.dim], v, m->sel.general ? (const void*)k->ptrs[0] : nullptr, s);
-      break;
-    }
-    case KK_SC3_MACRO:
-    case KK_SC3_SWEEP0:
-    case KK_SC3_SWEEP1:
-    case KK_SC3_SWEEP2:
-    case KK_SC3_FUSED: {
-      // argument lists of the reference (lb_ternary.py:220-333); the fused sweep: three (in, out) pairs
-      slf::Sc3Args a = {};
-      a.map = (const void*)k->ptrs[0];
-      int next = 1;
-      if (k->kind == KK_SC3_MACRO) {
-        for (int l = 0; l < 3; l++) a.dist_in[l] = (void*)k->ptrs[next++];
-      } else if (k->kind == KK_SC3_FUSED) {
-        for (int l = 0; l < 3; l++) {
-          a.dist_in[l] = (void*)k->ptrs[next++];
-          a.dist_out[l] = (void*)k->ptrs[next++];
-        }
-      } else {
-        a.dist_in[0] = (void*)k->ptrs[next++];
-        a.dist_out[0] = (void*)k->ptrs[next++];
-      }
-      for (int l = 0; l < 3; l++) a.field[l] = (void*)k->ptrs[next++];
-      for (int d = 0; d < g.dim; d++) a.v[d] = (void*)k->ptrs[next++];
-      a.options = (uint32_t)k->ints[0];
-      if (m->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-      if (!m->sel.general) a.map = nullptr;
-      slf::Prop prop;
-      if (int rc = step_prop(k, &prop)) return rc;
-      int y0, y1, z0, z1;
-      if (int rc = sweep_region(g, region, &y0, &y1, &z0, &z1)) return rc;
-      if (k->kind == KK_SC3_MACRO) e = slf::launch_sc3_macro(m->sel, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1, s);
-      else if (k->kind == KK_SC3_FUSED) e = slf::launch_sc3_fused(m->sel, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1, m->block_x, s);
-      else e = slf::launch_sc3_sweep(m->sel, (int)k->kind - (int)KK_SC3_SWEEP0, prop, g, m->phys, m->sc3, a, y0, y1, z0, z1,
+    case slf::KK_SC3_MACRO:
+    case slf::KK_SC3_SWEEP0:
+    case slf::KK_SC3_SWEEP1:
+    case slf::KK_SC3_SWEEP2:
+    case slf::KK_SC3_FUSED: {
+      slf::Sc3Args a3 = b.sc3;
+      if (m->sel.general && !a3.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+      if (!m->sel.general) a3.map = nullptr;
+      if (int rc = sweep_shape(k, region, false, &sh)) return rc;
+      if (kk == slf::KK_SC3_MACRO) e = slf::launch_sc3_macro(m->sel, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1, s);
+      else if (kk == slf::KK_SC3_FUSED) e = slf::launch_sc3_fused(m->sel, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
+      else e = slf::launch_sc3_sweep(m->sel, (int)kk - (int)slf::KK_SC3_SWEEP0, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1,
                                      m->block_x, s);
       break;
     }
-    case KK_SC3_INIT: {
-      // (map, dist1, dist2, dist3, vx, vy[, vz], rho, phi, theta)  -- reference lb_ternary.py:118-142
-      void* const dist[3] = {(void*)k->ptrs[1], (void*)k->ptrs[2], (void*)k->ptrs[3]};
-      const void* const v[3] = {(const void*)k->ptrs[4], (const void*)k->ptrs[5], g.dim == 3 ? (const void*)k->ptrs[6] : nullptr};
-      const void* const field[3] = {(const void*)k->ptrs[4 + g.dim], (const void*)k->ptrs[5 + g.dim], (const void*)k->ptrs[6 + g.dim]};
-      e = slf::launch_sc3_init(m->sel, g, dist, field, v, s);
+    case slf::KK_RESIDENT: {
+      // dist_in / dist_in2: source a / b, dist_out / dist_out2: destination a / b; the kernel's SweepArgs carry the map only
+      const void* src[2] = {a.dist_in, a.dist_in2};
+      void* dst[2] = {a.dist_out, a.dist_out2};
+      a = slf::SweepArgs{};
+      a.map = b.sweep.map;
+      a.options = b.sweep.options & ~1u;       // no field output from inside a stretch of resident steps
+      if (int rc = sweep_common(k, a)) return rc;
+      e = slf::launch_resident(m->sel, m->access_pattern == SLF_AA, g, m->phys, a, src, dst, (int)k->iteration, (int)b.ints[1],
+                               (int)b.ints[2], (int)b.ints[3], (int)b.ints[4], s);
       break;
     }
-    case KK_SC_INIT: {
-      // ([nodes,] map, dist1, dist2, vx, vy[, vz], rho, phi)  -- reference lb_binary.py:107-127
-      const int b0 = g.indirect ? 1 : 0;
-      if (g.indirect && !k->ptrs[0]) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
-      const void* v[3] = {(const void*)k->ptrs[b0 + 3], (const void*)k->ptrs[b0 + 4],
-                          g.dim == 3 ? (const void*)k->ptrs[b0 + 5] : nullptr};
-      e = slf::launch_sc_init(m->sel, g, m->phys, (void*)k->ptrs[b0 + 1], (void*)k->ptrs[b0 + 2],
-                              (const void*)k->ptrs[b0 + 3 + g.dim], (const void*)k->ptrs[b0 + 4 + g.dim], v,
-                              g.indirect ? (const void*)k->ptrs[0] : nullptr, s);
+    // the initial conditions: (dist.., v.., rho[, phi[, theta]]) in the order of the reference (lb_single.py:72-94,
+    // lb_binary.py:107-127, lb_ternary.py:118-142)
+    case slf::KK_SET_INITIAL_CONDITIONS:
+      if (int rc = nodes_given(k)) return rc;
+      e = slf::launch_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, a.nodes, s);
       break;
-    }
-    case KK_SET_INITIAL_CONDITIONS: {
-      // (dist, vx, vy[, vz], rho, map)  -- reference lb_single.py:72-94
-      const int b0 = g.indirect ? 1 : 0;   // indirect: (nodes, dist, v.., rho, map)
-      const void* v[3] = {(const void*)k->ptrs[b0 + 1], (const void*)k->ptrs[b0 + 2],
-                          g.dim == 3 ? (const void*)k->ptrs[b0 + 3] : nullptr};
-      if (g.indirect && !k->ptrs[0]) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
-      e = slf::launch_init(m->sel, g, m->phys, (void*)k->ptrs[b0 + 0], (const void*)k->ptrs[b0 + 1 + g.dim], v,
-                           g.indirect ? (const void*)k->ptrs[0] : nullptr, s);
+    case slf::KK_SC_INIT:
+      if (int rc = nodes_given(k)) return rc;
+      e = slf::launch_sc_init(m->sel, g, m->phys, a.dist_in, a.dist_in2, a.rho, a.phi, a.v, a.nodes, s);
       break;
-    }
-    case KK_PBC:
-    case KK_PBC_SWAP:
-      e = slf::launch_pbc(m->sel, g, (void*)k->ptrs[0], (int)k->ints[0], k->kind == KK_PBC_SWAP, s);
+    case slf::KK_FE_INIT:
+      e = slf::launch_fe_init(m->sel, g, m->fe, a.dist_in, a.dist_in2, a.rho, a.phi, a.v, m->sel.general ? a.map : nullptr, s);
       break;
-    case KK_MACRO_PBC:
-      e = slf::launch_macro_pbc(m->sel, g, (void*)k->ptrs[0], (int)k->ints[0], s);
+    case slf::KK_SC3_INIT:
+      e = slf::launch_sc3_init(m->sel, g, b.sc3.dist_in, b.sc3.field, b.sc3.v, s);
       break;
-    case KK_COLLECT_BOX:
-    case KK_DISTRIBUTE_BOX:
-      if (k->ints.size() >= 6) {
+    case slf::KK_PBC:
+    case slf::KK_PBC_SWAP:
+      e = slf::launch_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], kk == slf::KK_PBC_SWAP, s);
+      break;
+    case slf::KK_MACRO_PBC:
+      e = slf::launch_macro_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], s);
+      break;
+    case slf::KK_COLLECT_BOX:
+    case slf::KK_DISTRIBUTE_BOX:
+      if (b.n_ints >= 6) {
         int dirs[32], nd = 0;
-        for (int q = 0; q < 32; q++) if (((unsigned int)k->ints[0] >> q) & 1u) dirs[nd++] = q;    // ascending
+        for (int q = 0; q < 32; q++) if (((unsigned int)b.ints[0] >> q) & 1u) dirs[nd++] = q;    // ascending
         if (nd > 12) return fail(SLF_ERR_INVALID, "Collect/DistributeContinuousData: at most 12 directions per launch (a face of D3Q19 carries 5)");
-        e = slf::launch_box(m->sel, g, k->kind == KK_COLLECT_BOX, (void*)k->ptrs[0], (void*)k->ptrs[1], dirs, nd,
-                            (unsigned long long)(uint32_t)k->ints[1], (long long)k->ints[2], (int)k->ints[3],
-                            (long long)k->ints[4], (int)k->ints[5], k->ints.size() == 8 ? (long long)k->ints[6] : 0,
-                            k->ints.size() == 8 ? (long long)k->ints[7] : 0, false, s);
+        e = slf::launch_box(m->sel, g, kk == slf::KK_COLLECT_BOX, (void*)b.ptrs[0], (void*)b.ptrs[1], dirs, nd,
+                            (unsigned long long)(uint32_t)b.ints[1], (long long)b.ints[2], (int)b.ints[3],
+                            (long long)b.ints[4], (int)b.ints[5], b.n_ints == 8 ? (long long)b.ints[6] : 0,
+                            b.n_ints == 8 ? (long long)b.ints[7] : 0, false, s);
         break;
       }
-      [[fallthrough]];
-    case KK_COLLECT_FACE_SWAP:
-    case KK_DISTRIBUTE_FACE_SWAP:
-    case KK_COLLECT_MACRO_FACE:
-    case KK_DISTRIBUTE_MACRO_FACE: {
-      // The reference's face kernels (kernel_utils.mako:476-953), mapped onto the box kernel.  face: 2 Y_LOW, 3 Y_HIGH,
-      // 4 Z_LOW, 5 Z_HIGH (subdomain.py:30-36); the layer a kernel reads / writes is lat_linear / lat_linear_macro /
-      // lat_linear_dist / lat_linear_with_swap of subdomain_runner.py:486-510; the populations are
-      // get_interblock_dists(grid, normal(face)) in ascending order -- their opposite slots in the ...WithSwap kernels --
-      // buffer [k][other][x] (2-D: [k][x]).
-      const bool collect = k->kind == KK_COLLECT_BOX || k->kind == KK_COLLECT_FACE_SWAP || k->kind == KK_COLLECT_MACRO_FACE;
-      const bool swap = k->kind == KK_COLLECT_FACE_SWAP || k->kind == KK_DISTRIBUTE_FACE_SWAP;
-      const bool macro = k->kind == KK_COLLECT_MACRO_FACE || k->kind == KK_DISTRIBUTE_MACRO_FACE;
-      int face, base_gx, base_other = 0, max_lx, max_other = 1, layer = -1;
-      if (g.dim == 3) {
-        face = (int)k->ints[0]; base_gx = (int)k->ints[1]; base_other = (int)k->ints[2];
-        max_lx = (int)k->ints[3]; max_other = (int)k->ints[4];
-      } else if (macro) {
-        face = 2; base_gx = (int)k->ints[0]; max_lx = (int)k->ints[1]; layer = (int)k->ints[2];
-      } else {
-        face = (int)k->ints[0]; base_gx = (int)k->ints[1]; max_lx = (int)k->ints[2];
-      }
-      if (face < 2 || face >= 2 * g.dim) return fail(SLF_ERR_INVALID, "face must be a Y or Z face (X faces travel through index lists / x-face buffers)");
-      const int axis = face >> 1;
-      const bool low = (face & 1) == 0;
-      const int lat = axis == 1 ? g.lat_ny : g.lat_nz;
-      if (layer < 0) {
-        if (macro) layer = collect ? (low ? 1 : lat - 2) : (low ? 0 : lat - 1);             // lat_linear_macro / lat_linear
-        else if (collect) layer = swap ? (low ? 1 : lat - 2) : (low ? 0 : lat - 1);        // lat_linear_macro / lat_linear
-        else layer = swap ? (low ? lat - 1 : 0) : (low ? lat - 2 : 1);                     // lat_linear_with_swap / lat_linear_dist
-      }
-      int dirs[32], nd = 0;
-      if (macro) {
-        dirs[nd++] = 0;
-      } else {
-        const int sign = low ? -1 : 1;
-        for (int q = 1; q < (g.dim == 3 ? 19 : 9); q++) {
-          const int ea = g.dim == 3 ? slf::e_comp<slf::D3Q19>(q, axis) : slf::e_comp<slf::D2Q9>(q, axis);
-          if (ea == sign) dirs[nd++] = swap ? (g.dim == 3 ? slf::D3Q19::opp(q) : slf::D2Q9::opp(q)) : q;
-        }
-      }
-      int ncols, nrows;
-      if (g.dim == 3) {
-        if (max_other % nd) return fail(SLF_ERR_INVALID, "max_other must be a multiple of the number of populations that cross the face");
-        ncols = max_lx; nrows = max_other / nd;
-      } else {
-        if (!macro && max_lx % nd) return fail(SLF_ERR_INVALID, "max_lx must be a multiple of the number of populations that cross the face");
-        ncols = macro ? max_lx : max_lx / nd; nrows = 1;
-      }
-      const long long row_stride = axis == 1 ? (long long)g.arr_nxy : (long long)g.arr_nx;   // rows run along the other axis
-      const unsigned long long base = (unsigned long long)base_gx +
-          (axis == 1 ? (unsigned long long)g.arr_nx * layer + (unsigned long long)g.arr_nxy * base_other
-                     : (unsigned long long)g.arr_nx * base_other + (unsigned long long)g.arr_nxy * layer);
-      const int lat_other = g.dim == 3 ? (axis == 1 ? g.lat_nz : g.lat_ny) : 1;       // extent along the rows' axis
-      if (base_gx < 0 || base_gx + ncols > g.arr_nx || base_other < 0 || base_other + nrows > lat_other || layer < 0 || layer >= lat)
-        return fail(SLF_ERR_INVALID, "face box outside the subdomain (base_gx + max_lx, base_other + rows or the layer exceed the arrays)");
+      [[fallthrough]];      // the reference's own argument list
+    case slf::KK_COLLECT_FACE_SWAP:
+    case slf::KK_DISTRIBUTE_FACE_SWAP:
+    case slf::KK_COLLECT_MACRO_FACE:
+    case slf::KK_DISTRIBUTE_MACRO_FACE: {
+      slf::FaceBox box;
+      const char* why = nullptr;
+      if (int rc = slf::face_box(g, kk, b.ints, &box, &why)) return fail(rc, why);
       slf::Geometry gm = g;
-      if (macro) gm.dist_size = 0;
-      e = slf::launch_box(m->sel, gm, collect, (void*)k->ptrs[0], (void*)k->ptrs[1], dirs, nd, base, 1, ncols, row_stride, nrows,
-                          0, 0, macro, s);
+      if (box.macro) gm.dist_size = 0;
+      e = slf::launch_box(m->sel, gm, box.collect, (void*)b.ptrs[0], (void*)b.ptrs[1], box.dirs, box.nd, box.base, 1, box.ncols,
+                          box.row_stride, box.nrows, 0, 0, box.macro, s);
       break;
     }
-    case KK_COLLECT_SPARSE:
-    case KK_DISTRIBUTE_SPARSE:
-      e = slf::launch_sparse(m->sel, k->kind == KK_COLLECT_SPARSE, (const unsigned long long*)k->ptrs[0],
-                             (void*)k->ptrs[1], (void*)k->ptrs[2], (int)k->ints[0], s);
+    case slf::KK_COLLECT_SPARSE:
+    case slf::KK_DISTRIBUTE_SPARSE:
+      e = slf::launch_sparse(m->sel, kk == slf::KK_COLLECT_SPARSE, (const unsigned long long*)b.ptrs[0],
+                             (void*)b.ptrs[1], (void*)b.ptrs[2], (int)b.ints[0], s);
       break;
   }
   if (e != hipSuccess) return hip_fail(e, "kernel launch");

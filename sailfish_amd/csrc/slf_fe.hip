@@ -391,14 +391,4 @@ hipError_t launch_fe_init(const KernelSelector& sel, const Geometry& g, const Fr
   });
 }
 
-// The names of this family (C ABI slf_kernel_get): index = which kernel
-int fe_kernel_index(const char* name) {
-  static const char* const names[] = {"FreeEnergyPrepareMacroFields", "FreeEnergyCollideAndPropagateFluid",
-                                      "FreeEnergyCollideAndPropagateOrderParam"};
-  for (int i = 0; i < 3; i++) {
-    if (!strcmp(names[i], name)) return i;
-  }
-  return -1;
-}
-
 }  // namespace slf

@@ -234,8 +234,6 @@ hipError_t launch_fe_sweep(const KernelSelector& sel, int which, Prop prop, cons
                            const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
 hipError_t launch_fe_init(const KernelSelector& sel, const Geometry& g, const FreeEnergy& fe, void* dist1, void* dist2,
                           const void* rho, const void* phi, const void* const v[3], const void* map, hipStream_t s);
-// 0 / 1 / 2: FreeEnergyPrepareMacroFields / ...CollideAndPropagateFluid / ...CollideAndPropagateOrderParam, -1: none of them
-int fe_kernel_index(const char* name);
 
 // ---- ternary Shan-Chen mixture (slf_sc3.hip) ----
 // pass in front: a.dist_in[0..2] (read) -> a.field[0..2], a.v
@@ -249,8 +247,6 @@ hipError_t launch_sc3_fused(const KernelSelector& sel, Prop prop, const Geometry
                             const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
 hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* const dist[3], const void* const field[3],
                            const void* const v[3], hipStream_t s);
-// 0: ShanChenCollideAndPropagate2 (the name only this family has), -1: not one of them
-int sc3_kernel_index(const char* name);
 
 // ---- several steps inside one launch (slf_resident.hip): 2-D lattices ----
 // src / dst: the raw distribution arrays ([0] = the array of the in-place pattern / copy A of the two-copy pattern, [1] =

@@ -380,14 +380,4 @@ hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* c
   });
 }
 
-// The names only this family has (C ABI slf_kernel_get); the names it shares with the binary model take the ternary
-// argument lists in a ternary module (slf_api.hip)
-int sc3_kernel_index(const char* name) {
-  static const char* const names[] = {"ShanChenCollideAndPropagate2"};
-  for (int i = 0; i < 1; i++) {
-    if (!strcmp(names[i], name)) return i;
-  }
-  return -1;
-}
-
 }  // namespace slf

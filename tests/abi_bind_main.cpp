@@ -1,0 +1,377 @@
+// Walks the host logic of the C ABI (sailfish_amd/csrc/slf_bind.h) on the CPU and prints one line per case:
+//   section \t subject \t configuration \t try \t code \t message \t detail
+// tests/test_abi_bind.py builds it with AddressSanitizer and UBSan, runs it and compares the lines with
+// tests/golden/abi_binding.json.  Nothing here touches a GPU.
+#include <stdio.h>
+
+#include <string>
+#include <vector>
+
+#include "slf_bind.h"
+
+namespace {
+
+struct Config {
+  std::string name;
+  slf_module_desc desc;
+  slf::ModuleConfig cfg;
+  int code;
+};
+
+void line(const char* section, const std::string& subject, const std::string& config, const std::string& what, int code,
+          const std::string& message, const std::string& detail) {
+  printf("%s\t%s\t%s\t%s\t%d\t%s\t%s\n", section, subject.c_str(), config.c_str(), what.c_str(), code, message.c_str(),
+         detail.c_str());
+}
+
+std::string num(double v) {
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
+}
+template <class T>
+std::string list(const T* v, int n) {
+  std::string s = "[";
+  for (int i = 0; i < n; i++) s += (i ? "," : "") + num((double)v[i]);
+  return s + "]";
+}
+
+// every field of the structs a module is configured with
+std::string dump(const slf::ModuleConfig& c) {
+  const slf::Geometry& g = c.geo;
+  const slf::Physics& p = c.phys;
+  std::string s;
+  s += "sel=" + num(c.sel.lattice) + "," + num(c.sel.model) + "," + num(c.sel.precision) + "," + num(c.sel.general);
+  s += " access=" + num(c.access_pattern) + " block_x=" + num(c.block_x) + " n_node_params=" + num(c.n_node_params);
+  s += " geo: dim=" + num(g.dim) + " lat=" + num(g.lat_nx) + "," + num(g.lat_ny) + "," + num(g.lat_nz) + " arr=" + num(g.arr_nx) +
+       "," + num(g.arr_ny) + "," + num(g.arr_nz) + "," + num(g.arr_nxy) + " dist_size=" + num(g.dist_size) + " wrap=" + list(g.wrap, 3) +
+       " axis_mode=" + list(g.axis_mode, 3) + " type_mask=" + num(g.type_mask) + " param=" + num(g.param_shift) + "," +
+       num(g.param_mask) + " orient_shift=" + num(g.orient_shift) + " type_lut=" + std::to_string(g.type_lut) + " link_tags=" +
+       num(g.use_link_tags) + " variant=" + num(g.variant) + " indirect=" + num(g.indirect) + " bc_level=" + num(g.bc_level) +
+       " x_ghost_unused=" + num(g.x_ghost_unused);
+  s += " phys: tau=" + num(p.tau) + " visc=" + num(p.visc) + " accel=" + list(p.accel, 3) + " mrt=" + list(p.mrt_rates, 27) +
+       " incompressible=" + num(p.incompressible) + " has_force=" + num(p.has_force) + " relax=" + num(p.relaxation_enabled) +
+       " edm=" + num(p.force_edm) + " regularized=" + num(p.regularized) + " subgrid=" + num(p.subgrid) + "," +
+       num(p.smagorinsky_const) + " entropic=" + num(p.entropic_equilibrium) + "," + num(p.entropy_tolerance) + "," +
+       num(p.alpha_tolerance) + " tms_mask=" + num(p.tms_mask);
+  s += " sc: " + num(c.sc.enabled) + " tau_phi=" + num(c.sc.tau_phi) + " G=" + list(c.sc.G, 4) + " potential=" + num(c.sc.potential) +
+       " accel1=" + list(c.sc.accel1, 3);
+  s += " fe: " + num(c.fe.enabled) + " " + num(c.fe.Gamma) + "," + num(c.fe.kappa) + "," + num(c.fe.A) + " tau=" + num(c.fe.tau_a) + "," +
+       num(c.fe.tau_b) + "," + num(c.fe.tau_phi) + " wall=" + num(c.fe.wall_phase) + "," + num(c.fe.wall_order) + " rim=" + list(c.fe.rim, 3);
+  s += " sc3: " + num(c.sc3.enabled) + " tau=" + num(c.sc3.tau_phi) + "," + num(c.sc3.tau_theta) + " G=" + list(c.sc3.G, 9) +
+       " potential=" + num(c.sc3.potential) + " accel1=" + list(c.sc3.accel1, 3) + " accel2=" + list(c.sc3.accel2, 3);
+  return s;
+}
+
+// A valid descriptor: 6 x 5 (x 4) nodes, rows padded to 8; fluid, ghost, unused, propagation-only and full-way bounce-back nodes
+slf_module_desc base_desc(int lattice, int access, int simtype, int model, int addressing) {
+  static const double params[3] = {0.5, 0.25, 0.125};
+  slf_module_desc d = {};
+  d.struct_size = sizeof(slf_module_desc);
+  d.lattice = lattice; d.model = model; d.precision = 4; d.access_pattern = access;
+  d.lat_nx = 6; d.lat_ny = 5; d.lat_nz = lattice == SLF_D3Q19 ? 4 : 1;
+  d.arr_nx = 8; d.arr_ny = 5; d.arr_nz = d.lat_nz;
+  d.envelope = 1;
+  d.relaxation_enabled = 1;
+  d.tau = 0.8; d.visc = 0.1;
+  d.nt_type_mask = 7; d.nt_misc_shift = 3; d.nt_param_shift = 2; d.nt_scratch_shift = 1;
+  d.n_types = 5;
+  for (int i = 0; i < 5; i++) d.type_kind[i] = i;
+  d.n_node_params = 3; d.node_params = params;
+  d.simtype = simtype;
+  d.tau_phi = 0.9;
+  d.sc_G[0] = 0.1; d.sc_G[1] = 1.2; d.sc_G[2] = 1.2; d.sc_G[3] = 0.2;
+  d.node_addressing = addressing;
+  d.dist_stride = addressing == SLF_ADDR_INDIRECT ? 100 : 0;
+  d.fe_Gamma = 0.5; d.fe_kappa = 0.04; d.fe_A = 0.03; d.fe_tau_a = 0.9; d.fe_tau_b = 0.7;
+  d.bc_wall_grad_phase = 0.1; d.bc_wall_grad_order = 1;
+  d.tau_theta = 1.1;
+  for (int i = 0; i < 9; i++) d.sc3_G[i] = 0.1 * (i + 1);
+  d.entropy_tolerance = 1e-6; d.alpha_tolerance = 1e-10;
+  if (model == SLF_MRT) for (int i = 0; i < 19; i++) d.mrt_rates[i] = 1.0 + 0.01 * i;
+  return d;
+}
+
+std::vector<Config> all_configs() {
+  std::vector<Config> out;
+  auto add = [&out](const std::string& name, const slf_module_desc& d) { out.push_back(Config{name, d, {}, 0}); };
+  struct Fam { const char* name; int simtype, model; bool indirect; };
+  const Fam fams[] = {{"bgk", SLF_SIM_LBM, SLF_BGK, true}, {"mrt", SLF_SIM_LBM, SLF_MRT, true}, {"elbm", SLF_SIM_LBM, SLF_ELBM, true},
+                      {"sc2", SLF_SIM_SHAN_CHEN_BINARY, SLF_BGK, true}, {"scs", SLF_SIM_SHAN_CHEN_SINGLE, SLF_BGK, true},
+                      {"fe", SLF_SIM_FREE_ENERGY, SLF_BGK, false}, {"sc3", SLF_SIM_SHAN_CHEN_TERNARY, SLF_BGK, false}};
+  for (const Fam& f : fams)
+    for (int lattice : {SLF_D2Q9, SLF_D3Q19})
+      for (int access : {SLF_AB, SLF_AA})
+        for (int addr : {SLF_ADDR_DIRECT, SLF_ADDR_INDIRECT}) {
+          if (addr == SLF_ADDR_INDIRECT && !f.indirect) continue;
+          add(std::string(f.name) + (lattice == SLF_D2Q9 ? "-d2q9" : "-d3q19") + (access == SLF_AB ? "-ab" : "-aa") +
+                  (addr == SLF_ADDR_DIRECT ? "-direct" : "-indirect"), base_desc(lattice, access, f.simtype, f.model, addr));
+        }
+  // valid modules in which CollideAndPropagateResident does not exist (3-D: above)
+  slf_module_desc d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.regularized = 1; add("resident-regularized", d);
+  d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.incompressible = SLF_DENSITY_ROUNDOFF; add("resident-roundoff", d);
+  d = base_desc(SLF_D2Q9, SLF_AA, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.periodic_local[1] = 1; add("resident-ghost-periodic", d);
+  d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.n_types = 6; d.type_kind[5] = SLF_NK_HALF_BB; add("resident-half-bb", d);
+  d = base_desc(SLF_D2Q9, SLF_AA, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.periodic_fused[0] = d.periodic_fused[1] = 1; d.fluid_only = 1; d.n_types = 0; d.has_force = 1; d.accel[0] = 1e-5;
+  d.force_implementation = SLF_FORCE_EDM; d.sparse_geometry = 1; d.use_link_tags = 1; add("bgk-d2q9-aa-fused-fluid-only", d);
+  d = base_desc(SLF_D3Q19, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+  d.n_types = 8; d.type_kind[5] = SLF_NK_WALL_TMS; d.type_kind[6] = SLF_NK_ZOUHE_VELOCITY; d.type_kind[7] = SLF_NK_YU_OUTFLOW;
+  d.subgrid = SLF_SUBGRID_LES_SMAGORINSKY; d.smagorinsky_const = 0.1; d.lat_nx = 2000; d.arr_nx = 2048; add("bgk-d3q19-ab-les-tms-long-rows", d);
+
+  // every refusal of the descriptor
+  const int B = SLF_BGK, LBM = SLF_SIM_LBM, DIR = SLF_ADDR_DIRECT, IND = SLF_ADDR_INDIRECT;
+#define REFUSAL(name, lattice, access, simtype, model, addr, change) \
+  d = base_desc(lattice, access, simtype, model, addr);              \
+  change;                                                            \
+  add("refuse-" name, d);
+  REFUSAL("struct-size", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.struct_size -= 4)
+  REFUSAL("lattice", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.lattice = 7)
+  REFUSAL("model", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.model = 7)
+  REFUSAL("precision", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.precision = 2)
+  REFUSAL("access", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.access_pattern = 2)
+  REFUSAL("envelope", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.envelope = 2)
+  REFUSAL("size-small", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.lat_ny = 2)
+  REFUSAL("size-2d-nz", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.lat_nz = d.arr_nz = 3)
+  REFUSAL("size-3d-nz", SLF_D3Q19, SLF_AB, LBM, B, DIR, d.lat_nz = 2)
+  REFUSAL("padding", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.arr_nx = 5)
+  REFUSAL("tau", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.tau = 0.5)
+  REFUSAL("n-types", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.n_types = 17)
+  REFUSAL("n-types-negative", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.n_types = -1)
+  REFUSAL("too-large", SLF_D3Q19, SLF_AB, LBM, B, DIR, (d.lat_nx = d.arr_nx = 2048, d.lat_ny = d.arr_ny = 2048, d.lat_nz = d.arr_nz = 1024))
+  REFUSAL("stride-too-large", SLF_D3Q19, SLF_AB, LBM, B, DIR, d.dist_stride = 0xFFFFFFFFull)
+  REFUSAL("addressing", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.node_addressing = 2)
+  REFUSAL("indirect-fluid-only", SLF_D2Q9, SLF_AB, LBM, B, IND, d.fluid_only = 1)
+  REFUSAL("indirect-simtype", SLF_D2Q9, SLF_AB, LBM, B, IND, d.simtype = 9)
+  REFUSAL("indirect-no-stride", SLF_D2Q9, SLF_AB, LBM, B, IND, d.dist_stride = 0)
+  REFUSAL("stride-small", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.dist_stride = 39)
+  REFUSAL("node-kind", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.type_kind[2] = 17)
+  REFUSAL("node-kind-negative", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.type_kind[2] = -1)
+  REFUSAL("copy-aa", SLF_D2Q9, SLF_AA, LBM, B, DIR, d.type_kind[4] = SLF_NK_COPY)
+  REFUSAL("yu-outflow-aa", SLF_D3Q19, SLF_AA, LBM, B, DIR, d.type_kind[4] = SLF_NK_YU_OUTFLOW)
+  REFUSAL("do-nothing-aa-indirect", SLF_D2Q9, SLF_AA, LBM, B, IND, d.type_kind[4] = SLF_NK_DO_NOTHING)
+  REFUSAL("edm-mrt", SLF_D2Q9, SLF_AB, LBM, SLF_MRT, DIR, d.force_implementation = SLF_FORCE_EDM)
+  REFUSAL("subgrid-value", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.subgrid = 2)
+  REFUSAL("regularized-mrt", SLF_D2Q9, SLF_AB, LBM, SLF_MRT, DIR, d.regularized = 1)
+  REFUSAL("regularized-sc2", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_BINARY, B, DIR, d.regularized = 1)
+  REFUSAL("subgrid-roundoff", SLF_D2Q9, SLF_AB, LBM, B, DIR, (d.subgrid = 1, d.smagorinsky_const = 0.1, d.incompressible = 2))
+  REFUSAL("subgrid-edm", SLF_D2Q9, SLF_AB, LBM, B, DIR, (d.subgrid = 1, d.smagorinsky_const = 0.1, d.force_implementation = 1))
+  REFUSAL("subgrid-constant", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.subgrid = 1)
+  REFUSAL("tms-fluid-only", SLF_D2Q9, SLF_AB, LBM, B, DIR, (d.type_kind[4] = SLF_NK_WALL_TMS, d.fluid_only = 1))
+  REFUSAL("entropic-equilibrium-bgk", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.entropic_equilibrium = 1)
+  REFUSAL("elbm-rates", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, d.mrt_rates[3] = 1.0)
+  REFUSAL("elbm-sc2", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_BINARY, SLF_ELBM, DIR, (void)0)
+  REFUSAL("elbm-roundoff", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, d.incompressible = 2)
+  REFUSAL("elbm-incompressible-entropic", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, (d.incompressible = 1, d.entropic_equilibrium = 1))
+  REFUSAL("elbm-force", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, d.has_force = 1)
+  REFUSAL("elbm-entropy-tolerance", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, d.entropy_tolerance = 0.0)
+  REFUSAL("elbm-alpha-tolerance", SLF_D2Q9, SLF_AB, LBM, SLF_ELBM, DIR, d.alpha_tolerance = -1.0)
+  REFUSAL("roundoff-mrt", SLF_D2Q9, SLF_AB, LBM, SLF_MRT, DIR, d.incompressible = 2)
+  REFUSAL("roundoff-node-kind", SLF_D2Q9, SLF_AB, LBM, B, DIR, (d.incompressible = 2, d.type_kind[4] = SLF_NK_ZOUHE_VELOCITY))
+  REFUSAL("density-model", SLF_D2Q9, SLF_AB, LBM, B, DIR, d.incompressible = 3)
+  REFUSAL("sc2-mrt", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_BINARY, SLF_MRT, DIR, (void)0)
+  REFUSAL("sc2-tau-phi", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_BINARY, B, DIR, d.tau_phi = 0.5)
+  REFUSAL("sc2-node-kind", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_BINARY, B, DIR, d.type_kind[4] = SLF_NK_HALF_BB)
+  REFUSAL("scs-node-kind", SLF_D3Q19, SLF_AA, SLF_SIM_SHAN_CHEN_SINGLE, B, DIR, d.type_kind[4] = SLF_NK_EQUILIBRIUM_DENSITY)
+  REFUSAL("fe-mrt", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, SLF_MRT, DIR, (void)0)
+  REFUSAL("fe-force", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.has_force = 1)
+  REFUSAL("fe-accel1", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.accel1[1] = 1e-5)
+  REFUSAL("fe-indirect", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, IND, (void)0)
+  REFUSAL("fe-incompressible", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.incompressible = 1)
+  REFUSAL("fe-tau", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.fe_tau_b = 0.5)
+  REFUSAL("fe-wall-order", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.bc_wall_grad_order = 3)
+  REFUSAL("fe-rim", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.fe_zero_grad_rim[1] = 3)
+  REFUSAL("fe-half-bb", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.type_kind[4] = SLF_NK_HALF_BB)
+  REFUSAL("fe-node-kind", SLF_D2Q9, SLF_AB, SLF_SIM_FREE_ENERGY, B, DIR, d.type_kind[4] = SLF_NK_ZOUHE_DENSITY)
+  REFUSAL("sc3-mrt", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, SLF_MRT, DIR, (void)0)
+  REFUSAL("sc3-indirect", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, IND, (void)0)
+  REFUSAL("sc3-incompressible", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.incompressible = 1)
+  REFUSAL("sc3-tau", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.tau_theta = 0.5)
+  REFUSAL("sc3-potential", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.sc_potential = 2)
+  REFUSAL("sc3-node-kind", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.type_kind[4] = SLF_NK_HALF_BB)
+#undef REFUSAL
+  return out;
+}
+
+// ---- binding ---------------------------------------------------------------------------------------------------------
+struct Call {
+  std::string fmt;
+  int argc;
+};
+
+std::string arg_of(const void* p) {          // pointer argument i carries 0x1000 * (i + 1)
+  const unsigned long long v = (unsigned long long)p;
+  return v ? std::to_string(v / 0x1000 - 1) : "-";
+}
+
+std::string dump(const slf::BoundArgs& b) {
+  const slf::SweepArgs& a = b.sweep;
+  const slf::Sc3Args& t = b.sc3;
+  std::string s = "sweep: nodes=" + arg_of(a.nodes) + " map=" + arg_of(a.map) + " dist_in=" + arg_of(a.dist_in) + " dist_out=" +
+                  arg_of(a.dist_out) + " dist_in2=" + arg_of(a.dist_in2) + " dist_out2=" + arg_of(a.dist_out2) + " rho=" + arg_of(a.rho) +
+                  " phi=" + arg_of(a.phi) + " v=" + arg_of(a.v[0]) + "," + arg_of(a.v[1]) + "," + arg_of(a.v[2]) + " alpha=" +
+                  arg_of(a.alpha) + " lap=" + arg_of(a.lap) + " options=" + num(a.options) + " local_velocity=" + num(a.sc_local_velocity);
+  s += " sc3: map=" + arg_of(t.map);
+  for (int l = 0; l < 3; l++) s += " in" + num(l) + "=" + arg_of(t.dist_in[l]) + " out" + num(l) + "=" + arg_of(t.dist_out[l]);
+  s += " field=" + arg_of(t.field[0]) + "," + arg_of(t.field[1]) + "," + arg_of(t.field[2]) + " v=" + arg_of(t.v[0]) + "," +
+       arg_of(t.v[1]) + "," + arg_of(t.v[2]) + " options=" + num(t.options);
+  s += " ptrs=[";
+  for (int i = 0; i < b.n_ptrs && i < slf::MAX_BOUND_PTRS; i++) s += (i ? "," : "") + arg_of((const void*)b.ptrs[i]);
+  s += "] ints=" + list(b.ints, b.n_ints < slf::MAX_BOUND_INTS ? b.n_ints : slf::MAX_BOUND_INTS) + " n=" + num(b.n_ptrs) + "," + num(b.n_ints) +
+       " alpha_arg=" + num(b.alpha_arg) + " build_slots=" + num(b.build_slots);
+  return s;
+}
+
+// the argument list the table holds for this name and kind
+const slf::KernelRow* signature_of(const char* name, slf::KernelKind kind) {
+  for (const slf::KernelRow& r : slf::KERNEL_TABLE)
+    if (!strcmp(r.name, name) && r.kind == kind) return &r;
+  return nullptr;
+}
+
+std::vector<std::pair<std::string, Call>> calls_for(const slf::ModuleConfig& c, const slf::KernelRow& sig) {
+  const int dim = c.geo.dim;
+  std::string exact;
+  if (slf::is_face_kind(sig.kind)) {
+    exact = dim == 3 ? "PiiiiiP" : "PiiiP";
+  } else {
+    if (c.geo.indirect && sig.nodes_in_front) exact += 'P';
+    for (const char* s = sig.slots; *s; s++) exact += std::string(*s == 'v' ? dim : 1, 'P');
+    exact += std::string(sig.n_ints == slf::BOX_INTS ? 6 : sig.n_ints, 'i');
+  }
+  const int n = (int)exact.size();
+  std::vector<std::pair<std::string, Call>> calls;
+  calls.push_back({"exact", {exact, n}});
+  std::string s = exact;
+  s.erase(s.rfind('P'), 1);
+  calls.push_back({"pointer-fewer", {s, n - 1}});
+  calls.push_back({"pointer-more", {exact + "P", n + 1}});            // entropic CollideAndPropagate: the alpha field
+  calls.push_back({"two-pointers-more", {exact + "PP", n + 2}});
+  calls.push_back({"int-more", {exact + "i", n + 1}});
+  s = exact;
+  s[0] = 'f';
+  calls.push_back({"bad-format-char", {s, n}});
+  calls.push_back({"argc-short", {exact, n - 1}});
+  std::string ints_first, ptrs_last;
+  for (char ch : exact) (ch == 'i' ? ints_first : ptrs_last) += ch;
+  calls.push_back({"ints-first", {ints_first + ptrs_last, n}});
+  calls.push_back({"pointers-first", {ptrs_last + ints_first, n}});
+  calls.push_back({"thirty-pointers", {std::string(30, 'P'), 30}});
+  if (slf::is_box_kind(sig.kind)) {
+    calls.push_back({"box-8-ints", {"PPiiiiiiii", 10}});
+    calls.push_back({"box-7-ints", {"PPiiiiiii", 9}});
+    calls.push_back({"box-reference-form", {dim == 3 ? "PiiiiiP" : "PiiiP", dim == 3 ? 7 : 5}});
+    calls.push_back({"box-reference-form-buffer-second", {dim == 3 ? "PPiiiii" : "PPiii", dim == 3 ? 7 : 5}});
+    calls.push_back({"box-reference-form-of-the-other-dimension", {dim == 3 ? "PiiiP" : "PiiiiiP", dim == 3 ? 5 : 7}});
+  }
+  return calls;
+}
+
+// ---- face box --------------------------------------------------------------------------------------------------------
+void face_boxes(const slf::ModuleConfig& c2, const slf::ModuleConfig& c3) {
+  const slf::KernelKind kinds[] = {slf::KK_COLLECT_BOX, slf::KK_DISTRIBUTE_BOX, slf::KK_COLLECT_FACE_SWAP, slf::KK_DISTRIBUTE_FACE_SWAP,
+                                   slf::KK_COLLECT_MACRO_FACE, slf::KK_DISTRIBUTE_MACRO_FACE};
+  for (const slf::ModuleConfig* c : {&c2, &c3}) {
+    const int dim = c->geo.dim;
+    for (slf::KernelKind kind : kinds) {
+      const bool macro = kind == slf::KK_COLLECT_MACRO_FACE || kind == slf::KK_DISTRIBUTE_MACRO_FACE;
+      struct Try { std::string name; long long ints[5]; };
+      std::vector<Try> tries;
+      for (int face = 1; face <= 6; face++) {
+        if (dim == 3) tries.push_back({"face" + num(face), {face, 1, 1, 4, macro ? 2 : 10}});
+        else if (macro) tries.push_back({"layer" + num(face - 2), {1, 4, face - 2, 0, 0}});      // 2-D macro: (base_gx, max_lx, gy)
+        else tries.push_back({"face" + num(face), {face, 1, 12, 0, 0}});
+      }
+      if (dim == 3) {
+        tries.push_back({"max-other-7", {2, 1, 1, 4, 7}});
+        tries.push_back({"base-gx-6", {2, 6, 1, 4, macro ? 2 : 10}});
+        tries.push_back({"base-gx-negative", {4, -1, 1, 4, macro ? 2 : 10}});
+        tries.push_back({"base-other-3", {5, 1, 3, 4, macro ? 2 : 10}});
+        tries.push_back({"whole-face", {3, 0, 0, 8, macro ? 4 : 20}});
+      } else if (macro) {
+        tries.push_back({"layer-5", {1, 4, 5, 0, 0}});
+        tries.push_back({"base-gx-6", {6, 4, 2, 0, 0}});
+      } else {
+        tries.push_back({"max-lx-7", {2, 1, 7, 0, 0}});
+        tries.push_back({"base-gx-6", {3, 6, 12, 0, 0}});
+        tries.push_back({"whole-face", {2, 0, 24, 0, 0}});
+      }
+      for (const Try& t : tries) {
+        slf::FaceBox box = {};
+        const char* err = "";
+        const int rc = slf::face_box(c->geo, kind, t.ints, &box, &err);
+        std::string detail;
+        if (!rc)
+          detail = "collect=" + num(box.collect) + " macro=" + num(box.macro) + " layer=" + num(box.layer) + " dirs=" +
+                   list(box.dirs, box.nd) + " base=" + std::to_string(box.base) + " row_stride=" + std::to_string(box.row_stride) +
+                   " ncols=" + num(box.ncols) + " nrows=" + num(box.nrows);
+        line("face", "kind" + num(kind), dim == 2 ? "d2q9" : "d3q19", t.name, rc, err, detail);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+int main() {
+  for (const char* knob : {"SLF_BC_LEVEL", "SLF_VARIANT", "SLF_BLOCK_X"}) unsetenv(knob);
+  std::vector<Config> configs = all_configs();
+  for (Config& c : configs) {
+    const char* err = "";
+    c.code = slf::module_config(&c.desc, &c.cfg, &err);
+    line("config", "-", c.name, "-", c.code, err, c.code ? "" : dump(c.cfg));
+  }
+  std::vector<std::string> names;
+  for (const slf::KernelRow& r : slf::KERNEL_TABLE) {
+    bool seen = false;
+    for (const std::string& n : names) seen = seen || n == r.name;
+    if (!seen) names.push_back(r.name);
+  }
+  names.push_back("");
+  names.push_back("NoSuchKernel");
+  for (const std::string& name_s : names) {
+    const char* name = name_s.c_str();
+    for (const Config& cc : configs) {
+      if (cc.code) continue;
+      const slf::ModuleConfig& c = cc.cfg;
+      const slf::KernelRow* row = nullptr;
+      std::string err;
+      const int rc = slf::resolve(c, name, &row, &err);
+      line("resolve", name_s, cc.name, "-", rc, err, rc ? "" : "kind=" + num(row->kind) + " local_velocity=" + num(row->local_velocity));
+      if (rc) continue;
+      const slf::KernelRow* sig = signature_of(name, row->kind);
+      if (!sig) {
+        line("bind", name_s, cc.name, "no-signature", -1, "", "");
+        continue;
+      }
+      for (const auto& call : calls_for(c, *sig)) {
+        const std::string& fmt = call.second.fmt;
+        // argument i: a pointer 0x1000 * (i + 1) or the integer 100 + i
+        std::vector<unsigned long long> pv(fmt.size() + 1);
+        std::vector<int32_t> iv(fmt.size() + 1);
+        std::vector<const void*> argv(fmt.size() + 1);
+        for (size_t i = 0; i < fmt.size(); i++) {
+          pv[i] = 0x1000ull * (i + 1);
+          iv[i] = 100 + (int)i;
+          argv[i] = fmt[i] == 'i' ? (const void*)&iv[i] : (const void*)&pv[i];
+        }
+        slf::BoundArgs bound = {};
+        err.clear();
+        const int brc = slf::bind(c, *row, fmt.c_str(), argv.data(), call.second.argc, &bound, &err);
+        line("bind", name_s, cc.name, call.first, brc, err, brc ? "" : dump(bound));
+      }
+    }
+  }
+  const slf::ModuleConfig* c2 = nullptr;
+  const slf::ModuleConfig* c3 = nullptr;
+  for (const Config& cc : configs) {
+    if (cc.name == "bgk-d2q9-aa-direct") c2 = &cc.cfg;
+    if (cc.name == "bgk-d3q19-aa-direct") c3 = &cc.cfg;
+  }
+  face_boxes(*c2, *c3);
+  return 0;
+}

@@ -81,11 +81,22 @@ REFERENCE_KERNELS = [
     'ShanChenCollideAndPropagate0', 'ShanChenCollideAndPropagate1']
 
 
+def served_kernel_names():
+    """The name literal of every row of slf::KERNEL_TABLE (sailfish_amd/csrc/slf_bind.h), the one place slf_kernel_get()
+    resolves names from."""
+    src = open(os.path.join(ROOT, 'sailfish_amd', 'csrc', 'slf_bind.h')).read()
+    table = src[src.index('KERNEL_TABLE[] = {'):]
+    table = table[:table.index('\n};')]
+    rows = re.findall(r'^\s*\{"([A-Za-z0-9]+)", KK_[A-Z0-9_]+,', table, flags=re.M)
+    assert len(rows) == len(re.findall(r'^\s*\{', table, flags=re.M)) and len(rows) >= 30, rows     # every row was read
+    return set(rows)
+
+
 def test_every_in_scope_reference_kernel_name_is_served():
-    """slf_kernel_get() resolves names with a chain of string compares: every name of the table must be in it (the GPU
-    round trips of the face kernels are tests/test_gpu_face_kernels.py; the sweeps and PBC kernels run in every test)."""
-    src = open(os.path.join(ROOT, 'sailfish_amd', 'csrc', 'slf_api.hip')).read()
-    served = set(re.findall(r'!strcmp\(name, "([A-Za-z0-9]+)"\)', src))
+    """slf_kernel_get() resolves names through the kernel table of slf_bind.h: every name of the list above must have a
+    row in it (what the rows say is tests/test_abi_bind.py; the GPU round trips of the face kernels are
+    tests/test_gpu_face_kernels.py; the sweeps and PBC kernels run in every test)."""
+    served = served_kernel_names()
     missing = [n for n in REFERENCE_KERNELS if n not in served]
     assert not missing, missing
     header = open(HEADER).read()
@@ -95,12 +106,12 @@ def test_every_in_scope_reference_kernel_name_is_served():
 
 # kernels this library adds to the reference's set (documented in include/sailfish_hip.h next to the ones they stand in for)
 ADDED_KERNELS = ['ShanChenCollideAndPropagateFused', 'ShanChenCollideAndPropagateFusedV', 'ShanChenPrepareDensities',
-                 'ComputeMacroFields', 'CollideAndPropagateResident']
+                 'ComputeMacroFields', 'CollideAndPropagateResident', 'FreeEnergyPrepareMacroFields',
+                 'FreeEnergyCollideAndPropagateFluid', 'FreeEnergyCollideAndPropagateOrderParam', 'ShanChenCollideAndPropagate2']
 
 
 def test_added_kernel_names_are_served_and_documented():
-    src = open(os.path.join(ROOT, 'sailfish_amd', 'csrc', 'slf_api.hip')).read()
-    served = set(re.findall(r'!strcmp\(name, "([A-Za-z0-9]+)"\)', src))
+    served = served_kernel_names()
     header = open(HEADER).read()
     for n in ADDED_KERNELS:
         assert n in served, n
