@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Decaying Kida vortex in a periodic box (the flow of sailfish's examples/turbulence/kida_vortex.py; S. Kida and
-Y. Murakami, Kolmogorov similarity in freely decaying turbulence, Phys. Fluids 30, 2030 (1987)).  D3Q19 -- the
-reference's default here, D3Q15, is not implemented.  Kinetic energy and enstrophy per node are formed on the device
-every 20 steps (sailfish.stats.KineticEnergyEnstrophyMixIn) and written to <output>_ke_ens_<subdomain id>.dat as rows
-of (iteration, energy, enstrophy); without --output they go to the log.  --shift_x/y/z move the initial field by
-whole nodes: the statistics of a periodic box do not depend on them."""
+Y. Murakami, Kolmogorov similarity in freely decaying turbulence, Phys. Fluids 30, 2030 (1987)).  --grid chooses the
+lattice: D3Q19 (the default here), D3Q15 (the reference's default for this flow) or D3Q27.  Kinetic energy and enstrophy
+per node are formed on the device every --stats_every steps (20; sailfish.stats.KineticEnergyEnstrophyMixIn) and written
+to <output>_ke_ens_<subdomain id>.dat as rows of (iteration, energy, enstrophy); without --output they go to the log.
+--shift_x/y/z move the initial field by whole nodes: the statistics of a periodic box do not depend on them."""
 import os
 import sys
 
@@ -58,6 +58,7 @@ class KidaSim(LBFluidSim, KineticEnergyEnstrophyMixIn):
         group.add_argument('--shift_x', type=int, default=0)
         group.add_argument('--shift_y', type=int, default=0)
         group.add_argument('--shift_z', type=int, default=0)
+        group.add_argument('--stats_every', type=int, default=0, help='steps between two samples (0: %d)' % cls.every)
 
     @classmethod
     def modify_config(cls, config):
@@ -66,6 +67,7 @@ class KidaSim(LBFluidSim, KineticEnergyEnstrophyMixIn):
 
     def __init__(self, config):
         super(KidaSim, self).__init__(config)
+        self.every = getattr(config, 'stats_every', 0) or type(self).every
         self.stats = []
 
     def after_step(self, runner):

@@ -36,7 +36,7 @@ typedef struct slf_kernel slf_kernel;
 
 enum { SLF_OK = 0, SLF_ERR_INVALID = 1, SLF_ERR_HIP = 2, SLF_ERR_UNSUPPORTED = 3, SLF_ERR_NOT_FOUND = 4 };
 
-enum { SLF_D2Q9 = 0, SLF_D3Q19 = 1 };
+enum { SLF_D2Q9 = 0, SLF_D3Q19 = 1, SLF_D3Q15 = 2, SLF_D3Q27 = 3 };   /* 2, 3: BGK single-fluid modules only */
 /* SLF_ELBM: the entropic collision (--model=elbm; reference templates/entropic.mako, relaxation.mako:56-97). */
 enum { SLF_BGK = 0, SLF_MRT = 1, SLF_ELBM = 2 };
 enum { SLF_AB = 0, SLF_AA = 1 };
@@ -108,7 +108,7 @@ enum {
  * geo_encoder.py:341-363). */
 typedef struct slf_module_desc {
   uint32_t struct_size;        /* sizeof(slf_module_desc), ABI check */
-  int32_t lattice;             /* SLF_D2Q9 | SLF_D3Q19            (--grid) */
+  int32_t lattice;             /* SLF_D2Q9 | SLF_D3Q19 | SLF_D3Q15 | SLF_D3Q27 (--grid) */
   int32_t model;               /* SLF_BGK | SLF_MRT | SLF_ELBM    (--model) */
   int32_t precision;           /* 4 (single) | 8 (double)          (--precision) */
   int32_t access_pattern;      /* SLF_AB | SLF_AA                  (--access_pattern) */

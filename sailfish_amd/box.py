@@ -71,8 +71,8 @@ class BoxSim(object):
         CollideAndPropagate; None = as the module's model says; False = no array (every Newton iteration starts from 2)."""
         self.backend = backend
         self.desc = desc
-        self.dim = 2 if desc.lattice == hipabi.SLF_D2Q9 else 3
-        self.Q = 9 if self.dim == 2 else 19
+        grid = [g for g in sym.KNOWN_GRIDS if g.slf_id == desc.lattice][0]
+        self.dim, self.Q = grid.dim, grid.Q
         self.dtype = np.float32 if desc.precision == 4 else np.float64
         self.shape = (desc.arr_nz, desc.arr_ny, desc.arr_nx)
         self.nodes = desc.arr_nz * desc.arr_ny * desc.arr_nx

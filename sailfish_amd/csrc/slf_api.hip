@@ -84,6 +84,10 @@ struct slf_kernel {
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
 
+// D3Q15 / D3Q27 modules: their lattice-dependent kernels live in slf_lat.hip, every other family refuses them by name
+static bool on_lat(const slf_module* m) { return slf::is_lat_lattice(m->sel.lattice); }
+static const char* lat_name(const slf_module* m) { return m->sel.lattice == SLF_D3Q15 ? "D3Q15" : "D3Q27"; }
+
 // Indirect addressing: the slot -> node table of `nodes` (SlotTable, slf_kernels.h), built on first use and whenever a
 // launch names another table.  SLF_INDIRECT_SLOTS=0: never (one thread per dense node, the round-3 kernels: A/B switch).
 static const slf::SlotTable* slot_table_for(slf_module* m, const void* nodes, hipStream_t s) {
@@ -976,6 +980,7 @@ int slf_module_classify_rows(slf_module* m, const void* map_dptr, slf_stream* st
   m->rows = slf::RowClasses{};
   if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
   if (!map_dptr) return SLF_OK;                                   // forget the tables
+  if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(lat_name(m)) + ": row classes belong to the D3Q19 whole-row kernels");
   if (!m->sel.general || m->sel.lattice != 1 || g.indirect || !(g.variant & 8))
     return fail(SLF_ERR_UNSUPPORTED, "row classes: D3Q19 modules with a node map and direct addressing (whole-row kernels) only");
   SLF_HIP(hipSetDevice(m->ctx->device));
@@ -1116,6 +1121,7 @@ static int check_xface_buffers(const slf_module* m, void* send_low, void* send_h
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
   if (send_low || send_high || recv_low || recv_high) {
     const slf::Geometry& g = m->geo;
+    if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(lat_name(m)) + ": x-face buffers are not implemented on this lattice (D3Q19 only)");
     if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || m->fe.enabled || m->sc3.enabled || !(g.variant & 8))
       return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: D3Q19 single-fluid modules with direct addressing (whole-row kernels) only");
     if (g.wrap[0]) return fail(SLF_ERR_INVALID, "x-face buffers make no sense with x wrapped inside the sweep");
@@ -1154,6 +1160,7 @@ static int check_xface_planes(const slf_module* m, int32_t which, void* send_low
     if (m->sc3.enabled)
       return fail(SLF_ERR_UNSUPPORTED, "x-face planes: not implemented for simtype = SLF_SIM_SHAN_CHEN_TERNARY (the planes carry two "
                                        "lattices and two density fields); connected x faces go through ghost columns and index lists");
+    if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(lat_name(m)) + ": x-face planes are not implemented on this lattice (D3Q19 only)");
     if (m->sel.lattice != 1 || g.indirect || !m->sc.enabled || !(g.variant & 8))
       return fail(SLF_ERR_UNSUPPORTED, "x-face planes: D3Q19 Shan-Chen modules with direct addressing (whole-row kernels)");
     if (m->sc.enabled == 2 && which == 1) return fail(SLF_ERR_INVALID, "x-face planes: the single-component model has one lattice");
@@ -1245,6 +1252,7 @@ int slf_stats_profiles(slf_module* m, int axis, const void* vx, const void* vy, 
 // ---- force on bodies by momentum exchange (slf_force.hip) --------------------------------------------------------
 static int check_force_call(const slf_module* m, int n_objects, uint32_t max_links, const char* what) {
   if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": force objects are not implemented on " + lat_name(m));
   if (m->sc.enabled || m->fe.enabled || m->sc3.enabled)
     return fail(SLF_ERR_UNSUPPORTED, std::string(what) + ": single-fluid modules only (the force is read off lattice 0 alone)");
   if (n_objects < 0 || n_objects > 65535) return fail(SLF_ERR_INVALID, std::string(what) + ": 0 .. 65535 objects per call");
@@ -1411,6 +1419,7 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   if (!k->bound) return fail(SLF_ERR_INVALID, "pair sweep: set the kernel arguments first (source and destination are checked)");
   if (rows_per_strip < 0 || planes_per_chunk < 0) return fail(SLF_ERR_INVALID, "pair sweep: negative strip / chunk size");
   const slf_module* m = k->mod;
+  if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string("pair sweep: not implemented on ") + lat_name(m) + " (D3Q19, single precision, BGK modules only)");
   const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows(m->geo);
   const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk(m->geo);
   // The knobs of the kernel, read here, per kernel object (unset or empty: the default; not a small non-negative integer:
@@ -1479,6 +1488,11 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       // (the slot table is built when the arguments are bound, slf_kernel_set_args: a launch may be part of a graph capture)
       if (g.indirect && kk == slf::KK_COLLIDE_AND_PROPAGATE && m->slots.nodes == a.nodes) a.slots = &m->slots;
       if (int rc = sweep_shape(k, region, kk == slf::KK_COMPUTE_MACRO, &sh)) return rc;
+      if (on_lat(m)) {
+        if (kk == slf::KK_COMPUTE_MACRO) e = slf::launch_lat_macro(m->sel, sh.prop, g, m->phys, a, s);
+        else e = slf::launch_lat_sweep(m->sel, sh.prop, g, m->phys, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
+        break;
+      }
       if (kk == slf::KK_COMPUTE_MACRO) e = slf::launch_macro(m->sel, sh.prop, g, m->phys, a, s);
       else e = slf::launch_sweep(m->sel, sh.prop, g, m->phys, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
       break;
@@ -1541,7 +1555,8 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
     // lb_binary.py:107-127, lb_ternary.py:118-142)
     case slf::KK_SET_INITIAL_CONDITIONS:
       if (int rc = nodes_given(k)) return rc;
-      e = slf::launch_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, a.nodes, s);
+      if (on_lat(m)) e = slf::launch_lat_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, s);
+      else e = slf::launch_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, a.nodes, s);
       break;
     case slf::KK_SC_INIT:
       if (int rc = nodes_given(k)) return rc;
@@ -1555,7 +1570,8 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       break;
     case slf::KK_PBC:
     case slf::KK_PBC_SWAP:
-      e = slf::launch_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], kk == slf::KK_PBC_SWAP, s);
+      if (on_lat(m)) e = slf::launch_lat_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], kk == slf::KK_PBC_SWAP, s);
+      else e = slf::launch_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], kk == slf::KK_PBC_SWAP, s);
       break;
     case slf::KK_MACRO_PBC:
       e = slf::launch_macro_pbc(m->sel, g, (void*)b.ptrs[0], (int)b.ints[0], s);

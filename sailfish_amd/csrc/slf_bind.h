@@ -77,10 +77,41 @@ struct ModuleConfig {
   int n_node_params;
 };
 
+// D3Q15 and D3Q27 run the BGK sweep of slf_lat.hip and nothing else: what it does not implement is named here and refused,
+// whatever the other checks of module_config() would have said.  NULL: the descriptor is served (or is another lattice's).
+inline bool is_lat_lattice(int lattice) { return lattice == SLF_D3Q15 || lattice == SLF_D3Q27; }
+inline const char* lat_refusal(const slf_module_desc* d) {
+  if (!is_lat_lattice(d->lattice)) return nullptr;
+#define SLF_LAT_MSG(text) (d->lattice == SLF_D3Q15 ? "D3Q15: " text : "D3Q27: " text)
+  if (d->model == SLF_MRT) return SLF_LAT_MSG("--model=mrt is not implemented on this lattice; the BGK collision only");
+  if (d->model == SLF_ELBM) return SLF_LAT_MSG("--model=elbm is not implemented on this lattice; the BGK collision only");
+  if (d->model != SLF_BGK) return SLF_LAT_MSG("the BGK collision only");
+  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
+    return SLF_LAT_MSG("the Shan-Chen models are not implemented on this lattice; single-fluid modules only");
+  if (d->simtype == SLF_SIM_FREE_ENERGY) return SLF_LAT_MSG("the free-energy model is not implemented on this lattice; single-fluid modules only");
+  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return SLF_LAT_MSG("the ternary Shan-Chen model is not implemented on this lattice; single-fluid modules only");
+  if (d->simtype != SLF_SIM_LBM) return SLF_LAT_MSG("single-fluid modules only");
+  if (d->regularized) return SLF_LAT_MSG("--regularized is not implemented on this lattice");
+  if (d->subgrid) return SLF_LAT_MSG("--subgrid is not implemented on this lattice");
+  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return SLF_LAT_MSG("--minimize_roundoff is not implemented on this lattice");
+  if (d->entropic_equilibrium) return SLF_LAT_MSG("entropic_equilibrium belongs to --model=elbm, which is not implemented on this lattice");
+  if (d->node_addressing != SLF_ADDR_DIRECT) return SLF_LAT_MSG("--node_addressing=indirect is not implemented on this lattice; direct addressing only");
+  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
+    const int k = d->type_kind[i];
+    if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB ||
+          k == SLF_NK_HALF_BB))
+      return SLF_LAT_MSG("fluid, NTFullBBWall and NTHalfBBWall nodes only; the other node types are not implemented on this lattice");
+  }
+#undef SLF_LAT_MSG
+  return nullptr;
+}
+
 inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char** err) {
   *c = ModuleConfig{};
   if (d->struct_size != sizeof(slf_module_desc)) return refuse(err, SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
-  if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19) return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported lattice");
+  if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19 && d->lattice != SLF_D3Q15 && d->lattice != SLF_D3Q27)
+    return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported lattice");
+  if (const char* why = lat_refusal(d)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported collision model");
   if (d->precision != 4 && d->precision != 8) return refuse(err, SLF_ERR_UNSUPPORTED, "precision must be 4 or 8");
@@ -315,6 +346,7 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
     // (--regularized / --subgrid / --model=elbm were refused above: single-fluid modules only)
     if (why) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   }
+  if (is_lat_lattice(d->lattice)) g.variant = 0;      // no tuned / whole-row D3Q19 kernels: the sweep of slf_lat.hip
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
   // workgroup; longer rows are cut into 256-thread chunks.
   int bx = ((d->lat_nx - 2 + 63) / 64) * 64;
@@ -462,6 +494,17 @@ inline int resolve(const ModuleConfig& c, const char* name, const KernelRow** ou
   if (!named) return refuse(err, SLF_ERR_NOT_FOUND, std::string("unknown kernel: ") + name);
   if (!row) return wrong_family(c, *named, err);
   const KernelKind kk = row->kind;
+  if (is_lat_lattice(c.sel.lattice)) {
+    // D3Q15 / D3Q27: CollideAndPropagate, ComputeMacroFields, SetInitialConditions and the ghost-layer kernels are served by
+    // slf_lat.hip; the sparse, box and macro-field kernels never look at a direction; everything else is refused here
+    const std::string lat = c.sel.lattice == SLF_D3Q15 ? "D3Q15" : "D3Q27";
+    if (kk == KK_RESIDENT)
+      return refuse(err, SLF_ERR_UNSUPPORTED, lat + ": CollideAndPropagateResident is not implemented on this lattice (2-D lattices only)");
+    if (is_face_kind(kk))
+      return refuse(err, SLF_ERR_UNSUPPORTED, lat + ": " + name + " (the reference's face argument lists) is not implemented on this "
+                                              "lattice; faces travel through Collect / DistributeContinuousData with a direction mask or "
+                                              "through index lists");
+  }
   if (kk == KK_RESIDENT) {
     if (int rc = resident_refusal(c, err)) return rc;
   }
@@ -541,6 +584,9 @@ inline int bind(const ModuleConfig& c, const KernelRow& row, const char* fmt, co
     // 3-D (dist, face, base_gx, base_other, max_lx, max_other, buffer), 2-D (dist, face, base_gx, max_lx, buffer)
     if (b->n_ints == (dim == 3 ? 5 : 3)) {
       want_i = b->n_ints;
+      if (is_lat_lattice(c.sel.lattice))
+        return refuse(err, SLF_ERR_UNSUPPORTED, "D3Q15 / D3Q27: the reference's face argument list is not implemented on these lattices; "
+                                                "pass the direction mask and the box");
       if (strcmp(fmt, face_fmt)) return refuse(err, SLF_ERR_INVALID, "reference form: the buffer is the last argument");
       if (c.geo.indirect) return refuse(err, SLF_ERR_UNSUPPORTED, "indirect addressing: halo through index lists");
     }

@@ -19,11 +19,13 @@ template <class F> inline bool pick_prop(Prop p, F&& f) { return pick<int, PROP_
 // precision of a module: f(float{}) or f(double{}), returns what f returns
 template <class F> inline auto pick_real(const KernelSelector& sel, F&& f) { return sel.precision == 4 ? f(float{}) : f(double{}); }
 
-// lattice x precision of a module: f(LR<L, R>{}), returns f's hipError_t
+// lattice x precision of a module: f(LR<L, R>{}), returns f's hipError_t.  D2Q9 and D3Q19, the lattices every kernel family
+// is written for; any other id is an error here, never D3Q19 (D3Q15 and D3Q27 have their own picker, slf_lat.hip)
 template <class L_, class R_> struct LR { using L = L_; using R = R_; };
 template <class F> inline hipError_t pick_lr(const KernelSelector& sel, F&& f) {
-  if (sel.lattice == 0) return pick_real(sel, [&](auto r) { return f(LR<D2Q9, decltype(r)>{}); });
-  return pick_real(sel, [&](auto r) { return f(LR<D3Q19, decltype(r)>{}); });
+  if (sel.lattice == D2Q9::id) return pick_real(sel, [&](auto r) { return f(LR<D2Q9, decltype(r)>{}); });
+  if (sel.lattice == D3Q19::id) return pick_real(sel, [&](auto r) { return f(LR<D3Q19, decltype(r)>{}); });
+  return hipErrorInvalidValue;
 }
 
 }  // namespace slf

@@ -248,6 +248,16 @@ hipError_t launch_sc3_fused(const KernelSelector& sel, Prop prop, const Geometry
 hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* const dist[3], const void* const field[3],
                            const void* const v[3], hipStream_t s);
 
+// ---- D3Q15 and D3Q27 (slf_lat.hip): BGK single-fluid modules, direct addressing ----
+// the counterparts of launch_sweep / launch_init / launch_pbc / launch_macro; any other lattice: hipErrorInvalidValue
+hipError_t launch_lat_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                            int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_lat_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist, const void* rho,
+                           const void* const v[3], hipStream_t s);
+hipError_t launch_lat_pbc(const KernelSelector& sel, const Geometry& g, void* dist, int axis, bool with_swap, hipStream_t s);
+hipError_t launch_lat_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
+                            hipStream_t s);
+
 // ---- several steps inside one launch (slf_resident.hip): 2-D lattices ----
 // src / dst: the raw distribution arrays ([0] = the array of the in-place pattern / copy A of the two-copy pattern, [1] =
 // copy B) and where the tiles go after `steps` steps from iteration it0; tiles of tile_x x tile_y nodes, halo of `halo`

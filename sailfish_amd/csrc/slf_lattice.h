@@ -112,6 +112,60 @@ struct D3Q19 {
   static constexpr int M_RHO = 0, M_MX = 3, M_MY = 5, M_MZ = 7;
 };
 
+// D3Q15 and D3Q27 (reference sym.py:228-239, 409-428): direction order, opposites and weights only -- no MRT members, the
+// BGK sweep of slf_lat.hip is all that runs on them.  Pinned by tests/golden/lattices_q15_q27.json.
+struct D3Q15 {
+  static constexpr int dim = 3;
+  static constexpr int Q = 15;
+  static constexpr int id = 2;
+  // fC fE fW fN fS fT fB fTNE fTNW fTSE fTSW fBNE fBNW fBSE fBSW
+  static constexpr int ex(int i) {
+    constexpr int t[15] = {0, 1, -1, 0, 0, 0, 0, 1, -1, 1, -1, 1, -1, 1, -1};
+    return t[i];
+  }
+  static constexpr int ey(int i) {
+    constexpr int t[15] = {0, 0, 0, 1, -1, 0, 0, 1, 1, -1, -1, 1, 1, -1, -1};
+    return t[i];
+  }
+  static constexpr int ez(int i) {
+    constexpr int t[15] = {0, 0, 0, 0, 0, 1, -1, 1, 1, 1, 1, -1, -1, -1, -1};
+    return t[i];
+  }
+  static constexpr int opp(int i) {
+    constexpr int t[15] = {0, 2, 1, 4, 3, 6, 5, 14, 13, 12, 11, 10, 9, 8, 7};
+    return t[i];
+  }
+  static constexpr int wnum(int i) { return i == 0 ? 2 : 1; }
+  static constexpr int wden(int i) { return i < 7 ? 9 : 72; }
+  static constexpr int dir2vecidx(int o) { return o; }
+};
+
+struct D3Q27 {
+  static constexpr int dim = 3;
+  static constexpr int Q = 27;
+  static constexpr int id = 3;
+  // the 19 directions of D3Q19 in its order, then the corners: fTNE fBNE fTSE fBSE fTNW fBNW fTSW fBSW
+  static constexpr int ex(int i) {
+    constexpr int t[27] = {0, 1, -1, 0, 0, 0, 0, 1, -1, 1, -1, 0, 0, 0, 0, 1, -1, 1, -1, 1, 1, 1, 1, -1, -1, -1, -1};
+    return t[i];
+  }
+  static constexpr int ey(int i) {
+    constexpr int t[27] = {0, 0, 0, 1, -1, 0, 0, 1, 1, -1, -1, 1, -1, 1, -1, 0, 0, 0, 0, 1, 1, -1, -1, 1, 1, -1, -1};
+    return t[i];
+  }
+  static constexpr int ez(int i) {
+    constexpr int t[27] = {0, 0, 0, 0, 0, 1, -1, 0, 0, 0, 0, 1, 1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, -1, 1, -1};
+    return t[i];
+  }
+  static constexpr int opp(int i) {
+    constexpr int t[27] = {0, 2, 1, 4, 3, 6, 5, 10, 9, 8, 7, 14, 13, 12, 11, 18, 17, 16, 15, 26, 25, 24, 23, 22, 21, 20, 19};
+    return t[i];
+  }
+  static constexpr int wnum(int i) { return i == 0 ? 8 : (i < 7 ? 2 : 1); }
+  static constexpr int wden(int i) { return i < 7 ? 27 : (i < 19 ? 54 : 216); }
+  static constexpr int dir2vecidx(int o) { return o; }
+};
+
 template <class L>
 constexpr int e_comp(int i, int d) {
   return d == 0 ? L::ex(i) : (d == 1 ? L::ey(i) : L::ez(i));

@@ -11,7 +11,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 
 SLF_MAX_NODE_TYPES = 16
 SLF_MAX_Q = 27
-SLF_D2Q9, SLF_D3Q19 = 0, 1
+SLF_D2Q9, SLF_D3Q19, SLF_D3Q15, SLF_D3Q27 = 0, 1, 2, 3
 SLF_BGK, SLF_MRT, SLF_ELBM = 0, 1, 2
 SLF_AB, SLF_AA = 0, 1
 SLF_SIM_LBM, SLF_SIM_SHAN_CHEN_BINARY, SLF_SIM_SHAN_CHEN_SINGLE, SLF_SIM_FREE_ENERGY, SLF_SIM_SHAN_CHEN_TERNARY = 0, 1, 2, 3, 4

@@ -217,9 +217,43 @@ class LBSim(object):
     def check_module_desc(cls, kw):
         """Refuses, on the host and with a clear message, what no kernel of the library covers (the library refuses the
         same at module creation)."""
+        cls.check_lattice(kw)
         if hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []) and kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
             raise NotImplementedError('NTWallTMS nodes: single-fluid simulations only (the Shan-Chen kernels serve fluid and '
                                       'full-way bounce-back nodes)')
+
+    # what the sweep of D3Q15 / D3Q27 (csrc/slf_lat.hip) serves: the BGK collision of a single fluid over these node kinds
+    LAT_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
+                 hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB)
+
+    @staticmethod
+    def check_lattice(kw):
+        """D3Q15 and D3Q27: everything but the BGK collision of a single fluid with fluid, full-way and half-way wall nodes,
+        dense addressing and the standard or incompressible density model is refused, naming the lattice."""
+        name = {hipabi.SLF_D3Q15: 'D3Q15', hipabi.SLF_D3Q27: 'D3Q27'}.get(kw.get('lattice'))
+        if name is None:
+            return
+        why = None
+        model = kw.get('model', hipabi.SLF_BGK)
+        simtype = kw.get('simtype', hipabi.SLF_SIM_LBM)
+        if model != hipabi.SLF_BGK:
+            why = '--model=%s is not implemented; the BGK collision only' % {hipabi.SLF_MRT: 'mrt', hipabi.SLF_ELBM: 'elbm'}.get(model, model)
+        elif simtype != hipabi.SLF_SIM_LBM:
+            why = 'the %s model is not implemented; single-fluid simulations only' % {
+                hipabi.SLF_SIM_SHAN_CHEN_BINARY: 'Shan-Chen', hipabi.SLF_SIM_SHAN_CHEN_SINGLE: 'Shan-Chen',
+                hipabi.SLF_SIM_FREE_ENERGY: 'free-energy', hipabi.SLF_SIM_SHAN_CHEN_TERNARY: 'ternary Shan-Chen'}.get(simtype, simtype)
+        elif kw.get('regularized'):
+            why = '--regularized is not implemented'
+        elif kw.get('subgrid'):
+            why = '--subgrid is not implemented'
+        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
+            why = '--minimize_roundoff is not implemented'
+        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
+            why = '--node_addressing=indirect is not implemented; direct addressing only'
+        elif any(k not in LBSim.LAT_KINDS for k in kw.get('type_kind', [])):
+            why = 'fluid, NTFullBBWall and NTHalfBBWall nodes only; the other node types are not implemented'
+        if why:
+            raise NotImplementedError('%s: %s on this lattice' % (name, why))
 
     def fill_module_desc(self, kw):
         """Contributes to the kernel-module descriptor (the counterpart of the reference's

@@ -42,7 +42,8 @@ class LBFluidSim(LBSim):
         super(LBFluidSim, self).fill_module_desc(kw)
         cfg = self.config
         if not self.grid.model_supported(cfg.model):
-            raise ValueError('model %s not supported on grid %s' % (cfg.model, self.grid.__name__))
+            raise ValueError('model %s not supported on grid %s%s' % (
+                cfg.model, self.grid.__name__, '' if hasattr(self.grid, 'mrt_matrix') else ' (the BGK collision only)'))
         kw.update(lattice=self.grid.slf_id,
                   model={'mrt': hipabi.SLF_MRT, 'elbm': hipabi.SLF_ELBM}.get(cfg.model, hipabi.SLF_BGK),
                   tau=sym.relaxation_time(cfg.visc), visc=cfg.visc,

@@ -222,6 +222,8 @@ class SubdomainRunner(object):
                                  '(do not combine with --nohip_fused_periodic)')
             kw['fluid_only'] = 0
             kw['node_addressing'] = hipabi.SLF_ADDR_INDIRECT
+            if hasattr(self._sim, 'check_lattice'):
+                self._sim.check_lattice(kw)
             kw['dist_stride'] = (self._subdomain.active_nodes + 1 + 31) // 32 * 32   # + one spare slot (halo lists)
             self._check_halfbb_targets()
         return hipabi.make_desc(**kw)
@@ -778,6 +780,8 @@ class SubdomainRunner(object):
         if not sim.force_objects:
             return
         cfg = self.config
+        if int(self._desc.lattice) in (hipabi.SLF_D3Q15, hipabi.SLF_D3Q27):
+            raise NotImplementedError('%s: force objects are not implemented on this lattice' % sim.grid.__name__)
         if len(sim.grids) != 1 or int(self._desc.simtype) != hipabi.SLF_SIM_LBM:
             raise NotImplementedError('force objects: single-fluid simulations only (the momentum exchange is read off one '
                                       'lattice; Shan-Chen and binary models are not covered)')

@@ -30,6 +30,8 @@ class DxQy(object):
 
     @classmethod
     def model_supported(cls, model):
+        if not hasattr(cls, '_mrt_basis'):      # D3Q15, D3Q27: the BGK sweep only
+            return model == 'bgk'
         if model == 'mrt':
             return hasattr(cls, 'mrt_matrix')
         if model == 'elbm':
@@ -89,7 +91,29 @@ class D3Q19(DxQy):
                 [(x * x - y * y) * z for x, y, z in b]]
 
 
-KNOWN_GRIDS = (D2Q9, D3Q19)
+class D3Q15(DxQy):
+    """reference sym.py:228-239; no MRT basis here: BGK only."""
+    dim = 3
+    Q = 15
+    slf_id = 2
+    basis = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1),
+             (1, 1, 1), (-1, 1, 1), (1, -1, 1), (-1, -1, 1),
+             (1, 1, -1), (-1, 1, -1), (1, -1, -1), (-1, -1, -1)]
+    weights = [Fraction(2, 9)] + [Fraction(1, 9)] * 6 + [Fraction(1, 72)] * 8
+
+
+class D3Q27(DxQy):
+    """reference sym.py:409-428 (which gives it no MRT basis either)."""
+    dim = 3
+    Q = 27
+    slf_id = 3
+    basis = D3Q19.basis + [(1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1),
+                           (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)]
+    weights = [Fraction(8, 27)] + [Fraction(2, 27)] * 6 + [Fraction(1, 54)] * 12 + [Fraction(1, 216)] * 8
+
+
+# D3Q19 stays the first 3-D entry: the default --grid is the first lattice of the simulation's dimension
+KNOWN_GRIDS = (D2Q9, D3Q19, D3Q15, D3Q27)
 
 _NAME_MAP_2D = {(0, 0): 'C', (1, 0): 'E', (-1, 0): 'W', (0, 1): 'N', (0, -1): 'S'}
 
@@ -148,8 +172,9 @@ def _prepare_grids():
                 grid.dir2vecidx[d] = i
                 grid.vecidx2dir[i] = d
                 d += 1
-        grid.mrt_matrix = np.array(_gram_schmidt_int(grid._mrt_basis()), dtype=np.int64)
-        grid.mrt_norms = (grid.mrt_matrix * grid.mrt_matrix).sum(axis=1)
+        if hasattr(grid, '_mrt_basis'):
+            grid.mrt_matrix = np.array(_gram_schmidt_int(grid._mrt_basis()), dtype=np.int64)
+            grid.mrt_norms = (grid.mrt_matrix * grid.mrt_matrix).sum(axis=1)
         grid.weights_float = np.array([float(w) for w in grid.weights])
         # weights of the entropy function H = sum_i f_i ln(f_i / w_i) of the entropic model: products of the D1Q3 weights
         # {-1: 1/6, 0: 2/3, 1: 1/6} unless the lattice defines its own (reference sym.py:951-1024) -- D2Q9 is a product
@@ -173,6 +198,8 @@ def relaxation_time(viscosity):
 def mrt_rates(grid, visc):
     """Per-moment relaxation rates with the viscosity-dependent ones filled in
     (inv_tau = 1 / (0.5 + 3 visc), reference sym.py:110,371)."""
+    if not hasattr(grid, 'mrt_collision'):
+        return [0.0] * grid.Q
     inv_tau = 1.0 / (0.5 + 3.0 * visc)
     return [inv_tau if c is None else float(c) for c in grid.mrt_collision]
 
@@ -217,7 +244,8 @@ def lookup_grid(name):
     for g in KNOWN_GRIDS:
         if g.__name__ == name:
             return g
-    raise ValueError('unsupported grid %s (the HIP backend implements D2Q9 and D3Q19)' % name)
+    raise ValueError('unsupported grid %s (the HIP backend implements D2Q9, D3Q19 and, for the BGK collision of a single '
+                     'fluid, D3Q15 and D3Q27)' % name)
 
 
 class _Symbols(object):

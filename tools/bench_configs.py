@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -275,6 +275,15 @@ def main():
                          visc=1.0 / 6.0, tau_phi=0.9, tau_theta=1.1, G11=-0.1, G12=0.3, G13=0.25, G22=-0.09, G23=0.35, G33=-0.06,
                          access_pattern=pattern, max_iters=int(600 * it), benchmark_sample_from=int(200 * it)), nbytes))
                 os.environ.pop('SLF_SC_FUSED', None)
+    # config 13 (only with --only): the periodic box of config 1 on D3Q15 (13a two-copy, 13b in-place) and D3Q27 (13c, 13d):
+    # csrc/slf_lat.hip.  Bytes per update: 2 Q populations of 4 bytes, 120 and 216
+    for cid, grid, pattern in (('13a', 'D3Q15', 'AB'), ('13b', 'D3Q15', 'AA'), ('13c', 'D3Q27', 'AB'), ('13d', 'D3Q27', 'AA')):
+        if cid in only:
+            q = int(grid[3:])
+            res.append(run('%s: %s BGK periodic box 256^3 (%s)' % (cid, grid, pattern), BoxSim, LBGeometry3D,
+                           dict(lat_nx=256, lat_ny=256, lat_nz=256, periodic_x=True, periodic_y=True, periodic_z=True,
+                                visc=1.0 / 6.0, access_pattern=pattern, grid=grid, max_iters=int(3000 * it),
+                                benchmark_sample_from=int(1000 * it)), 2 * q * 4))
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
