@@ -19,7 +19,8 @@
 //   f_0   = rho - ((f_1 + f_2) + ...),  g_0 = phi - ((g_1 + g_2) + ...)
 //   tau0  = tau_b + ((phi + 1) (tau_a - tau_b)) 0.5, tau_b below phi = -1, tau_a above phi = 1;  f += (1 / tau0) (feq - f)
 // Wave-uniform choices (node map or none, wetting order, which rims have zero gradients) are run-time values: one
-// instantiation per lattice, precision and streaming mode for each of the three kernels.
+// instantiation per lattice, precision and streaming mode for each of the three kernels.  Node position and kind (sc_node,
+// nn_kind), loads and stores (sc_load, sc_store) and the launch shape (nn_shape) are slf_nn.h's.
 #include <string.h>
 #include "slf_nn.h"
 
@@ -176,21 +177,17 @@ __global__ void __launch_bounds__(1024) fe_macro_kernel(const FeParams<R> p) {
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, g.lat_nx - 2, live, p.xcd_shift);
   if (!live) return;
-  int kind = NK_FLUID;
-  uint32_t code = 0;
-  if (p.map) {
-    code = p.map[n.gi];
-    kind = node_kind(g.type_lut, g.type_mask, code);
-  }
-  if (kind_is_wet(kind)) {
+  NnKind nk;
+  nn_kind<true>(g, p.map, n.gi, live, nk);       // every kind stays: wall nodes get their phi here
+  if (nk.wet) {
     R f[L::Q];
     sc_load<L, R, PROP>(f, p.d_in, g.dist_size, n);
     p.phi[n.gi] = density<L, R>(f);
-  } else if (kind == NK_FULL_BB) {
+  } else if (nk.kind == NK_FULL_BB) {
     // wetting walls (Kusumaatmaja, option 2): phi of the fluid node `order` nodes along the wall's normal, minus
     // order * (the prescribed gradient); orientation 0: the wall's own populations.  A helper node outside the real
     // nodes was refused when the simulation was set up (lb_binary.py).
-    const int o = (int)(code >> g.orient_shift);
+    const int o = (int)(nk.code >> g.orient_shift);
     int hx = n.gx, hy = n.gy, hz = n.gz;
     if (o >= 1 && o <= 2 * L::dim) {
       int ex = 0, ey = 0, ez = 0;       // the normal: a chain of selects (a table indexed at run time would live in LDS)
@@ -218,27 +215,14 @@ __global__ void __launch_bounds__(1024) fe_sweep_kernel(const FeParams<R> p) {
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
-  const uint32_t gi = n.gi;
-  int kind = NK_FLUID;
-  bool active = live;
-  if (p.map) {
-    kind = node_kind(g.type_lut, g.type_mask, p.map[gi]);
-    if constexpr (!ROW) {
-      if (kind_is_excluded(kind)) return;
-    } else {
-      active = live && !kind_is_excluded(kind);
-    }
-  }
-  const bool wet = kind_is_wet(kind) && active;
+  NnKind nk;
+  if (!nn_kind<ROW>(g, p.map, n.gi, live, nk)) return;
   const size_t ds = g.dist_size;
   const uint32_t lo = n.xi * (uint32_t)sizeof(R);
 
   R f[L::Q];
   sc_load<L, R, PROP>(f, p.d_in, ds, n);
-  if (wet) {
+  if (nk.wet) {
     const R phi = *at_byte(uniform_base((const R*)p.phi + n.row), lo);
     R fe[L::Q];
     R omega;
@@ -268,8 +252,8 @@ __global__ void __launch_bounds__(1024) fe_sweep_kernel(const FeParams<R> p) {
     }
     static_for<0, L::Q>([&](auto I) { f[I] = f[I] + omega * (fe[I] - f[I]); });
   }
-  if (kind == NK_FULL_BB) bounce_back<L, R>(f);
-  sc_store<L, R, PROP, true, ROW>(g, f, p.d_out, ds, n, nx, live, active);
+  if (nk.kind == NK_FULL_BB) bounce_back<L, R>(f);
+  sc_store<L, R, PROP, true, ROW>(g, f, p.d_out, ds, n, nx, live, nk.active);
 }
 
 // Both lattices at their equilibria of the host's rho, phi, v on every node of the arrays; Laplacian and gradient of the
@@ -343,13 +327,10 @@ hipError_t launch_fe_macro(const KernelSelector& sel, Prop prop, const Geometry&
     FeParams<R> p = make_fe<R>(g, fe, a, y0, z0);
     p.d_in = (const R*)a.dist_out;
     p.d_out = nullptr;
-    const int nx = g.lat_nx - 2;
-    int bx = ((nx + 63) / 64) * 64;
-    if (bx > 1024) bx = 256;
-    const dim3 grid((nx + bx - 1) / bx, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-    if (grid.y == 0 || grid.z == 0) return hipSuccess;
-    if (prop == PROP_AA_ODD) hipLaunchKernelGGL((fe_macro_kernel<L, R, PROP_AA_ODD>), grid, dim3(bx, 1, 1), 0, s, p);
-    else hipLaunchKernelGGL((fe_macro_kernel<L, R, PROP_AB>), grid, dim3(bx, 1, 1), 0, s, p);
+    const NNShape sh = nn_shape<L>(g, false, prop, y0, y1, z0, z1, nn_pass_block_x(g.lat_nx - 2));
+    if (sh.empty) return hipSuccess;
+    if (prop == PROP_AA_ODD) hipLaunchKernelGGL((fe_macro_kernel<L, R, PROP_AA_ODD>), sh.grid, sh.block, 0, s, p);
+    else hipLaunchKernelGGL((fe_macro_kernel<L, R, PROP_AB>), sh.grid, sh.block, 0, s, p);
     return hipGetLastError();
   });
 }
@@ -361,15 +342,12 @@ hipError_t launch_fe_sweep(const KernelSelector& sel, int which, Prop prop, cons
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;
     FeParams<R> p = make_fe<R>(g, fe, a, y0, z0);
-    const int nx = g.lat_nx - 2;
-    const bool row = L::dim == 3 && prop != PROP_AA_EVEN;       // the x-streaming steps in 3-D: whole rows (or equal segments)
-    const int bx = row ? row_block_x(nx) : block_x;
-    const dim3 grid((nx + bx - 1) / bx, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-    if (grid.y == 0 || grid.z == 0) return hipSuccess;
-    p.xcd_shift = xcd_shift_for(grid.y, grid.x);      // the stencil's phi rows: neighbouring rows on one XCD
+    const NNShape sh = nn_shape<L>(g, true, prop, y0, y1, z0, z1, block_x);      // the x-streaming steps in 3-D: whole rows
+    if (sh.empty) return hipSuccess;
+    p.xcd_shift = sh.xcd_shift;      // the stencil's phi rows: neighbouring rows on one XCD
     hipError_t e = hipErrorInvalidValue;
     pick<int, 0, 1>(which == 0 ? 0 : 1, [&](auto K) { pick_prop(prop, [&](auto P) {
-      hipLaunchKernelGGL((fe_sweep_kernel<L, R, K, P>), grid, dim3(bx, 1, 1), 0, s, p);
+      hipLaunchKernelGGL((fe_sweep_kernel<L, R, K, P>), sh.grid, sh.block, 0, s, p);
       e = hipGetLastError();
     }); });
     return e;

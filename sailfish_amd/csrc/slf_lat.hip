@@ -8,8 +8,9 @@
 //
 // The sweep has the shape of fe_sweep_kernel (slf_fe.hip): one workgroup per (y, z) row -- or per x-segment of one --
 // that streams through row_push() in the two-copy pattern and the odd in-place step, and into the node's own opposite
-// slots in the even in-place step.  Everything per node is a piece of slf_node.h / slf_sweep.h / slf_nn.h templated on the
-// lattice; nothing here knows a direction by number.
+// slots in the even in-place step.  Everything per node is a piece of slf_node.h / slf_sweep.h / slf_nn.h (sc_node, nn_kind,
+// sc_load, sc_store) templated on the lattice; nothing here knows a direction by number.  The launch shape is nn_shape()
+// with this unit's bound on threads per workgroup.
 //
 // Operation order per node (the arithmetic of the D3Q19 general path, node_update<..., GENERAL, BCL = 0> plus its half-way
 // wall, with other tables; the numpy twin tests/_lat_twin.py restates it):
@@ -46,28 +47,14 @@ __global__ void __launch_bounds__((lat_max_threads<L, R>())) lat_sweep_kernel(co
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
-  int kind = NK_FLUID;
-  uint32_t code = 0;
-  bool active = live;
-  if (p.map) {
-    code = p.map[n.gi];
-    kind = node_kind(g.type_lut, g.type_mask, code);
-    if constexpr (!ROW) {
-      if (kind_is_excluded(kind)) return;
-    } else {
-      active = live && !kind_is_excluded(kind);
-    }
-  }
-  const bool wet = kind_is_wet(kind) && active;
+  NnKind nk;
+  if (!nn_kind<ROW>(g, p.map, n.gi, live, nk)) return;
   const size_t ds = g.dist_size;
   const uint32_t lo = n.xi * (uint32_t)sizeof(R);
 
   R f[L::Q];
   sc_load<L, R, PROP>(f, p.din, ds, n);
-  if (wet) {
+  if (nk.wet) {
     R rho, v[3];
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (p.relaxation_enabled) bgk_relax<L, R>(f, rho, v, p.cp);
@@ -79,9 +66,9 @@ __global__ void __launch_bounds__((lat_max_threads<L, R>())) lat_sweep_kernel(co
       *at_byte(uniform_base(p.vz + n.row), lo) = v[2];
     }
   }
-  if (kind == NK_FULL_BB) bounce_back<L, R>(f);
-  if (kind == NK_HALF_BB && active) half_bb_store<L, R, PROP, false>(p, f, (int)(code >> g.orient_shift), n.gi, n.gi, n.ox, n.oy, n.oz);
-  sc_store<L, R, PROP, true, ROW>(g, f, p.dout, ds, n, nx, live, active);
+  if (nk.kind == NK_FULL_BB) bounce_back<L, R>(f);
+  if (nk.kind == NK_HALF_BB && nk.active) half_bb_store<L, R, PROP, false>(p, f, (int)(nk.code >> g.orient_shift), n.gi, n.gi, n.ox, n.oy, n.oz);
+  sc_store<L, R, PROP, true, ROW>(g, f, p.dout, ds, n, nx, live, nk.active);
 }
 
 // ---------------------------------------------------------------------------
@@ -92,15 +79,6 @@ static hipError_t pick_lat(const KernelSelector& sel, F&& f) {
   if (sel.lattice == D3Q15::id) return pick_real(sel, [&](auto r) { return f(LR<D3Q15, decltype(r)>{}); });
   if (sel.lattice == D3Q27::id) return pick_real(sel, [&](auto r) { return f(LR<D3Q27, decltype(r)>{}); });
   return hipErrorInvalidValue;
-}
-
-// workgroup width of the row steps: row_block_x() while it fits the kernel's launch bound, else equal segments that do
-static int lat_block_x(int nx, int max_threads) {
-  const int bx = row_block_x(nx);
-  if (bx <= max_threads) return bx;
-  const int waves = (nx + 63) / 64, per = max_threads / 64;
-  const int nseg = (waves + per - 1) / per;
-  return ((waves + nseg - 1) / nseg) * 64;
 }
 
 hipError_t launch_lat_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
@@ -115,14 +93,11 @@ hipError_t launch_lat_sweep(const KernelSelector& sel, Prop prop, const Geometry
     b.rows = nullptr;
     b.slots = nullptr;
     const SweepParams<L, R> p = make_params<L, R>(g, ph, b, y0, z0);
-    const int nx = g.lat_nx - 2;
-    constexpr int MAXT = lat_max_threads<L, R>();
-    const int bx = prop != PROP_AA_EVEN ? lat_block_x(nx, MAXT) : (block_x < MAXT ? block_x : MAXT);
-    const dim3 grid((nx + bx - 1) / bx, y1 - y0, z1 - z0);
-    if (grid.y == 0 || grid.z == 0) return hipSuccess;
+    const NNShape sh = nn_shape<L>(g, true, prop, y0, y1, z0, z1, block_x, lat_max_threads<L, R>());
+    if (sh.empty) return hipSuccess;
     hipError_t e = hipErrorInvalidValue;
     pick_prop(prop, [&](auto P) {
-      hipLaunchKernelGGL((lat_sweep_kernel<L, R, P>), grid, dim3(bx, 1, 1), 0, s, p);
+      hipLaunchKernelGGL((lat_sweep_kernel<L, R, P>), sh.grid, sh.block, 0, s, p);
       e = hipGetLastError();
     });
     return e;

@@ -1,7 +1,14 @@
-// What the sweeps of the models with nearest-neighbour fields share (binary / single-component Shan-Chen: slf_sc.hip; the
-// free-energy binary fluid: slf_fe.hip; the ternary Shan-Chen mixture: slf_sc3.hip): a node's row and lane position, the
-// cached read of a field at a neighbouring node, the pseudopotential, and the loads and stores of one lattice's populations
-// for the three streaming modes.
+// What the sweeps that read a neighbouring field or stream through row_push() share (binary / single-component Shan-Chen:
+// slf_sc.hip; the ternary Shan-Chen mixture: slf_sc3.hip; the free-energy binary fluid: slf_fe.hip; D3Q15 / D3Q27:
+// slf_lat.hip).  Per node, in the order a sweep uses them:
+//   sc_node                          row and lane position
+//   nn_kind                          the node's code and kind, whether it is swept at all and whether it collides
+//   sc_load, sc_store                one lattice's populations in the three streaming modes
+//   sc_neighbour                     cached read of a field at a neighbouring node
+//   sc_psi, sc_with_potential        the pseudopotential
+//   sc_stencil                       the stencil sum S_d of one field, of which every Shan-Chen force is made
+//   sc_add_momentum                  one lattice's share of the common velocity
+// and on the host nn_pass_block_x / nn_shape, the launch shape of every launcher of the four units.
 #pragma once
 #include "slf_dispatch.h"
 #include "slf_rowpush.h"
@@ -39,6 +46,38 @@ __device__ __forceinline__ ScNode sc_node(const Geometry& g, int y0, int z0, int
   return n;
 }
 
+// What a sweep does with a node once its position is known.  Without a node map every real node is a fluid node.  MAP: -1
+// the pointer decides at run time (wave-uniform), else a kernel's compile-time GENERAL: 1 = there is a map, 0 = none.  (Not
+// GENERAL ? p.map : nullptr with a test of the pointer: the branch that leaves in the GENERAL kernels cost the D3Q19 f32
+// sc_sweep_kernels two VGPRs and a resident wave.)  ROW: one workgroup = one whole row streaming through row_push(); every
+// thread stays until the end (barrier inside), excluded nodes and idle lanes are merely inactive.  Otherwise they leave:
+// false = nothing to do for this lane.
+struct NnKind {
+  uint32_t code;      // the node map's entry (orientation: code >> g.orient_shift)
+  int kind;
+  bool active, wet;   // swept at all | collides
+};
+template <bool ROW, int MAP = -1>
+__device__ __forceinline__ bool nn_kind(const Geometry& g, const uint32_t* map, uint32_t gi, bool live, NnKind& k) {
+  if constexpr (!ROW) {
+    if (!live) return false;
+  }
+  k.code = 0;
+  k.kind = NK_FLUID;
+  k.active = live;
+  if (MAP > 0 || (MAP < 0 && map)) {
+    k.code = map[gi];
+    k.kind = node_kind(g.type_lut, g.type_mask, k.code);
+    if constexpr (!ROW) {
+      if (kind_is_excluded(k.kind)) return false;
+    } else {
+      k.active = live && !kind_is_excluded(k.kind);
+    }
+  }
+  k.wet = kind_is_wet(k.kind) && k.active;
+  return true;
+}
+
 // element (row + yz-offset of direction I, forward or backward) + (xi shifted along x) of a node-indexed array
 template <class L, int I, class T>
 __device__ __forceinline__ const SLF_GLOBAL T* sc_neighbour(const T* base, const ScNode& n, bool forward) {
@@ -66,6 +105,57 @@ template <class F>
 __device__ __forceinline__ void sc_with_potential(int potential, F&& body) {
   if (potential == 0) body(std::integral_constant<int, 0>{});
   else body(std::integral_constant<int, 1>{});
+}
+
+// What an edge lane knows about its connected x face (sc_edge(), slf_sc.hip): which face, its receive plane, and where
+// the stencil values of field 0 that sit across the face lie in it; those of field J lie J * fstride further on.
+template <class L, class R>
+struct ScEdge {
+  bool lo, hi;
+  const R* plane;
+  int off[count_x_dirs<L>()];
+  int fstride;
+};
+
+// S[d] += sum_i psi(field(x + e_i)) (+-w_i) over the directions with e_i,d != 0, i = 1 .. Q - 1: the neighbour values come
+// through the caches (every value is used by Q - 1 nodes).  XF: n is the node sc_edge() made, whose own loads stay inside
+// the row, and the values across the face come from the receive plane.  The one place this sum is written; the numpy
+// twin tests/_scn_twin.py restates its order.
+template <class L, class R, int POT, bool XF = false>
+__device__ __forceinline__ void sc_stencil(const R* field, const ScNode& n, R (&S)[3], const ScEdge<L, R>* e = nullptr,
+                                           int J = 0) {
+  [[maybe_unused]] R ev[count_x_dirs<L>()];
+  if constexpr (XF) {
+    static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = (R)0; });
+    if (e->lo || e->hi) {
+      static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = e->plane[e->off[K] + J * e->fstride]; });
+    }
+  }
+  static_for<1, L::Q>([&](auto I) {
+    R nb = *sc_neighbour<L, I>(field, n, true);
+    if constexpr (XF && L::ex(I) > 0) nb = e->hi ? ev[x_dir_rank<L, I>()] : nb;
+    if constexpr (XF && L::ex(I) < 0) nb = e->lo ? ev[x_dir_rank<L, I>()] : nb;
+    const R psi = sc_psi<R, POT>(nb);
+    static_for<0, L::dim>([&](auto D) {
+      constexpr int ec = e_comp<L>(I, D);
+      if constexpr (ec > 0) S[D] = S[D] + psi * Weights<L, R>::w(I);
+      if constexpr (ec < 0) S[D] = S[D] + psi * ((R)0 - Weights<L, R>::w(I));
+    });
+  });
+}
+
+// One lattice's share of the common velocity  sum_k j_k / tau_k  over  sum_k rho_k / tau_k  (binary_shan_chen.mako:69-83,
+// ternary_shan_chen.mako:75-95): v = (1/tau_0) j_0, then v = v + (1/tau_k) j_k; the caller divides by the total.
+template <class L, class R, bool FIRST>
+__device__ __forceinline__ void sc_add_momentum(R (&v)[3], R omega, const R (&f)[L::Q]) {
+  const R j0 = omega * momentum<L, R, 0>(f);
+  const R j1 = omega * momentum<L, R, 1>(f);
+  v[0] = FIRST ? j0 : v[0] + j0;
+  v[1] = FIRST ? j1 : v[1] + j1;
+  if constexpr (L::dim == 3) {
+    const R j2 = omega * momentum<L, R, 2>(f);
+    v[2] = FIRST ? j2 : v[2] + j2;
+  }
 }
 
 // INDIRECT (reference subdomain_runner.py:829-878, kernel_common.mako:140-167; serves NNSubdomainRunner too): the
@@ -120,6 +210,40 @@ __device__ __forceinline__ void sc_store(const Geometry& g, R (&f)[L::Q], R* dou
       }
     });
   }
+}
+
+// ---- host: the launch shape ----
+// Block width of the pass kernels (densities, velocity): the whole row in one workgroup where it fits
+static inline int nn_pass_block_x(int nx) {
+  const int bx = ((nx + 63) / 64) * 64;
+  return bx > 1024 ? 256 : bx;
+}
+
+// row: whole-row workgroups (or equal x-segments) + aligned stores for the x-streaming steps in 3-D (as slf_row.hip), where
+// the caller's kernels have that form (row_ok); block_x is then the row's, not the caller's.  max_threads: the kernel's
+// launch bound where it is below row_block_x()'s 1024 -- rows beyond it are cut into equal segments of whole waves that fit.
+struct NNShape {
+  dim3 grid, block;
+  bool row, empty;
+  int xcd_shift;      // rows that share field rows through the L2: neighbouring rows on one XCD (xcd_row(), slf_sweep.h)
+};
+template <class L>
+static NNShape nn_shape(const Geometry& g, bool row_ok, Prop prop, int y0, int y1, int z0, int z1, int block_x,
+                        int max_threads = 0) {
+  const int nx = g.lat_nx - 2;
+  NNShape sh;
+  sh.row = row_ok && L::dim == 3 && prop != PROP_AA_EVEN;
+  if (sh.row) block_x = row_block_x(nx);
+  if (max_threads && block_x > max_threads) {
+    const int waves = (nx + 63) / 64, per = max_threads / 64;
+    const int nseg = (waves + per - 1) / per;
+    block_x = sh.row ? ((waves + nseg - 1) / nseg) * 64 : max_threads;
+  }
+  sh.block = dim3(block_x, 1, 1);
+  sh.grid = dim3((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
+  sh.empty = sh.grid.y == 0 || sh.grid.z == 0;
+  sh.xcd_shift = xcd_shift_for(sh.grid.y, sh.grid.x);
+  return sh;
 }
 
 }  // namespace slf

@@ -14,6 +14,11 @@
 // reads the 18 neighbour densities of the *other* field through the cache hierarchy (each value is
 // reused by 18 nodes; rows of a workgroup are contiguous), the acceleration F_k / rho_k enters the BGK
 // collision through Guo forcing exactly like a body force (relaxation_common.mako:56-64,110-149).
+//
+// From slf_nn.h: the node prologue (nn_kind), the stencil sum (sc_stencil), the common velocity (sc_add_momentum), loads
+// and stores, the launch shape (nn_shape).  Here: the aligned pull (sc_pull_rows), the acceleration of one lattice made
+// of stencil sums (sc_accel), and everything about the x-face planes -- sc_face_receive / sc_face_send_own_row,
+// sc_pull_node, sc_load_lattice (one lattice's populations under planes), sc_edge.
 #include "slf_nn.h"
 
 namespace slf {
@@ -112,34 +117,6 @@ __device__ __forceinline__ void sc_pull_rows(R (&fa)[L::Q], R (&fb)[L::Q], const
   });
 }
 
-// Shan-Chen acceleration of one lattice (sc_calculate_force, shan_chen.mako:9-27): the 18 neighbour values of each
-// coupled field come through the caches (every value is used by 18 nodes).
-template <class L, class R, int NFIELDS>
-__device__ __forceinline__ void sc_accel(const R* const (&fields)[2], const R (&G)[2], R rho, int potential, const ScNode& n,
-                                         R (&a)[3]) {
-  sc_with_potential(potential, [&](auto POT) {
-    static_for<0, NFIELDS>([&](auto J) {
-      const R cc = G[J];
-      if (cc != (R)0) {
-        R force[3] = {(R)0, (R)0, (R)0};
-        static_for<1, L::Q>([&](auto I) {
-          const R psi = sc_psi<R, POT>(*sc_neighbour<L, I>(fields[J], n, true));
-          static_for<0, L::dim>([&](auto D) {
-            constexpr int e = e_comp<L>(I, D);
-            if constexpr (e > 0) force[D] = force[D] + psi * Weights<L, R>::w(I);
-            if constexpr (e < 0) force[D] = force[D] + psi * ((R)0 - Weights<L, R>::w(I));
-          });
-        });
-        const R psi_loc = sc_psi<R, POT>(rho);
-        static_for<0, L::dim>([&](auto D) {
-          force[D] = force[D] * (((R)0 - psi_loc) * cc);
-          a[D] = a[D] + force[D];
-        });
-      }
-    });
-  });
-}
-
 // ---- connected x faces (XF): the binary model over the x-face planes of a 1-D decomposition along x ----
 // Populations: per lattice the single-fluid scheme (slf_sweep.h x_face_receive / x_face_send_own_row, row_push's xsend).
 // Densities: the force stencil of an edge node reads the neighbour subdomain's first / last column; the pass in front
@@ -198,6 +175,22 @@ __device__ __forceinline__ ScNode sc_pull_node(const Geometry& g, const ScNode& 
   }
   return m;
 }
+// The populations of lattice K (din) as this step reads them: pulled past the ghost column where a plane delivers (odd
+// in-place step, fluid-only), else the plain or indirect load; then what entered through the receive planes (RECV = false:
+// the caller receives itself, sc_fused_kernel).
+template <class L, class R, int PROP, bool GENERAL, bool INDIRECT, bool XF, bool RECV = true>
+__device__ __forceinline__ void sc_load_lattice(R (&f)[L::Q], const ScParams<L, R>& p, int K, const R* din, const ScNode& n,
+                                                int nx, bool live, uint32_t si = 0) {
+  const Geometry& g = p.g;
+  if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
+    sc_load<L, R, PROP, INDIRECT>(f, din, g.dist_size, sc_pull_node(g, n, nx, p.xrecv[K][0] != nullptr, p.xrecv[K][1] != nullptr));
+  } else {
+    sc_load<L, R, PROP, INDIRECT>(f, din, g.dist_size, n, p.nodes, si);
+  }
+  if constexpr (XF && RECV) {
+    if (live) sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[K], f, n.gx, nx, face_rows<L>(g, n.gy, n.gz));
+  }
+}
 
 // row of (y, z) in a density plane, and the offsets to its y / z neighbours (wrapped like the arrays)
 struct ScMacroRows {
@@ -222,14 +215,7 @@ __device__ __forceinline__ void sc_macro_offsets(const ScMacroRows& mr, int (&of
   });
 }
 
-// What an edge lane knows about its face: which face, its receive plane, and where the five stencil values per field lie.
-template <class L, class R>
-struct ScEdge {
-  bool lo, hi;
-  const R* plane;
-  int off[count_x_dirs<L>()];
-  int fstride;
-};
+// the ScEdge (slf_nn.h) of a lane, and in ns its node with the x offsets that would leave through a connected face zeroed
 template <class L, class R>
 __device__ __forceinline__ ScEdge<L, R> sc_edge(const ScParams<L, R>& p, const ScNode& n, int nx, bool live, ScNode& ns) {
   const Geometry& g = p.g;
@@ -248,36 +234,26 @@ __device__ __forceinline__ ScEdge<L, R> sc_edge(const ScParams<L, R>& p, const S
   e.fstride = mr.fstride;
   return e;
 }
-// sc_accel() of one field for a node that may sit on a connected x face (single-component model): the same sum in the
-// same order, the values across the face from the receive plane
-template <class L, class R>
-__device__ __forceinline__ void sc_accel_edge(const R* field, R G, R rho, int potential, const ScNode& ns,
-                                              const ScEdge<L, R>& e, R (&a)[3]) {
+
+// Shan-Chen acceleration of one lattice (sc_calculate_force, shan_chen.mako:9-27), before the division by its density:
+// a += S_j ((0 - psi(rho)) G_j) for the first NFIELDS fields j with G_j != 0, S_j from sc_stencil() (slf_nn.h); under XF
+// for a node that may sit on a connected x face (n and e from sc_edge())
+template <class L, class R, int NFIELDS, bool XF = false>
+__device__ __forceinline__ void sc_accel(const R* const (&fields)[2], const R (&G)[2], R rho, int potential,
+                                         const ScNode& n, R (&a)[3], const ScEdge<L, R>* e = nullptr) {
   sc_with_potential(potential, [&](auto POT) {
-    if (G != (R)0) {
-      R ev[count_x_dirs<L>()];
-      static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = (R)0; });
-      if (e.lo || e.hi) {
-        static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = e.plane[e.off[K]]; });
-      }
-      R force[3] = {(R)0, (R)0, (R)0};
-      static_for<1, L::Q>([&](auto I) {
-        R nb = *sc_neighbour<L, I>(field, ns, true);
-        if constexpr (L::ex(I) > 0) nb = e.hi ? ev[x_dir_rank<L, I>()] : nb;
-        if constexpr (L::ex(I) < 0) nb = e.lo ? ev[x_dir_rank<L, I>()] : nb;
-        const R psi = sc_psi<R, POT>(nb);
+    static_for<0, NFIELDS>([&](auto J) {
+      const R cc = G[J];
+      if (cc != (R)0) {
+        R force[3] = {(R)0, (R)0, (R)0};
+        sc_stencil<L, R, POT, XF>(fields[J], n, force, e, J);
+        const R psi_loc = sc_psi<R, POT>(rho);
         static_for<0, L::dim>([&](auto D) {
-          constexpr int ec = e_comp<L>(I, D);
-          if constexpr (ec > 0) force[D] = force[D] + psi * Weights<L, R>::w(I);
-          if constexpr (ec < 0) force[D] = force[D] + psi * ((R)0 - Weights<L, R>::w(I));
+          force[D] = force[D] * (((R)0 - psi_loc) * cc);
+          a[D] = a[D] + force[D];
         });
-      });
-      const R psi_loc = sc_psi<R, POT>(rho);
-      static_for<0, L::dim>([&](auto D) {
-        force[D] = force[D] * (((R)0 - psi_loc) * G);
-        a[D] = a[D] + force[D];
-      });
-    }
+      }
+    });
   });
 }
 
@@ -302,29 +278,12 @@ __global__ void __launch_bounds__(1024) sc_macro_kernel(const ScParams<L, R> p) 
     const int kind = node_kind(g.type_lut, g.type_mask, code);
     if (!kind_is_wet(kind)) return;
   }
-  const size_t ds = g.dist_size;
   R f[L::Q];
-  // lattice 0
-  if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, ds, sc_pull_node(g, n, g.lat_nx - 2, p.xrecv[0][0] != nullptr, p.xrecv[0][1] != nullptr));
-  } else {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, ds, n, p.nodes, si);
-  }
-  if constexpr (XF) sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[0], f, n.gx, g.lat_nx - 2, face_rows<L>(g, n.gy, n.gz));
+  sc_load_lattice<L, R, PROP, GENERAL, INDIRECT, XF>(f, p, 0, p.d_in, n, g.lat_nx - 2, live, si);
   const R rho0 = density<L, R>(f);
   R v[3] = {(R)0, (R)0, (R)0};
-  if constexpr (VOUT) {
-    v[0] = p.omega[0] * momentum<L, R, 0>(f);
-    v[1] = p.omega[0] * momentum<L, R, 1>(f);
-    if constexpr (L::dim == 3) v[2] = p.omega[0] * momentum<L, R, 2>(f);
-  }
-  // lattice 1
-  if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
-    sc_load<L, R, PROP, INDIRECT>(f, (const R*)p.d_out, ds, sc_pull_node(g, n, g.lat_nx - 2, p.xrecv[1][0] != nullptr, p.xrecv[1][1] != nullptr));
-  } else {
-    sc_load<L, R, PROP, INDIRECT>(f, (const R*)p.d_out, ds, n, p.nodes, si);
-  }
-  if constexpr (XF) sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[1], f, n.gx, g.lat_nx - 2, face_rows<L>(g, n.gy, n.gz));
+  if constexpr (VOUT) sc_add_momentum<L, R, true>(v, p.omega[0], f);
+  sc_load_lattice<L, R, PROP, GENERAL, INDIRECT, XF>(f, p, 1, (const R*)p.d_out, n, g.lat_nx - 2, live, si);
   const R rho1 = density<L, R>(f);
   p.rho0[gi] = rho0;
   p.rho1[gi] = rho1;
@@ -335,10 +294,7 @@ __global__ void __launch_bounds__(1024) sc_macro_kernel(const ScParams<L, R> p) 
     if (p.msend[1] && n.gx == g.lat_nx - 2) { p.msend[1][mrow] = rho0; p.msend[1][mrow + g.arr_ny] = rho1; }
   }
   if constexpr (VOUT) {
-    v[0] = v[0] + p.omega[1] * momentum<L, R, 0>(f);
-    v[1] = v[1] + p.omega[1] * momentum<L, R, 1>(f);
-    if constexpr (L::dim == 3) v[2] = v[2] + p.omega[1] * momentum<L, R, 2>(f);
-    // common velocity: sum_k j_k / tau_k over sum_k rho_k / tau_k (binary_shan_chen.mako:69-83)
+    sc_add_momentum<L, R, false>(v, p.omega[1], f);
     const R total = p.omega[0] * rho0 + p.omega[1] * rho1;
     p.vx[gi] = v[0] / total;
     p.vy[gi] = v[1] / total;
@@ -370,27 +326,14 @@ __global__ void __launch_bounds__(1024) sc_sweep_kernel(const ScParams<L, R> p) 
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
   const uint32_t gi = n.gi;
+  NnKind nk;
+  if (!nn_kind<ROW, GENERAL>(g, p.map, gi, live, nk)) return;
   uint32_t si = gi;
   if constexpr (INDIRECT) {
     si = p.nodes[gi];
     if (si == INVALID_NODE) return;
   }
-  int kind = NK_FLUID;
-  bool active = live;
-  if constexpr (GENERAL) {
-    const uint32_t code = p.map[gi];
-    kind = node_kind(g.type_lut, g.type_mask, code);
-    if constexpr (!ROW) {
-      if (kind_is_excluded(kind)) return;
-    } else {
-      active = live && !kind_is_excluded(kind);
-    }
-  }
-  const bool wet = kind_is_wet(kind) && active;
   const size_t ds = g.dist_size;
 
   R f[L::Q];
@@ -398,7 +341,7 @@ __global__ void __launch_bounds__(1024) sc_sweep_kernel(const ScParams<L, R> p) 
   const R* own = (K == 0) ? p.rho0 : p.rho1;
   const R rho = own[gi];
   R a[3] = {(R)0, (R)0, (R)0};
-  if (wet) {
+  if (nk.wet) {
     const R* const fields[2] = {p.rho0, p.rho1};
     sc_accel<L, R, 2>(fields, p.G, rho, p.potential, n, a);
     static_for<0, L::dim>([&](auto D) { a[D] = a[D] / rho; });
@@ -411,11 +354,9 @@ __global__ void __launch_bounds__(1024) sc_sweep_kernel(const ScParams<L, R> p) 
   v[1] = p.vy[gi];
   v[2] = (R)0;
   if constexpr (L::dim == 3) v[2] = p.vz[gi];
-  if constexpr (GENERAL) {
-    if (kind == NK_FULL_BB) bounce_back<L, R>(f);
-  }
-  if (wet) bgk_relax_accel<L, R>(f, rho, v, p.omega[K], p.guo_pref[K], false, true, a, p.force_edm != 0);
-  sc_store<L, R, PROP, GENERAL, ROW, INDIRECT>(g, f, p.d_out, ds, n, nx, live, active, p.nodes, si);
+  if (nk.kind == NK_FULL_BB) bounce_back<L, R>(f);
+  if (nk.wet) bgk_relax_accel<L, R>(f, rho, v, p.omega[K], p.guo_pref[K], false, true, a, p.force_edm != 0);
+  sc_store<L, R, PROP, GENERAL, ROW, INDIRECT>(g, f, p.d_out, ds, n, nx, live, nk.active, p.nodes, si);
 }
 
 // Both lattices in one pass.  The force on lattice k is  - psi(rho_k) sum_j G_kj S_j  with the stencil sums
@@ -448,6 +389,8 @@ sc_fused_kernel(const ScParams<L, R> p) {
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
+  // nn_kind() (slf_nn.h) written out: through the helper one of the spilling f64 D3Q19 instantiations or another takes 4-8
+  // more bytes of scratch per lane, whichever way its result is handed over (profiles/NOTES.md)
   if constexpr (!ROW) {
     if (!live) return;
   }
@@ -485,46 +428,14 @@ sc_fused_kernel(const ScParams<L, R> p) {
   R S[2][3] = {{(R)0, (R)0, (R)0}, {(R)0, (R)0, (R)0}};
   // XF: the stencil of an edge node reaches into the neighbour subdomain -- those five values per field come from the
   // receive plane; the lane's own loads stay inside the row (the ghost column's line is never fetched)
-  [[maybe_unused]] bool is_lo = false, is_hi = false;
-  [[maybe_unused]] const R* mplane = nullptr;
-  [[maybe_unused]] int moff[count_x_dirs<L>()];
   ScNode ns = n;
-  if constexpr (XF) {
-    is_lo = live && p.mrecv[0] && n.gx == 1;
-    is_hi = live && p.mrecv[1] && n.gx == nx;
-    if (is_lo) ns.ox.m = 0;
-    if (is_hi) ns.ox.p = 0;
-    const ScMacroRows mr = sc_macro_rows(g, n.gy, n.gz);
-    int offp[count_x_dirs<L>()], offm[count_x_dirs<L>()];
-    sc_macro_offsets<L, true>(mr, offp);
-    sc_macro_offsets<L, false>(mr, offm);
-    static_for<0, count_x_dirs<L>()>([&](auto K) { moff[K] = mr.row + (is_lo ? offm[K] : offp[K]); });
-    mplane = is_lo ? p.mrecv[0] : p.mrecv[1];
-  }
+  [[maybe_unused]] ScEdge<L, R> edge;
+  if constexpr (XF) edge = sc_edge<L, R>(p, n, nx, live, ns);
   if (wet) {
     const R* const fields[2] = {p.rho0, p.rho1};
     sc_with_potential(p.potential, [&](auto POT) {
       static_for<0, 2>([&](auto J) {
-        if (p.G[J] != (R)0 || p.G2[J] != (R)0) {
-          [[maybe_unused]] R ev[count_x_dirs<L>()];
-          if constexpr (XF) {
-            static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = (R)0; });
-            if (is_lo || is_hi) {
-              static_for<0, count_x_dirs<L>()>([&](auto K) { ev[K] = mplane[moff[K] + (int)J * g.arr_ny]; });
-            }
-          }
-          static_for<1, L::Q>([&](auto I) {
-            R nb = *sc_neighbour<L, I>(fields[J], ns, true);
-            if constexpr (XF && L::ex(I) > 0) nb = is_hi ? ev[x_dir_rank<L, I>()] : nb;
-            if constexpr (XF && L::ex(I) < 0) nb = is_lo ? ev[x_dir_rank<L, I>()] : nb;
-            const R psi = sc_psi<R, POT>(nb);
-            static_for<0, L::dim>([&](auto D) {
-              constexpr int e = e_comp<L>(I, D);
-              if constexpr (e > 0) S[J][D] = S[J][D] + psi * Weights<L, R>::w(I);
-              if constexpr (e < 0) S[J][D] = S[J][D] + psi * ((R)0 - Weights<L, R>::w(I));
-            });
-          });
-        }
+        if (p.G[J] != (R)0 || p.G2[J] != (R)0) sc_stencil<L, R, POT, XF>(fields[J], ns, S[J], &edge, J);
       });
     });
   }
@@ -535,14 +446,12 @@ sc_fused_kernel(const ScParams<L, R> p) {
     if constexpr (PULL) {
       static_assert(OWNV && ROW && PROP == PROP_AA_ODD, "the aligned pull serves the whole-row odd step");
       sc_pull_rows<L, R>(fa, fb, p.d_in, p.d_in2, ds, n, nx);
-    } else if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
-      sc_load<L, R, PROP>(fa, p.d_in, ds, sc_pull_node(g, n, nx, p.xrecv[0][0] != nullptr, p.xrecv[0][1] != nullptr));
-      sc_load<L, R, PROP>(fb, p.d_in2, ds, sc_pull_node(g, n, nx, p.xrecv[1][0] != nullptr, p.xrecv[1][1] != nullptr));
     } else {
-      sc_load<L, R, PROP>(fa, p.d_in, ds, n);
-      sc_load<L, R, PROP>(fb, p.d_in2, ds, n);
+      sc_load_lattice<L, R, PROP, GENERAL, false, XF, false>(fa, p, 0, p.d_in, n, nx, live);
+      sc_load_lattice<L, R, PROP, GENERAL, false, XF, false>(fb, p, 1, p.d_in2, n, nx, live);
     }
     if constexpr (XF) {
+      // both lattices loaded before either receives: receiving lattice 0 in between costs the f64 kernels 8 bytes of scratch
       if (live) {
         const FaceRows fr = face_rows<L>(g, n.gy, n.gz);
         sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[0], fa, n.gx, nx, fr);
@@ -550,13 +459,9 @@ sc_fused_kernel(const ScParams<L, R> p) {
       }
     }
     rho[0] = density<L, R>(fa);
-    vc[0] = p.omega[0] * momentum<L, R, 0>(fa);
-    vc[1] = p.omega[0] * momentum<L, R, 1>(fa);
-    if constexpr (L::dim == 3) vc[2] = p.omega[0] * momentum<L, R, 2>(fa);
+    sc_add_momentum<L, R, true>(vc, p.omega[0], fa);
     rho[1] = density<L, R>(fb);
-    vc[0] = vc[0] + p.omega[1] * momentum<L, R, 0>(fb);
-    vc[1] = vc[1] + p.omega[1] * momentum<L, R, 1>(fb);
-    if constexpr (L::dim == 3) vc[2] = vc[2] + p.omega[1] * momentum<L, R, 2>(fb);
+    sc_add_momentum<L, R, false>(vc, p.omega[1], fb);
     const R total = p.omega[0] * rho[0] + p.omega[1] * rho[1];
     vc[0] = vc[0] / total;
     vc[1] = vc[1] / total;
@@ -592,11 +497,9 @@ sc_fused_kernel(const ScParams<L, R> p) {
       const FaceRows fr = face_rows<L>(g, n.gy, n.gz);
       row_push<L, R, GENERAL, sc_nt<L>()>(g, f, K == 0 ? p.d_out : p.d_out2, ds, n.row, n.xi, n.gx, nx, live, active, n.oy,
                                           n.oz, p.xsend[K], &fr);
-    } else if constexpr (XF) {
-      sc_store<L, R, PROP, GENERAL, ROW>(g, f, K == 0 ? p.d_out : p.d_out2, ds, n, nx, live, active);
-      sc_face_send_own_row<L, R>(p.xsend[K], f, n.gx, nx, face_rows<L>(g, n.gy, n.gz));
     } else {
       sc_store<L, R, PROP, GENERAL, ROW>(g, f, K == 0 ? p.d_out : p.d_out2, ds, n, nx, live, active);
+      if constexpr (XF) sc_face_send_own_row<L, R>(p.xsend[K], f, n.gx, nx, face_rows<L>(g, n.gy, n.gz));
     }
   };
   if constexpr (OWNV) {
@@ -655,12 +558,7 @@ __global__ void __launch_bounds__(1024) scs_macro_kernel(const ScParams<L, R> p)
     if (kind_is_excluded(kind)) return;
   }
   R f[L::Q];
-  if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, g.dist_size, sc_pull_node(g, n, g.lat_nx - 2, p.xrecv[0][0] != nullptr, p.xrecv[0][1] != nullptr));
-  } else {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, g.dist_size, n, p.nodes, si);
-  }
-  if constexpr (XF) sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[0], f, n.gx, g.lat_nx - 2, face_rows<L>(g, n.gy, n.gz));
+  sc_load_lattice<L, R, PROP, GENERAL, INDIRECT, XF>(f, p, 0, p.d_in, n, g.lat_nx - 2, live, si);
   const R rho = density<L, R>(f);
   p.rho0[n.gi] = rho;
   if constexpr (XF) {
@@ -679,59 +577,34 @@ __global__ void __launch_bounds__(1024) scs_sweep_kernel(const ScParams<L, R> p)
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
   const uint32_t gi = n.gi;
+  NnKind nk;
+  if (!nn_kind<ROW, GENERAL>(g, p.map, gi, live, nk)) return;
   uint32_t si = gi;
   if constexpr (INDIRECT) {
     si = p.nodes[gi];
     if (si == INVALID_NODE) return;
   }
-  int kind = NK_FLUID;
-  bool active = live;
-  if constexpr (GENERAL) {
-    const uint32_t code = p.map[gi];
-    kind = node_kind(g.type_lut, g.type_mask, code);
-    if constexpr (!ROW) {
-      if (kind_is_excluded(kind)) return;
-    } else {
-      active = live && !kind_is_excluded(kind);
-    }
-  }
-  const bool wet = kind_is_wet(kind) && active;
   const size_t ds = g.dist_size;
   R f[L::Q];
-  if constexpr (XF && PROP == PROP_AA_ODD && !GENERAL) {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, ds, sc_pull_node(g, n, nx, p.xrecv[0][0] != nullptr, p.xrecv[0][1] != nullptr));
-  } else {
-    sc_load<L, R, PROP, INDIRECT>(f, p.d_in, ds, n, p.nodes, si);
-  }
-  if constexpr (XF) {
-    if (live) sc_face_receive<L, R, PROP == PROP_AA_ODD>(p.xrecv[0], f, n.gx, nx, face_rows<L>(g, n.gy, n.gz));
-  }
+  sc_load_lattice<L, R, PROP, GENERAL, INDIRECT, XF>(f, p, 0, p.d_in, n, nx, live, si);
   R rho, v[3];
   macro_standard<L, R>(f, false, rho, v);
   R a[3] = {(R)0, (R)0, (R)0};
-  if (wet) {
+  if (nk.wet) {
     const R* const fields[2] = {p.rho0, p.rho0};
-    if constexpr (XF) {
-      ScNode ns;
-      const ScEdge<L, R> edge = sc_edge<L, R>(p, n, nx, live, ns);
-      sc_accel_edge<L, R>(p.rho0, p.G[0], rho, p.potential, ns, edge, a);
-    } else {
-      sc_accel<L, R, 1>(fields, p.G, rho, p.potential, n, a);
-    }
+    ScNode ns = n;
+    [[maybe_unused]] ScEdge<L, R> edge;
+    if constexpr (XF) edge = sc_edge<L, R>(p, n, nx, live, ns);
+    sc_accel<L, R, 1, XF>(fields, p.G, rho, p.potential, ns, a, &edge);
     static_for<0, L::dim>([&](auto D) { a[D] = a[D] / rho; });
     if (p.has_body_force) {
       static_for<0, L::dim>([&](auto D) { a[D] = a[D] + p.accel[D]; });
     }
   }
-  if constexpr (GENERAL) {
-    if (kind == NK_FULL_BB) bounce_back<L, R>(f);
-  }
-  if (wet) bgk_relax_accel<L, R>(f, rho, v, p.omega[0], p.guo_pref[0], false, true, a, p.force_edm != 0);
-  if ((p.options & 1u) && wet) {
+  if (nk.kind == NK_FULL_BB) bounce_back<L, R>(f);
+  if (nk.wet) bgk_relax_accel<L, R>(f, rho, v, p.omega[0], p.guo_pref[0], false, true, a, p.force_edm != 0);
+  if ((p.options & 1u) && nk.wet) {
     // the density field itself is written by PrepareMacroFields; v is the force-shifted output velocity
     p.vx[gi] = v[0];
     p.vy[gi] = v[1];
@@ -739,9 +612,9 @@ __global__ void __launch_bounds__(1024) scs_sweep_kernel(const ScParams<L, R> p)
   }
   if constexpr (XF && ROW) {
     const FaceRows fr = face_rows<L>(g, n.gy, n.gz);
-    row_push<L, R, GENERAL, sc_nt<L>()>(g, f, p.d_out, ds, n.row, n.xi, n.gx, nx, live, active, n.oy, n.oz, p.xsend[0], &fr);
+    row_push<L, R, GENERAL, sc_nt<L>()>(g, f, p.d_out, ds, n.row, n.xi, n.gx, nx, live, nk.active, n.oy, n.oz, p.xsend[0], &fr);
   } else {
-    sc_store<L, R, PROP, GENERAL, ROW, INDIRECT>(g, f, p.d_out, ds, n, nx, live, active, p.nodes, si);
+    sc_store<L, R, PROP, GENERAL, ROW, INDIRECT>(g, f, p.d_out, ds, n, nx, live, nk.active, p.nodes, si);
     if constexpr (XF) sc_face_send_own_row<L, R>(p.xsend[0], f, n.gx, nx, face_rows<L>(g, n.gy, n.gz));
   }
 }
@@ -834,43 +707,19 @@ static inline bool sc_xface_in_use(const SweepArgs& a) {
   return false;
 }
 
+// whole-row kernels are on (module variant bit 3, as slf_row.hip)
+static inline bool sc_rows_on(const Geometry& g) { return (g.variant & 8) != 0; }
+
 // rows sc_pull_rows() serves: wrapped along x inside the kernel, the whole row in one workgroup, whole-row kernels on
 static inline bool sc_row_pull_ok(const Geometry& g) {
   return SLF_SC_ROW_PULL && g.wrap[0] && g.lat_nx - 2 <= 1024 && (g.variant & 8) && !g.indirect;
-}
-
-// Block width of the pass kernels (densities, velocity): the whole row in one workgroup where it fits
-static inline int sc_pass_block_x(int nx) {
-  const int bx = ((nx + 63) / 64) * 64;
-  return bx > 1024 ? 256 : bx;
-}
-
-// Launch shape of all four launchers.  row: whole-row workgroups + aligned stores for the x-streaming steps in 3-D (as
-// slf_row.hip), where the caller's kernels have that form (row_ok); block_x is then the row's, not the caller's.
-struct ScShape {
-  dim3 grid, block;
-  bool row, empty;
-  int xcd_shift;      // the force stencil's rho / phi rows: neighbouring rows on one XCD
-};
-
-template <class L>
-static ScShape sc_shape(const Geometry& g, bool row_ok, Prop prop, int y0, int y1, int z0, int z1, int block_x) {
-  const int nx = g.lat_nx - 2;
-  ScShape sh;
-  sh.row = row_ok && L::dim == 3 && (g.variant & 8) && prop != PROP_AA_EVEN;
-  if (sh.row) block_x = row_block_x(nx);
-  sh.block = dim3(block_x, 1, 1);
-  sh.grid = dim3((nx + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-  sh.empty = sh.grid.y == 0 || sh.grid.z == 0;
-  sh.xcd_shift = xcd_shift_for(sh.grid.y, sh.grid.x);
-  return sh;
 }
 
 template <class L, class R>
 static hipError_t sc_macro2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
                             const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s) {
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
-  const ScShape sh = sc_shape<L>(g, false, prop, y0, y1, z0, z1, sc_pass_block_x(g.lat_nx - 2));
+  const NNShape sh = nn_shape<L>(g, false, prop, y0, y1, z0, z1, nn_pass_block_x(g.lat_nx - 2));
   if (sh.empty) return hipSuccess;
   // the densities-only form: indirect addressing keeps the reference's pass
   const bool vout = !a.sc_local_velocity || (a.options & 1u) || g.indirect;
@@ -911,7 +760,7 @@ static hipError_t sc_sweep2(LR<L, R>, int grid_idx, Prop prop, bool general, con
                             hipStream_t s) {
   if (sc_xface_in_use(a)) return hipErrorInvalidValue;       // planes: the fused sweep only
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, grid_idx, y0, z0);
-  const ScShape sh = sc_shape<L>(g, !g.indirect, prop, y0, y1, z0, z1, block_x);
+  const NNShape sh = nn_shape<L>(g, sc_rows_on(g) && !g.indirect, prop, y0, y1, z0, z1, block_x);
   if (sh.empty) return hipSuccess;
   p.xcd_shift = sh.xcd_shift;
   hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
@@ -947,7 +796,7 @@ template <class L, class R>
 static hipError_t sc_fused2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
                             const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
-  const ScShape sh = sc_shape<L>(g, true, prop, y0, y1, z0, z1, block_x);
+  const NNShape sh = nn_shape<L>(g, sc_rows_on(g), prop, y0, y1, z0, z1, block_x);
   if (sh.empty) return hipSuccess;
   p.xcd_shift = sh.xcd_shift;
   const bool ownv = a.sc_local_velocity, xf = sc_xface_in_use(a);
@@ -966,7 +815,7 @@ static hipError_t sc_fused2(LR<L, R>, Prop prop, bool general, const Geometry& g
       // XF && (dim != 3 || !OWNV): planes are 3-D and need the own-velocity sweep (refused above)
       // XF && PULL: the aligned loads wrap x inside the kernel, planes connect it outside (pull has !xf)
       // XF && ROW != (P != AA_EVEN): under planes an x-streaming step is always one whole-row workgroup (refused above
-      //   otherwise), and the even step never is (sc_shape)
+      //   otherwise), and the even step never is (nn_shape)
       if constexpr ((ROW && (L::dim != 3 || P == PROP_AA_EVEN)) || (PULL && !(ROW && OWNV && P == PROP_AA_ODD)) ||
                     (XF && (L::dim != 3 || !OWNV || PULL || ROW != (P != PROP_AA_EVEN)))) return;
       else {
@@ -990,7 +839,7 @@ static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, con
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
   p.G[0] = (R)sc.G[0];
   p.G[1] = (R)0;
-  const ScShape sh = sc_shape<L>(g, !macro && !g.indirect, prop, y0, y1, z0, z1, block_x);
+  const NNShape sh = nn_shape<L>(g, sc_rows_on(g) && !macro && !g.indirect, prop, y0, y1, z0, z1, block_x);
   if (sh.empty) return hipSuccess;
   p.xcd_shift = sh.xcd_shift;
   // connected x faces through planes (slf_module_set_xface_planes: sets 0 and 2 of the binary model's three): 3-D,
@@ -1025,7 +874,7 @@ static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, con
       // ROW && (dim != 3 || AA_EVEN): whole rows serve the x-streaming steps in 3-D; the even step does not stream
       // ROW && IND: indirect addressing has per-node kernels with translated neighbours, no whole rows
       // XF && ROW != (P != AA_EVEN): under planes an x-streaming step is always one whole-row workgroup (refused above
-      //   otherwise), and the even step never is (sc_shape)
+      //   otherwise), and the even step never is (nn_shape)
       if constexpr ((IND && (!G || XF)) || (XF && L::dim != 3) || (ROW && (L::dim != 3 || P == PROP_AA_EVEN || IND)) ||
                     (XF && ROW != (P != PROP_AA_EVEN))) return;
       else {
@@ -1040,7 +889,7 @@ static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, con
 hipError_t launch_scs_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                             const ShanChen& sc, const SweepArgs& a, hipStream_t s) {
   const int z0 = g.dim == 3 ? 1 : 0, z1 = g.dim == 3 ? g.lat_nz - 1 : 1;
-  const int bx = sc_pass_block_x(g.lat_nx - 2);
+  const int bx = nn_pass_block_x(g.lat_nx - 2);
   return pick_lr(sel, [&](auto lr) {
     return scs_launch2(lr, true, prop, sel.general, g, ph, sc, a, 1, g.lat_ny - 1, z0, z1, bx, s);
   });

@@ -7,13 +7,15 @@
 //   sc3_init_kernel    SetInitialConditions                (lb_ternary_fluid.mako)
 //
 // Layout, streaming modes and launch shape as the free-energy sweeps (slf_fe.hip): whole-row workgroups with row_push() for
-// the x-streaming steps in 3-D, the node's own slots in the even in-place step.
+// the x-streaming steps in 3-D, the node's own slots in the even in-place step.  The node prologue (nn_kind), the stencil
+// sum (sc_stencil), the common velocity (sc_add_momentum) and the launch shape (nn_shape) are slf_nn.h's, shared with the
+// binary model.
 //
 // Operation order (the numpy twin tests/_scn_twin.py restates it):
 //   pass in front, wet nodes:   rho_k = ((f_k,0 + f_k,1) + ...) of the populations as this step reads them
 //                               v     = (1/tau_0) j_0, then v = v + (1/tau_1) j_1, then v = v + (1/tau_2) j_2
 //                               total = ((1/tau_0) rho_0 + (1/tau_1) rho_1) + (1/tau_2) rho_2,  v = v / total
-//   sweep of lattice K:         S_j   = sum_i psi(rho_j(x + e_i)) (+-w_i), i = 1 .. Q - 1, per component (as sc_accel, slf_sc.hip)
+//   sweep of lattice K:         S_j   = sum_i psi(rho_j(x + e_i)) (+-w_i), i = 1 .. Q - 1, per component (sc_stencil, slf_nn.h)
 //                               a     = 0; for j = 0, 1, 2 with G_Kj != 0:  a = a + S_j ((0 - psi(rho_K)) G_Kj)
 //                               a     = a / rho_K [+ the body acceleration of lattice K]
 //                               full-way bounce-back swap on wall nodes; bgk_relax_accel(f, rho_K, v, 1/tau_K, 3 (1 - 1/(2 tau_K)), a)
@@ -55,20 +57,6 @@ struct Sc3Params {
   int has_force_k;
 };
 
-// S[d] = sum_i psi(field(x + e_i)) (+-w_i) over the directions with e_i,d != 0: the neighbour values through the caches, the
-// sum in sc_accel()'s order (slf_sc.hip)
-template <class L, class R, int POT>
-__device__ __forceinline__ void sc3_stencil(const R* field, const ScNode& n, R (&S)[3]) {
-  static_for<1, L::Q>([&](auto I) {
-    const R psi = sc_psi<R, POT>(*sc_neighbour<L, I>(field, n, true));
-    static_for<0, L::dim>([&](auto D) {
-      constexpr int e = e_comp<L>(I, D);
-      if constexpr (e > 0) S[D] = S[D] + psi * Weights<L, R>::w(I);
-      if constexpr (e < 0) S[D] = S[D] + psi * ((R)0 - Weights<L, R>::w(I));
-    });
-  });
-}
-
 // PROP: PROP_AB (the node's own slots: two-copy and the even in-place step) | PROP_AA_ODD
 template <class L, class R, int PROP>
 __global__ void __launch_bounds__(1024) sc3_macro_kernel(const Sc3Params<R> p) {
@@ -88,16 +76,8 @@ __global__ void __launch_bounds__(1024) sc3_macro_kernel(const Sc3Params<R> p) {
     R f[L::Q];
     sc_load<L, R, PROP>(f, p.d_in[K], ds, n);
     rho[K] = density<L, R>(f);
-    const R j0 = p.omega[K] * momentum<L, R, 0>(f);
-    const R j1 = p.omega[K] * momentum<L, R, 1>(f);
-    v[0] = (K == 0) ? j0 : v[0] + j0;
-    v[1] = (K == 0) ? j1 : v[1] + j1;
-    if constexpr (L::dim == 3) {
-      const R j2 = p.omega[K] * momentum<L, R, 2>(f);
-      v[2] = (K == 0) ? j2 : v[2] + j2;
-    }
+    sc_add_momentum<L, R, K == 0>(v, p.omega[K], f);
   });
-  // common velocity: sum_k j_k / tau_k over sum_k rho_k / tau_k (ternary_shan_chen.mako:75-95)
   const R total = (p.omega[0] * rho[0] + p.omega[1] * rho[1]) + p.omega[2] * rho[2];
   p.field[0][gi] = rho[0];
   p.field[1][gi] = rho[1];
@@ -105,27 +85,6 @@ __global__ void __launch_bounds__(1024) sc3_macro_kernel(const Sc3Params<R> p) {
   p.vx[gi] = v[0] / total;
   p.vy[gi] = v[1] / total;
   if constexpr (L::dim == 3) p.vz[gi] = v[2] / total;
-}
-
-// What the sweeps do with a node once it is known: row position, kind, whether it is swept at all
-struct Sc3Kind {
-  int kind;
-  bool active, wet;
-};
-template <bool ROW>
-__device__ __forceinline__ bool sc3_kind(const Geometry& g, const uint32_t* map, uint32_t gi, bool live, Sc3Kind& k) {
-  k.kind = NK_FLUID;
-  k.active = live;
-  if (map) {
-    k.kind = node_kind(g.type_lut, g.type_mask, map[gi]);
-    if constexpr (!ROW) {
-      if (kind_is_excluded(k.kind)) return false;
-    } else {
-      k.active = live && !kind_is_excluded(k.kind);
-    }
-  }
-  k.wet = kind_is_wet(k.kind) && k.active;
-  return true;
 }
 
 // One lattice (p.d_in[0] -> p.d_out[0]; p.own, p.omega_k, p.guo_k, p.Gk, p.accel_k are its field and constants).
@@ -137,12 +96,9 @@ __global__ void __launch_bounds__(1024) sc3_sweep_kernel(const Sc3Params<R> p) {
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
   const uint32_t gi = n.gi;
-  Sc3Kind nk;
-  if (!sc3_kind<ROW>(g, p.map, gi, live, nk)) return;
+  NnKind nk;
+  if (!nn_kind<ROW>(g, p.map, gi, live, nk)) return;
   const size_t ds = g.dist_size;
 
   R f[L::Q];
@@ -156,7 +112,7 @@ __global__ void __launch_bounds__(1024) sc3_sweep_kernel(const Sc3Params<R> p) {
         const R cc = p.Gk[J];
         if (cc != (R)0) {
           R S[3] = {(R)0, (R)0, (R)0};
-          sc3_stencil<L, R, POT>((const R*)p.field[J], n, S);
+          sc_stencil<L, R, POT>((const R*)p.field[J], n, S);
           static_for<0, L::dim>([&](auto D) { a[D] = a[D] + S[D] * (((R)0 - psi_loc) * cc); });
         }
       });
@@ -186,12 +142,9 @@ __global__ void __launch_bounds__(1024) sc3_fused_kernel(const Sc3Params<R> p) {
   const int nx = g.lat_nx - 2;
   bool live;
   const ScNode n = sc_node<L>(g, p.y0, p.z0, nx, live, p.xcd_shift);
-  if constexpr (!ROW) {
-    if (!live) return;
-  }
   const uint32_t gi = n.gi;
-  Sc3Kind nk;
-  if (!sc3_kind<ROW>(g, p.map, gi, live, nk)) return;
+  NnKind nk;
+  if (!nn_kind<ROW>(g, p.map, gi, live, nk)) return;
   const size_t ds = g.dist_size;
 
   R rho[3], psi_own[3];
@@ -203,7 +156,7 @@ __global__ void __launch_bounds__(1024) sc3_fused_kernel(const Sc3Params<R> p) {
   if (nk.wet) {
     sc_with_potential(p.potential, [&](auto POT) {
       static_for<0, 3>([&](auto J) {
-        if (p.G[J] != (R)0 || p.G[3 + J] != (R)0 || p.G[6 + J] != (R)0) sc3_stencil<L, R, POT>((const R*)p.field[J], n, S[J]);
+        if (p.G[J] != (R)0 || p.G[3 + J] != (R)0 || p.G[6 + J] != (R)0) sc_stencil<L, R, POT>((const R*)p.field[J], n, S[J]);
       });
       static_for<0, 3>([&](auto K) { psi_own[K] = sc_psi<R, POT>(rho[K]); });
     });
@@ -299,25 +252,17 @@ static Sc3Params<R> make_sc3(const Geometry& g, const Physics& ph, const ShanChe
   return p;
 }
 
-// block width of the pass kernels: the whole row in one workgroup where it fits
-static inline int sc3_pass_block_x(int nx) {
-  const int bx = ((nx + 63) / 64) * 64;
-  return bx > 1024 ? 256 : bx;
-}
-
 hipError_t launch_sc3_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
                             const Sc3Args& a, int y0, int y1, int z0, int z1, hipStream_t s) {
   return pick_lr(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;
     const Sc3Params<R> p = make_sc3<R>(g, ph, sc, a, y0, z0);
-    const int nx = g.lat_nx - 2;
-    const int bx = sc3_pass_block_x(nx);
-    const dim3 grid((nx + bx - 1) / bx, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-    if (grid.y == 0 || grid.z == 0) return hipSuccess;
+    const NNShape sh = nn_shape<L>(g, false, prop, y0, y1, z0, z1, nn_pass_block_x(g.lat_nx - 2));
+    if (sh.empty) return hipSuccess;
     // two-copy and the even in-place step: the node's own slots
-    if (prop == PROP_AA_ODD) hipLaunchKernelGGL((sc3_macro_kernel<L, R, PROP_AA_ODD>), grid, dim3(bx, 1, 1), 0, s, p);
-    else hipLaunchKernelGGL((sc3_macro_kernel<L, R, PROP_AB>), grid, dim3(bx, 1, 1), 0, s, p);
+    if (prop == PROP_AA_ODD) hipLaunchKernelGGL((sc3_macro_kernel<L, R, PROP_AA_ODD>), sh.grid, sh.block, 0, s, p);
+    else hipLaunchKernelGGL((sc3_macro_kernel<L, R, PROP_AB>), sh.grid, sh.block, 0, s, p);
     return hipGetLastError();
   });
 }
@@ -340,16 +285,13 @@ static hipError_t sc3_sweep(const KernelSelector& sel, int which, Prop prop, con
       }
       p.has_force_k = p.has_body_force[k];
     }
-    const int nx = g.lat_nx - 2;
-    const bool row = L::dim == 3 && prop != PROP_AA_EVEN;       // the x-streaming steps in 3-D: whole rows (or equal segments)
-    const int bx = row ? row_block_x(nx) : block_x;
-    const dim3 grid((nx + bx - 1) / bx, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
-    if (grid.y == 0 || grid.z == 0) return hipSuccess;
-    p.xcd_shift = xcd_shift_for(grid.y, grid.x);      // the stencil's density rows: neighbouring rows on one XCD
+    const NNShape sh = nn_shape<L>(g, true, prop, y0, y1, z0, z1, block_x);      // the x-streaming steps in 3-D: whole rows
+    if (sh.empty) return hipSuccess;
+    p.xcd_shift = sh.xcd_shift;      // the stencil's density rows: neighbouring rows on one XCD
     hipError_t e = hipErrorInvalidValue;
     pick_prop(prop, [&](auto P) {
-      if (which < 3) hipLaunchKernelGGL((sc3_sweep_kernel<L, R, P>), grid, dim3(bx, 1, 1), 0, s, p);
-      else hipLaunchKernelGGL((sc3_fused_kernel<L, R, P>), grid, dim3(bx, 1, 1), 0, s, p);
+      if (which < 3) hipLaunchKernelGGL((sc3_sweep_kernel<L, R, P>), sh.grid, sh.block, 0, s, p);
+      else hipLaunchKernelGGL((sc3_fused_kernel<L, R, P>), sh.grid, sh.block, 0, s, p);
       e = hipGetLastError();
     });
     return e;

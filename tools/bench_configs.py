@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -284,6 +284,15 @@ def main():
                            dict(lat_nx=256, lat_ny=256, lat_nz=256, periodic_x=True, periodic_y=True, periodic_z=True,
                                 visc=1.0 / 6.0, access_pattern=pattern, grid=grid, max_iters=int(3000 * it),
                                 benchmark_sample_from=int(1000 * it)), 2 * q * 4))
+    # config 14 (only with --only): the free-energy binary fluid of examples/binary_fluid/fe_separation_3d.py at 256^3, periodic
+    # (csrc/slf_fe.hip: pass in front + fluid sweep + order-parameter sweep), 14a two-copy, 14b in-place.  436 B per update
+    # from the argument lists (profiles/NOTES.md)
+    for cid, pattern in (('14a', 'AB'), ('14b', 'AA')):
+        if cid in only:
+            from examples.binary_fluid.fe_separation_3d import SeparationFESim
+            res.append(run('%s: free-energy binary fluid D3Q19 256^3 (%s)' % (cid, pattern), SeparationFESim, LBGeometry3D,
+                           dict(lat_nx=256, lat_ny=256, lat_nz=256, access_pattern=pattern, seed=11, max_iters=int(1500 * it),
+                                benchmark_sample_from=int(500 * it)), 436))
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
