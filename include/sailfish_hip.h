@@ -176,6 +176,17 @@ typedef struct slf_module_desc {
   double bc_wall_grad_phase;
   int32_t bc_wall_grad_order;
   int32_t fe_zero_grad_rim[3];
+  /* A body force that depends on position (add_body_force(DynamicValue(...)) of sym.S.gx / gy / gz; the reference renders the
+   * expression into the kernel, relaxation_common.mako:body_force).  accel_field = 1: the sweep reads an acceleration per node
+   * from the field handed over with slf_module_set_accel_field() and adds it to accel[] (one addition in the module's
+   * precision); has_force is implied.  Single-fluid modules on D2Q9 and D3Q19, BGK (Guo and EDM) and MRT, both access
+   * patterns and precisions, direct addressing, every node type of the per-node sweep except NTWallTMS; served by the
+   * per-node kernels (ACCF instantiations).  Refused with SLF_ERR_UNSUPPORTED: D3Q15 / D3Q27, --model=elbm, --regularized,
+   * --subgrid, --minimize_roundoff, NTWallTMS nodes, indirect addressing, the Shan-Chen, free-energy and ternary models;
+   * CollideAndPropagateResident and the pair sweep do not exist in such a module.  (The member sits here, not at the end:
+   * between two 8-byte aligned members it makes the structure 8 bytes longer, so a caller built against the earlier layout
+   * is refused by the struct_size check.) */
+  int32_t accel_field;
   /* simtype = SLF_SIM_SHAN_CHEN_TERNARY (reference lb_ternary.py, templates/models/ternary_shan_chen.mako): three lattices
    * with the densities rho, phi, theta, relaxed with tau, tau_phi and tau_theta (--tau_theta).  sc3_G[3 k + j] couples
    * lattice k to the field of lattice j (row-major G11 G12 G13 G21 ... G33; the host passes symmetric pairs); a coupling
@@ -384,8 +395,16 @@ int slf_module_update_node_params(slf_module* m, int first, const double* values
  * the rendered expression in relaxation_common.mako:body_force): the acceleration is an argument of every sweep launch,
  * so the host sets the value the NEXT launches take -- accel[3] for lattice 0, lattice 1 of a binary or ternary model, or
  * lattice 2 of a ternary one.  For lattice 0 the module must have been created with a body force (has_force): which
- * instantiation runs was decided there.  Forces that depend on position are not served (they would need a field). */
+ * instantiation runs was decided there.  Forces that depend on position: slf_module_set_accel_field. */
 int slf_module_set_body_force(slf_module* m, int lattice, const double accel[3]);
+/* The per-node acceleration of a module created with accel_field = 1: `field` is a device pointer to dim dense arrays in the
+ * module's precision, [d][arr_nz][arr_ny][arr_nx] -- layout and padding of rho, one component after the other, arr_nz *
+ * arr_ny * arr_nx elements apart.  The acceleration of node gi in every CollideAndPropagate launch from here on is
+ * accel[d] + field[d][gi]; only the entries of nodes the sweep updates are read (ghost, unused and padding entries never).
+ * The library keeps the pointer, not a copy: the field must outlive the launches.  SLF_ERR_INVALID on a module created
+ * without accel_field and for a NULL field; a CollideAndPropagate launch of an accel_field module before a field is set
+ * returns SLF_ERR_INVALID and launches nothing. */
+int slf_module_set_accel_field(slf_module* m, void* field);
 /* Row classes of the node map at `map_dptr` (no counterpart in the reference, whose kernels decode the map in every
  * thread: geo_helpers.mako:146-161, kernel_common.mako:191-201).  Builds, on the device, one class per 64-node
  * x-segment of every row -- 0 = all plain fluid: the wavefront that owns the segment neither reads the map (4 of the

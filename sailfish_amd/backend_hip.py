@@ -323,6 +323,10 @@ class HIPBackend(placement.VmmMixin):
         group.add_argument('--nohip_placement_tune', dest='hip_placement_tune', action='store_false', default=True,
                            help='keep the first placement of the distribution arrays instead of timing a few steps on '
                                 'it, placing again and keeping the better one (runs of 200 steps and more)')
+        group.add_argument('--nohip_accel_field', dest='hip_accel_field', action='store_false', default=True,
+                           help='refuse body forces that depend on position instead of serving them from a per-node '
+                                'acceleration field (slf_module_set_accel_field).  The option is how a backend says that it '
+                                'has the field at all: LBForcedSim refuses such forces under a configuration without it')
         group.add_argument('--nohip_fused_periodic', dest='hip_fused_periodic', action='store_false',
                            default=True,
                            help='apply periodic boundary conditions with separate ghost-layer kernels '
@@ -643,6 +647,13 @@ class HIPBackend(placement.VmmMixin):
         a = (ctypes.c_double * 3)(*([float(x) for x in accel] + [0.0] * (3 - len(accel))))
         _check(self._lib, self._lib.slf_module_set_body_force(module.handle, int(lattice), a), 'slf_module_set_body_force')
 
+    def set_accel_field(self, module, buf):
+        """The per-node acceleration of a module built with accel_field: `buf` is the device address of dim dense arrays
+        in the module's precision, laid out like rho, one component behind the other (C ABI slf_module_set_accel_field).
+        The library keeps the address: the buffer has to live as long as the module's sweeps are launched."""
+        _check(self._lib, self._lib.slf_module_set_accel_field(module.handle, ctypes.c_void_p(int(buf))),
+               'slf_module_set_accel_field')
+
     def set_x_ghost_unused(self, module, low, high):
         """Nothing reads the ghost column x = 0 (low) / x = nx + 1 (high): the sweeps stop storing into it."""
         _check(self._lib, self._lib.slf_module_set_x_ghost_unused(module.handle, int(bool(low)), int(bool(high))),
@@ -703,7 +714,7 @@ class HIPBackend(placement.VmmMixin):
         return (desc.lattice == hipabi.SLF_D3Q19 and not desc.fluid_only and not int(desc.node_addressing) and
                 not int(desc.simtype) and int(desc.incompressible) != hipabi.SLF_DENSITY_ROUNDOFF and
                 not int(desc.regularized) and not int(desc.subgrid) and
-                int(desc.model) != hipabi.SLF_ELBM and
+                int(desc.model) != hipabi.SLF_ELBM and not int(desc.accel_field) and
                 hipabi.SLF_NK_WALL_TMS not in list(desc.type_kind[:desc.n_types]))      # (those run the per-node kernels)
 
     # -- streams / events -----------------------------------------------------

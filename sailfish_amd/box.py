@@ -23,8 +23,9 @@ def make_box_desc(grid, size, model='bgk', precision='single', access_pattern='A
                   periodic_fused=(0, 0, 0), fluid_only=True, accel=None, incompressible=False,
                   relaxation_enabled=True, type_kind=None, node_params=None, nt_bits=None, use_link_tags=True,
                   alignment=32, dist_pad=None, regularized=False, subgrid=None, smagorinsky_const=0.1,
-                  entropic_equilibrium=False, entropy_tolerance=0.0, alpha_tolerance=1e-10):
-    """size = (nx, ny[, nz]) real nodes; a ghost envelope of 1 is added."""
+                  entropic_equilibrium=False, entropy_tolerance=0.0, alpha_tolerance=1e-10, accel_field=False):
+    """size = (nx, ny[, nz]) real nodes; a ghost envelope of 1 is added.  accel_field: the module reads an acceleration
+    per node (BoxSim(accel_field=...) hands it over); `accel` stays the uniform part."""
     dim = grid.dim
     assert len(size) == dim
     lat = [s + 2 for s in size]
@@ -42,6 +43,9 @@ def make_box_desc(grid, size, model='bgk', precision='single', access_pattern='A
     if accel is not None:
         kw['has_force'] = 1
         kw['accel'] = list(accel) + [0.0] * (3 - len(accel))
+    if accel_field:
+        kw['accel_field'] = 1
+        kw['has_force'] = 1
     if type_kind is not None:
         kw['type_kind'] = type_kind
     if node_params is not None:
@@ -66,8 +70,10 @@ class BoxSim(object):
     """One subdomain, no neighbours, on one GPU through the backend interface."""
 
     def __init__(self, backend, desc, periodic=(False, False, False), node_map=None, tune_placement=False,
-                 alpha_field=None):
-        """alpha_field (entropic modules): True = the alpha array exists (filled with 2) and is the trailing argument of
+                 alpha_field=None, accel_field=None, accel_field_fill=0.0):
+        """accel_field (modules built with accel_field): the acceleration at the real nodes, [dim, (nz,) ny, nx]; the ghost
+        and padding entries of the uploaded array hold accel_field_fill (no sweep reads them).
+        alpha_field (entropic modules): True = the alpha array exists (filled with 2) and is the trailing argument of
         CollideAndPropagate; None = as the module's model says; False = no array (every Newton iteration starts from 2)."""
         self.backend = backend
         self.desc = desc
@@ -119,6 +125,13 @@ class BoxSim(object):
         if alpha_field or (alpha_field is None and desc.model == hipabi.SLF_ELBM):
             self.alpha = np.full(self.shape, 2.0, dtype=self.dtype)
             self.gpu_alpha = b.alloc_buf(like=self.alpha, align_offset=foff)
+        self.accel_field = self.gpu_accel_field = None
+        if accel_field is not None:
+            self.accel_field = np.full((self.dim,) + self.shape, accel_field_fill, dtype=self.dtype)
+            for d in range(self.dim):
+                self.real_view(self.accel_field[d])[...] = np.asarray(accel_field[d], dtype=np.float64)
+            self.gpu_accel_field = b.alloc_buf(like=self.accel_field, align_offset=foff)
+            b.set_accel_field(self.module, self.gpu_accel_field)
         self.gpu_map = 0
         self.node_map = None
         if node_map is not None:
@@ -287,7 +300,8 @@ class BoxSim(object):
         self.sync()
         b = self.backend
         for addr in list(self.gpu_dist) + [self.gpu_rho] + list(self.gpu_v) + ([self.gpu_map] if self.gpu_map else []) + \
-                ([self.gpu_alpha] if self.gpu_alpha is not None else []):
+                ([self.gpu_alpha] if self.gpu_alpha is not None else []) + \
+                ([self.gpu_accel_field] if self.gpu_accel_field is not None else []):
             b.free_buf(addr)
         self.gpu_dist = []
         # drop the kernel objects: the backend's registry of iteration-dependent kernels holds them weakly

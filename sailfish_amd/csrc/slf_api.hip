@@ -68,6 +68,7 @@ struct slf_module : slf::ModuleConfig {   // sel, geo, phys, sc, fe, sc3, access
   hipEvent_t stage_ev[4];
   size_t stage_bytes[4];
   int stage_next;
+  void* accf;         // the acceleration field of an accel_field module (slf_module_set_accel_field), NULL = not set yet
 };
 struct slf_kernel {
   slf_module* mod;
@@ -1106,6 +1107,14 @@ int slf_module_set_body_force(slf_module* m, int lattice, const double accel[3])
   return SLF_OK;
 }
 
+int slf_module_set_accel_field(slf_module* m, void* field) {
+  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  if (!m->phys.accel_field) return fail(SLF_ERR_INVALID, "the module was created without an acceleration field (accel_field)");
+  if (!field) return fail(SLF_ERR_INVALID, "slf_module_set_accel_field: field is NULL");
+  m->accf = field;
+  return SLF_OK;
+}
+
 int slf_module_poll_invalid(slf_module* m, slf_stream* stream, int32_t out[4]) {
   if (!m || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   uint32_t h[4] = {0, 0, 0, 0};
@@ -1483,6 +1492,12 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
         a.xrecv[f] = m->xrecv[f];
       }
       a.rows = m->rows.map ? &m->rows : nullptr;
+      if (m->phys.accel_field && kk == slf::KK_COLLIDE_AND_PROPAGATE) {
+        if (!m->accf)
+          return fail(SLF_ERR_INVALID, "CollideAndPropagate: the module was created with accel_field, but no field is set "
+                                       "(slf_module_set_accel_field)");
+        a.accf = m->accf;
+      }
       if (int rc = sweep_common(k, a)) return rc;
       if (int rc = nodes_given(k)) return rc;
       // (the slot table is built when the arguments are bound, slf_kernel_set_args: a launch may be part of a graph capture)

@@ -106,11 +106,35 @@ inline const char* lat_refusal(const slf_module_desc* d) {
   return nullptr;
 }
 
+// An acceleration field (slf_module_desc::accel_field) is read by the ACCF instantiations of the per-node sweep and by
+// nothing else: what those do not cover is named here and refused.  NULL: no field, or the descriptor is served.
+inline const char* accf_refusal(const slf_module_desc* d) {
+  if (!d->accel_field) return nullptr;
+  if (d->accel_field != 1) return "accel_field must be 0 or 1";
+  if (d->lattice == SLF_D3Q15) return "accel_field: D3Q15 is not served (the sweep of D3Q15 / D3Q27 takes a constant acceleration); D2Q9 and D3Q19 only";
+  if (d->lattice == SLF_D3Q27) return "accel_field: D3Q27 is not served (the sweep of D3Q15 / D3Q27 takes a constant acceleration); D2Q9 and D3Q19 only";
+  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
+    return "accel_field: the Shan-Chen models are not served; single-fluid modules only";
+  if (d->simtype == SLF_SIM_FREE_ENERGY) return "accel_field: the free-energy model is not served; single-fluid modules only";
+  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return "accel_field: the ternary Shan-Chen model is not served; single-fluid modules only";
+  if (d->simtype != SLF_SIM_LBM) return "accel_field: single-fluid modules only";
+  if (d->model == SLF_ELBM) return "accel_field: --model=elbm is not served (the entropic collision takes no body force); BGK and MRT only";
+  if (d->regularized) return "accel_field: --regularized is not served";
+  if (d->subgrid) return "accel_field: --subgrid is not served";
+  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return "accel_field: --minimize_roundoff is not served";
+  if (d->node_addressing != SLF_ADDR_DIRECT) return "accel_field: --node_addressing=indirect is not served; direct addressing only";
+  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
+    if (d->type_kind[i] == SLF_NK_WALL_TMS) return "accel_field: NTWallTMS nodes are not served";
+  }
+  return nullptr;
+}
+
 inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char** err) {
   *c = ModuleConfig{};
   if (d->struct_size != sizeof(slf_module_desc)) return refuse(err, SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
   if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19 && d->lattice != SLF_D3Q15 && d->lattice != SLF_D3Q27)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported lattice");
+  if (const char* why = accf_refusal(d)) return refuse(err, d->accel_field == 1 ? SLF_ERR_UNSUPPORTED : SLF_ERR_INVALID, why);
   if (const char* why = lat_refusal(d)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported collision model");
@@ -209,7 +233,8 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   for (int i = 0; i < 3; i++) ph.accel[i] = d->accel[i];
   for (int i = 0; i < 27; i++) ph.mrt_rates[i] = d->mrt_rates[i];
   ph.incompressible = d->incompressible;
-  ph.has_force = d->has_force;
+  ph.accel_field = d->accel_field;
+  ph.has_force = d->has_force || d->accel_field;      // a field is a body force
   ph.relaxation_enabled = d->relaxation_enabled;
   ph.force_edm = d->force_implementation == SLF_FORCE_EDM;
   if (ph.force_edm && d->model != SLF_BGK)
@@ -347,12 +372,14 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
     if (why) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   }
   if (is_lat_lattice(d->lattice)) g.variant = 0;      // no tuned / whole-row D3Q19 kernels: the sweep of slf_lat.hip
+  if (ph.accel_field) g.variant = 0;       // the acceleration field is read by the per-node kernels only (ACCF)
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
   // workgroup; longer rows are cut into 256-thread chunks.
   int bx = ((d->lat_nx - 2 + 63) / 64) * 64;
   if (bx > 1024) bx = 256;
   const char* env = getenv("SLF_BLOCK_X");
   if (env && atoi(env) >= 64 && atoi(env) <= 1024 && atoi(env) % 64 == 0) bx = atoi(env);
+  if (ph.accel_field && bx > 512) bx = 512;      // the ACCF instantiations are bounded to 512 threads (slf_kernels.hip)
   c->block_x = bx;
   c->n_node_params = d->n_node_params > 0 ? d->n_node_params : 0;
   return SLF_OK;
@@ -506,6 +533,9 @@ inline int resolve(const ModuleConfig& c, const char* name, const KernelRow** ou
                                               "through index lists");
   }
   if (kk == KK_RESIDENT) {
+    if (c.phys.accel_field)
+      return refuse(err, SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: accel_field modules are not served (the resident kernel "
+                                              "takes a constant acceleration)");
     if (int rc = resident_refusal(c, err)) return rc;
   }
   if ((kk == KK_PBC || kk == KK_PBC_SWAP) && c.geo.indirect)

@@ -67,6 +67,9 @@ struct Physics {
   // read only by the boundary-condition code of the instantiations launched for modules that have one
   // (node_update<..., TMS = true>, slf_sweep.h).  Kept out of Geometry, which every kernel of the library takes by value.
   uint32_t tms_mask;
+  // slf_module_desc::accel_field: the module reads an acceleration per node (SweepArgs::accf); the ACCF instantiations of
+  // the per-node kernels run, has_force is set
+  int accel_field;
 };
 
 struct ShanChen {
@@ -142,6 +145,7 @@ struct SweepArgs {
   const void* mrecv[2];
   void* alpha;         // entropic modules: the alpha field (dense, like rho) or NULL
   void* lap;           // free-energy modules: the Laplacian of phi (dense, like rho), else unused
+  const void* accf;    // accel_field modules: the acceleration field [d][arr_nz][arr_ny][arr_nx] (slf_module_set_accel_field)
 };
 
 // What slf_module_classify_rows() found in a node map, per 64-node x-segment (= one wavefront of a whole-row

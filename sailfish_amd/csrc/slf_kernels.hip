@@ -28,9 +28,14 @@ namespace slf {
 // top of the collision does not fit the 128 of a 1024-thread workgroup (76-152 bytes of scratch per lane in the odd step).
 // MODEL = 2 (--model=elbm): the same bound -- f and fneq stay live across the Newton solve.
 // TMS: the instantiations for modules with Tamm-Mott-Smith wall nodes (node_update<..., TMS>, slf_sweep.h).
+// ACCF: the instantiations for modules with an acceleration field (slf_module_desc::accel_field): the node's acceleration
+// is cp.accel + field[d][gi], one coalesced load per dimension next to the population loads, live across the collision.
+// BGK and MRT, direct addressing, none of ROUNDOFF, TURB, TMS; launched iff the module has the flag (launch_sweep2).
+// Workgroups of at most 512 threads as well: under the 128 VGPRs of a 1024-thread workgroup the D3Q19 odd-step
+// instantiations spill (20-32 bytes of scratch per lane in single, 84-136 in double precision: profiles/accf).
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false,
-          bool TMS = false>
-__global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
+          bool TMS = false, bool ACCF = false>
+__global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const int gy = p.y0 + (int)blockIdx.y;
   const int gz = (L::dim == 3) ? p.z0 + (int)blockIdx.z : 0;
@@ -62,6 +67,13 @@ __global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kerne
   const AxisOff oz = (L::dim == 3) ? axis_off(gz, g.lat_nz, g.arr_nxy, g.wrap[2]) : AxisOff{0, 0};
   const size_t ds = g.dist_size;
 
+  // the acceleration field: issued in front of the population loads, so that all of them are in flight together
+  R acc[3] = {(R)0, (R)0, (R)0};
+  if constexpr (ACCF) {
+    const size_t fs = (size_t)g.arr_nxy * (size_t)g.arr_nz;
+    static_for<0, L::dim>([&](auto D) { acc[D] = (p.accf + fs * (size_t)D)[gi]; });
+  }
+
   // ---- load (reference getDist, geo_helpers.mako:258-276)
   R f[L::Q];
   static_for<0, L::Q>([&](auto I) {
@@ -77,7 +89,13 @@ __global__ void __launch_bounds__((TURB || MODEL == 2) ? 512 : 1024) sweep_kerne
 
   R rho, v[3];
   bool wet = true;
-  node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+  if constexpr (ACCF) {
+    static_for<0, L::dim>([&](auto D) { acc[D] = p.cp.accel[D] + acc[D]; });
+    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, 1, 2, ROUNDOFF, TURB, TMS, true>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet,
+                                                                                      si, &acc);
+  } else {
+    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+  }
 
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   // ---- macroscopic output (save_macro_fields, kernel_common.mako:213-240)
@@ -197,11 +215,12 @@ static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, co
   dim3 block(block_x, 1, 1);
   dim3 grid((g.lat_nx - 2 + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
   if (grid.y == 0 || grid.z == 0) return hipSuccess;
+  if (ph.accel_field && !a.accf) return hipErrorInvalidValue;      // (slf_kernel_launch refuses first, with a message)
   if (model != 0 && model != 2) model = 1;
   // BGK only (checked at module creation): --minimize_roundoff; --regularized / --subgrid=les-smagorinsky
   const bool roundoff = model == 0 && ph.incompressible == SLF_DENSITY_ROUNDOFF;
   const bool turb = model == 0 && !roundoff && (ph.regularized || ph.subgrid);
-  if ((turb || model == 2) && block.x > 512) {      // these instantiations: at most 512 threads per workgroup (launch bounds)
+  if ((turb || model == 2 || ph.accel_field) && block.x > 512) {      // these instantiations: at most 512 threads per workgroup (launch bounds)
     block.x = 512;
     grid.x = (g.lat_nx - 2 + 511) / 512;
   }
@@ -215,14 +234,18 @@ static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, co
   pick<int, 0, 1, 2>(model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
     pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
       pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) { pick_bool(ph.tms_mask != 0, [&](auto TMS) {
+      pick_bool(ph.accel_field != 0, [&](auto ACCF) {
         // indirect addressing: the node map is always read; --minimize_roundoff and --regularized / --subgrid exclude
         // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only;
-        // Tamm-Mott-Smith walls are node types: no such instantiation without the node map
-        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0) || (TMS && !G)) return;
+        // Tamm-Mott-Smith walls are node types: no such instantiation without the node map; an acceleration field:
+        // BGK / MRT with direct addressing and none of the three (refused at module creation otherwise, slf_bind.h)
+        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0) || (TMS && !G) ||
+                      (ACCF && (ROUNDOFF || TURB || TMS || IND || MODEL == 2))) return;
         else {
-          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS>), grid, block, 0, s, p);
+          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS, ACCF>), grid, block, 0, s, p);
           e = hipGetLastError();
         }
+      });
       }); }); });
     }); });
   }); });

@@ -249,6 +249,13 @@ SLF_D void bgk_relax(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L, R>& 
   }
 }
 
+// The same with the acceleration as an argument (the ACCF instantiations of the per-node kernels: cp.accel + the node's
+// entry of the acceleration field, slf_sweep.h); the module has a force by construction.
+template <class L, class R>
+SLF_D void bgk_relax(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L, R>& cp, const R (&a)[3]) {
+  bgk_relax_accel<L, R>(f, rho, v, cp.omega, cp.guo_pref, cp.incompressible != 0, true, a, cp.force_edm != 0);
+}
+
 // C7 helpers: one row of the integer moment matrix applied to a vector.
 template <class L, class R, int K>
 SLF_D R mrt_row(const R (&f)[L::Q]) {
@@ -370,16 +377,17 @@ SLF_D void mrt_equilibrium(const R (&m)[L::Q], R inv_rho, R (&meq)[L::Q]) {
 
 // C7: relaxation in moment space.  force_eq: equilibrium-type node (moments
 // forced to equilibrium, relaxation_mrt.mako:58-77).
+// a: the acceleration -- cp.accel, or cp.accel + the node's entry of the acceleration field (ACCF instantiations).
 template <class L, class R, int FORCE = FORCE_RUNTIME>
-SLF_D void mrt_relax(R (&f)[L::Q], R (&v)[3], const CollideParams<L, R>& cp, bool force_eq) {
+SLF_D void mrt_relax(R (&f)[L::Q], R (&v)[3], const CollideParams<L, R>& cp, bool force_eq, const R (&a)[3]) {
   R m[L::Q];
   if constexpr (L::id == D3Q19::id) mrt_forward_d3q19<R>(f, m);
   else static_for<0, L::Q>([&](auto K) { m[K] = mrt_row<L, R, K>(f); });
   const bool has_force = (FORCE == 1) ? true : ((FORCE == 0) ? false : (cp.has_force != 0));
   if (has_force) {
-    m[L::M_MX] = m[L::M_MX] + (R)0.5 * cp.accel[0];
-    m[L::M_MY] = m[L::M_MY] + (R)0.5 * cp.accel[1];
-    if constexpr (L::dim == 3) m[L::M_MZ] = m[L::M_MZ] + (R)0.5 * cp.accel[2];
+    m[L::M_MX] = m[L::M_MX] + (R)0.5 * a[0];
+    m[L::M_MY] = m[L::M_MY] + (R)0.5 * a[1];
+    if constexpr (L::dim == 3) m[L::M_MZ] = m[L::M_MZ] + (R)0.5 * a[2];
   }
   const R inv_rho = cp.incompressible ? (R)1 : (R)1 / m[L::M_RHO];
   R meq[L::Q];
@@ -393,16 +401,20 @@ SLF_D void mrt_relax(R (&f)[L::Q], R (&v)[3], const CollideParams<L, R>& cp, boo
     }
   });
   if (has_force) {
-    m[L::M_MX] = m[L::M_MX] + (R)0.5 * cp.accel[0];
-    m[L::M_MY] = m[L::M_MY] + (R)0.5 * cp.accel[1];
-    if constexpr (L::dim == 3) m[L::M_MZ] = m[L::M_MZ] + (R)0.5 * cp.accel[2];
+    m[L::M_MX] = m[L::M_MX] + (R)0.5 * a[0];
+    m[L::M_MY] = m[L::M_MY] + (R)0.5 * a[1];
+    if constexpr (L::dim == 3) m[L::M_MZ] = m[L::M_MZ] + (R)0.5 * a[2];
   }
   static_for<0, L::Q>([&](auto K) { m[K] = m[K] * (R)(1.0 / (double)L::mrt_norm(K)); });
   if constexpr (L::id == D3Q19::id) mrt_inverse_d3q19<R>(m, f);
   else static_for<0, L::Q>([&](auto I) { f[I] = mrt_col<L, R, I>(m); });
   if (has_force) {
-    static_for<0, L::dim>([&](auto D) { v[D] = v[D] + (R)0.5 * cp.accel[D]; });
+    static_for<0, L::dim>([&](auto D) { v[D] = v[D] + (R)0.5 * a[D]; });
   }
+}
+template <class L, class R, int FORCE = FORCE_RUNTIME>
+SLF_D void mrt_relax(R (&f)[L::Q], R (&v)[3], const CollideParams<L, R>& cp, bool force_eq) {
+  mrt_relax<L, R, FORCE>(f, v, cp, force_eq, cp.accel);
 }
 
 // C8: full-way bounce-back (boundary.mako:255-264).

@@ -48,7 +48,13 @@ struct SweepParams {
   R turb_visc, turb_c2x36;      // viscosity and 36 C^2 of the subgrid model
   // --model=elbm: read by the MODEL = 2 instantiations of the per-node kernels only.  alpha: dense field like rho, the
   // Newton start value of a node and the alpha it ended with; NULL: no alpha array (start from 2, nothing stored)
-  R* alpha;
+  // accf: the acceleration field of an accel_field module, [d][arr_nz][arr_ny][arr_nx], read by the ACCF instantiations
+  // of the per-node kernels only (BGK / MRT).  No module has both, so the two share the slot: the kernel-argument layout
+  // of every kernel stays what it was (see above).
+  union {
+    R* alpha;
+    const R* accf;
+  };
   ElbmParams<R> elbm;
   // Tamm-Mott-Smith walls (Physics::tms_mask): read by the TMS instantiations of the per-node kernels and the slot sweep only
   uint32_t tms_mask;
@@ -387,11 +393,17 @@ __device__ __forceinline__ void tms_fix_missing(const Geometry& g, R (&f)[L::Q],
 // TMS: the module has Tamm-Mott-Smith wall nodes (SweepParams::tms_mask != 0): half-way bounce-back types with the flag run
 // tms_fix_missing before and tms_add_equilibrium_difference after the collision; the target state stays live across it.
 // The per-node kernels and the slot sweep only; instantiations of their own, so that the others do not carry the registers.
+// ACCF: the module has an acceleration field (slf_module_desc::accel_field): the collision takes the node's acceleration
+// from `acc` (the caller formed cp.accel + field[gi]) instead of cp.accel.  The per-node kernels only; MODEL = BGK or MRT,
+// none of INDIRECT, ROUNDOFF, TURB, TMS; `acc` is not read otherwise.
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, int FORCE = FORCE_RUNTIME, int BCL = 2,
-          bool ROUNDOFF = false, bool TURB = false, bool TMS = false>
+          bool ROUNDOFF = false, bool TURB = false, bool TMS = false, bool ACCF = false>
 __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L::Q], uint32_t code, int kind,
                                             uint32_t gi, const AxisOff& ox, const AxisOff& oy, const AxisOff& oz,
-                                            R& rho, R (&v)[3], bool& wet, uint32_t si = INVALID_NODE) {
+                                            R& rho, R (&v)[3], bool& wet, uint32_t si = INVALID_NODE,
+                                            const R (*acc)[3] = nullptr) {
+  static_assert(!ACCF || ((MODEL == 0 || MODEL == 1) && !INDIRECT && !ROUNDOFF && !TURB && !TMS),
+                "ACCF: BGK / MRT, direct addressing, none of ROUNDOFF, TURB, TMS");
   if constexpr (!INDIRECT) si = gi;
   const Geometry& g = p.g;
   const size_t ds = g.dist_size;
@@ -461,7 +473,9 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (kind == NK_FULL_BB) bounce_back<L, R>(f);
     if (wet && p.relaxation_enabled) {
-      if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
+      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+      else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
+      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
       else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
     }
   } else if constexpr (GENERAL) {
@@ -566,7 +580,11 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     }
     // ---- collision (relaxate, relaxation.mako:196-202: wet nodes only)
     if (wet && p.relaxation_enabled) {
-      if constexpr (MODEL == 2) {
+      if constexpr (ACCF && MODEL == 0) {
+        bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+      } else if constexpr (ACCF) {
+        mrt_relax<L, R, 1>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY, *acc);
+      } else if constexpr (MODEL == 2) {
         elbm_collide<L, R>(p, f, rho, v, gi);
       } else if constexpr (MODEL == 0 && TURB) {
         bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
@@ -587,7 +605,9 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
   } else {
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (p.relaxation_enabled) {
-      if constexpr (MODEL == 2) elbm_collide<L, R>(p, f, rho, v, gi);
+      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+      else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
+      else if constexpr (MODEL == 2) elbm_collide<L, R>(p, f, rho, v, gi);
       else if constexpr (MODEL == 0 && TURB) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
       else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
       else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
@@ -640,6 +660,7 @@ inline SweepParams<L, R> make_params(const Geometry& g, const Physics& ph, const
   p.turb_visc = (R)ph.visc;
   p.turb_c2x36 = (R)(36.0 * ph.smagorinsky_const * ph.smagorinsky_const);
   p.alpha = (R*)a.alpha;
+  if (ph.accel_field) p.accf = (const R*)a.accf;      // shares the slot: an accel_field module is never entropic
   p.elbm.beta = (R)1 / ((R)2 * (R)(3.0 * ph.visc) + (R)1);       // tau0 = visc / cs^2 (reference lb_single.py:54-55)
   p.elbm.entropy_tol = (R)ph.entropy_tolerance;
   p.elbm.alpha_tol = (R)ph.alpha_tolerance;

@@ -65,6 +65,7 @@ class SlfModuleDesc(Structure):
         ('bc_wall_grad_phase', c_double),
         ('bc_wall_grad_order', c_int32),
         ('fe_zero_grad_rim', c_int32 * 3),
+        ('accel_field', c_int32),       # 1: the sweep reads an acceleration per node (slf_module_set_accel_field)
         # ternary Shan-Chen (simtype = SLF_SIM_SHAN_CHEN_TERNARY)
         ('tau_theta', c_double),
         ('sc3_G', c_double * 9),
@@ -153,6 +154,7 @@ SIGNATURES = {
     'slf_module_classify_rows': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int32 * 4)]),
     'slf_module_update_node_params': (c_int, [c_void_p, c_int, POINTER(c_double), c_int, c_void_p]),
     'slf_module_set_body_force': (c_int, [c_void_p, c_int, POINTER(c_double)]),
+    'slf_module_set_accel_field': (c_int, [c_void_p, c_void_p]),
     'slf_graph_capture_begin': (c_int, [c_void_p]),
     'slf_graph_capture_end': (c_int, [c_void_p, POINTER(c_void_p)]),
     'slf_graph_launch': (c_int, [c_void_p, c_void_p]),

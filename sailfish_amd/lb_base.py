@@ -218,6 +218,7 @@ class LBSim(object):
         """Refuses, on the host and with a clear message, what no kernel of the library covers (the library refuses the
         same at module creation)."""
         cls.check_lattice(kw)
+        cls.check_accel_field(kw)
         if hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []) and kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
             raise NotImplementedError('NTWallTMS nodes: single-fluid simulations only (the Shan-Chen kernels serve fluid and '
                                       'full-way bounce-back nodes)')
@@ -255,6 +256,37 @@ class LBSim(object):
         if why:
             raise NotImplementedError('%s: %s on this lattice' % (name, why))
 
+    @staticmethod
+    def check_accel_field(kw):
+        """A body force that depends on position (accel_field) is read by one family of sweep kernels (csrc/slf_kernels.hip,
+        the ACCF instantiations of the per-node sweep): single fluid, D2Q9 / D3Q19, BGK and MRT, dense addressing.  The rest
+        is refused here, naming the option (the library refuses the same at module creation)."""
+        if not kw.get('accel_field'):
+            return
+        why = None
+        simtype = kw.get('simtype', hipabi.SLF_SIM_LBM)
+        lat = {hipabi.SLF_D3Q15: 'D3Q15', hipabi.SLF_D3Q27: 'D3Q27'}.get(kw.get('lattice'))
+        if lat is not None:
+            why = '--grid=%s is not served; D2Q9 and D3Q19 only' % lat
+        elif simtype != hipabi.SLF_SIM_LBM:
+            why = 'the %s model is not served; single-fluid simulations only' % {
+                hipabi.SLF_SIM_SHAN_CHEN_BINARY: 'Shan-Chen', hipabi.SLF_SIM_SHAN_CHEN_SINGLE: 'Shan-Chen',
+                hipabi.SLF_SIM_FREE_ENERGY: 'free-energy', hipabi.SLF_SIM_SHAN_CHEN_TERNARY: 'ternary Shan-Chen'}.get(simtype, simtype)
+        elif kw.get('model', hipabi.SLF_BGK) == hipabi.SLF_ELBM:
+            why = '--model=elbm is not served; BGK and MRT only'
+        elif kw.get('regularized'):
+            why = '--regularized is not served'
+        elif kw.get('subgrid'):
+            why = '--subgrid is not served'
+        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
+            why = '--minimize_roundoff is not served'
+        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
+            why = '--node_addressing=indirect is not served; direct addressing only'
+        elif hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []):
+            why = 'NTWallTMS nodes are not served'
+        if why:
+            raise NotImplementedError('body forces that depend on position: %s' % why)
+
     def fill_module_desc(self, kw):
         """Contributes to the kernel-module descriptor (the counterpart of the reference's
         update_context(), lb_base.py:120-137)."""
@@ -268,6 +300,7 @@ class LBForcedSim(LBSim):
         super(LBForcedSim, self).__init__(config)
         self._forces = {}
         self._symbolic_forces = []      # DynamicValue accelerations (lattice 0) that depend on time
+        self._field_forces = []         # DynamicValue accelerations (lattice 0) that depend on position: the acceleration field
 
     @classmethod
     def add_options(cls, group, dim):
@@ -277,16 +310,34 @@ class LBForcedSim(LBSim):
 
     def add_body_force(self, force, grid=0, accel=True):
         """Adds a global acceleration (accel=True) acting on lattice `grid`: a constant one on any lattice of the model
-        (0, 1 in binary models, 0, 1, 2 in ternary ones), a time-dependent one (DynamicValue) on lattice 0 only."""
+        (0, 1 in binary models, 0, 1, 2 in ternary ones), a time-dependent or a position-dependent one (DynamicValue) on
+        lattice 0 only.  All of them add up."""
         dim = self.grids[0].dim
         assert len(force) == dim
         if isinstance(force, nt.DynamicValue):
             # reference lb_base.py:346-353.  An acceleration that depends on TIME is evaluated on the host before every
             # step (it is an argument of the sweep launches: SubdomainRunner._update_dynamic_params); one that depends on
-            # position would need a force field per node, which the kernels do not read
+            # POSITION is evaluated once, in float64, at the global coordinates of every real node, and becomes a dense
+            # field the sweep reads (accel_field_at; SubdomainRunner._init_accel_field; DESIGN.md §9g)
             if force.space_dependent():
                 self.config.space_dependence = True
-                raise NotImplementedError('body forces that depend on position are not supported by the HIP backend')
+                # the field is something the BACKEND has (set_accel_field); it says so through its option hip_accel_field
+                # (backend_hip.add_options, default on).  A configuration that carries no such option -- another backend,
+                # or none at all -- gets the refusal here, before anything is built, not an AttributeError at upload time
+                if not getattr(self.config, 'hip_accel_field', False):
+                    raise NotImplementedError('body forces that depend on position need a backend that reads an acceleration '
+                                              'field; this configuration names none (HIP backend: hip_accel_field, '
+                                              'switched off by --nohip_accel_field)')
+                if not accel or grid != 0:
+                    raise NotImplementedError('body forces that depend on position: accelerations (accel=True) on lattice 0 '
+                                              '(grid=0) only')
+                if force.time_dependent():
+                    raise NotImplementedError('body forces that depend on both position and time are not supported by the '
+                                              'HIP backend: the field would have to be uploaded before every step, which '
+                                              'the replayed step plan has no place for (split the expression into a '
+                                              'position-only and a time-only force if it is a sum)')
+                self._field_forces.append(force)
+                return
             # ... and the host evaluates it for lattice 0 only (body_force_at): lattices 1 and 2 of the binary and ternary
             # models take constant accelerations
             if not accel or grid != 0:
@@ -318,6 +369,21 @@ class LBForcedSim(LBSim):
         return total
 
     @property
+    def has_accel_field(self):
+        return bool(self._field_forces)
+
+    def accel_field_at(self, coords):
+        """The position-dependent part of the acceleration on lattice 0 at the nodes with global coordinates coords =
+        (gx, gy[, gz]) (equal-length 1-D arrays): float64 [dim, n], the sum over the registered forces."""
+        dim = self.grids[0].dim
+        n = len(coords[0])
+        total = np.zeros((dim, n), dtype=np.float64)
+        dt = getattr(self.config, 'dt_per_lattice_time_unit', 1.0)
+        for dv in self._field_forces:
+            total += dv.evaluate(coords, 0, dt).T
+        return total
+
+    @property
     def time_dependent_force(self):
         return any(dv.time_dependent() for dv in self._symbolic_forces)
 
@@ -327,6 +393,9 @@ class LBForcedSim(LBSim):
         if f is not None and (np.any(f != 0.0) or self._symbolic_forces):
             kw['has_force'] = 1
             kw['accel'] = list(f) + [0.0] * (3 - len(f))
+        if self._field_forces:
+            kw['accel_field'] = 1
+            kw['has_force'] = 1
         impl = getattr(self.config, 'force_implementation', 'guo')
         if impl not in ('guo', 'edm'):
             raise NotImplementedError('force_implementation=%s is not supported by the HIP backend' % impl)

@@ -225,6 +225,7 @@ def probe_sweep(backend, desc, dim, src, dst, nbytes, stream, steps=12):
     b = backend
     d = hipabi.SlfModuleDesc.from_buffer_copy(desc)
     d.model, d.simtype, d.fluid_only, d.n_types, d.has_force = hipabi.SLF_BGK, 0, 1, 0, 0
+    d.accel_field = 0               # (a body force of either kind is not part of the probe)
     d.incompressible, d.node_addressing, d.relaxation_enabled, d.tau = 0, 0, 1, 1.0
     for a in range(3):
         d.periodic_fused[a] = d.periodic_local[a] = int(a < dim)

@@ -224,6 +224,8 @@ class SubdomainRunner(object):
             kw['node_addressing'] = hipabi.SLF_ADDR_INDIRECT
             if hasattr(self._sim, 'check_lattice'):
                 self._sim.check_lattice(kw)
+            if hasattr(self._sim, 'check_accel_field'):
+                self._sim.check_accel_field(kw)
             kw['dist_stride'] = (self._subdomain.active_nodes + 1 + 31) // 32 * 32   # + one spare slot (halo lists)
             self._check_halfbb_targets()
         return hipabi.make_desc(**kw)
@@ -362,6 +364,29 @@ class SubdomainRunner(object):
             self.config.logger.debug('row classes: %s' % self.row_classes)
         if self.indirect:
             self._build_indirect_address_map()
+        self._init_accel_field(aligned)
+
+    def accel_field_host(self):
+        """The acceleration field of this subdomain as the sweep reads it: [dim] + the padded array shape, in the run's
+        precision -- the simulation's position-dependent body forces (LBForcedSim.accel_field_at) at the GLOBAL
+        coordinates of the real nodes, evaluated in float64 and rounded once; ghost and padding nodes hold 0."""
+        field = np.zeros((self.dim,) + tuple(self._physical_size), dtype=self.float)
+        grids = self._subdomain._get_mgrid()                     # global (hx, hy[, hz]) of the real nodes
+        vals = self._sim.accel_field_at(tuple(np.asarray(g, dtype=np.float64).ravel() for g in grids))
+        real = self._spec._nonghost_slice
+        for d in range(self.dim):
+            self._lat_view(field[d])[real] = vals[d].reshape(grids[0].shape)
+        return field
+
+    def _init_accel_field(self, alloc):
+        """A body force that depends on position: evaluated once, uploaded once, handed to the module.  The field is not
+        state: every prepare() -- a restored run included -- evaluates it again."""
+        self._gpu_accel_field = None
+        if not getattr(self._sim, 'has_accel_field', False):
+            return
+        self._host_accel_field = self.accel_field_host()
+        self._gpu_accel_field = alloc(self._host_accel_field)
+        self.backend.set_accel_field(self.module, self._gpu_accel_field)
 
     def _alloc_distributions(self):
         b = self.backend
@@ -1145,8 +1170,8 @@ class SubdomainRunner(object):
         cfg, sim, b = self.config, self._sim, self.backend
         if self.dim != 2 or not getattr(cfg, 'hip_resident', True) or os.environ.get('SLF_RESIDENT', '1') == '0' or \
                 not hasattr(sim, 'get_resident_kernels') or self._pbc_axes or self.indirect or len(sim.grids) != 1 or \
-                self._links or self.has_macro_exchange:
-            return None
+                self._links or self.has_macro_exchange or getattr(sim, 'has_accel_field', False):
+            return None                 # (an acceleration field is read by the per-node sweep only)
         d = self._desc
         ext = [(d.lat_nx - 2) if d.periodic_fused[0] else d.lat_nx, (d.lat_ny - 2) if d.periodic_fused[1] else d.lat_ny]
         # Where it pays (256^2 cavity on MI355X, GMLUPS with / without, profiles/r05/ldc2d_resident_variants.txt): in place

@@ -42,6 +42,8 @@ def supported(grid, desc, indirect=False, simtype=0):
         return False
     if int(desc.model) == hipabi.SLF_ELBM:      # per-node kernels as well
         return False
+    if int(desc.accel_field):                   # ... and so is the acceleration field: x faces through the ghost columns
+        return False
     variant = os.environ.get('SLF_VARIANT')
     if variant is not None and not (int(variant) & 8):
         return False

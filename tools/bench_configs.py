@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place, 15a,15b acceleration field: four rolls mill 2048^2 / periodic box 256^3 with 15ac,15bc their constant-force baselines -- run those under SLF_VARIANT=0)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -293,6 +293,55 @@ def main():
             res.append(run('%s: free-energy binary fluid D3Q19 256^3 (%s)' % (cid, pattern), SeparationFESim, LBGeometry3D,
                            dict(lat_nx=256, lat_ny=256, lat_nz=256, access_pattern=pattern, seed=11, max_iters=int(1500 * it),
                                 benchmark_sample_from=int(500 * it)), 436))
+    # config 15 (only with --only): a body force that depends on position (slf_module_desc::accel_field; the ACCF
+    # instantiations of the per-node sweep).  15a: examples/four_rolls_mill.py at 2048^2; 15b: the periodic box
+    # of config 1 with a force that is linear in x, y, z.  15ac / 15bc: the same boxes with a CONSTANT force -- under
+    # SLF_VARIANT=0 they run the per-node kernels as well, which makes them the like-for-like baseline (the tuned row
+    # kernels are not).  Two-copy and in-place each.  Bytes per update: the populations + dim field values.
+    if only & {'15a', '15ac', '15b', '15bc'}:
+        from examples.four_rolls_mill import FourRollsMill
+        from examples.taylor_green_2d import TaylorGreenSim
+        from sailfish.lb_base import LBForcedSim, LBSim
+        from sailfish.node_type import DynamicValue
+        from sailfish.sym import S
+
+        class QuietMill(FourRollsMill):
+            after_step = LBSim.after_step             # no error line: the run is not stepped one step at a time
+
+        class ConstantMill(TaylorGreenSim, LBForcedSim):
+            after_step = LBSim.after_step
+
+            def __init__(self, config):
+                super(ConstantMill, self).__init__(config)
+                self.add_body_force((1e-7, -2e-7))
+
+        class FieldBox(BoxSim, LBForcedSim):
+            def __init__(self, config):
+                super(FieldBox, self).__init__(config)
+                self.add_body_force(DynamicValue(1e-8 * S.gx - 2e-8 * S.gy, 3e-8 * S.gz + 1e-8 * S.gx, 1e-6 - 2e-8 * S.gy))
+
+        class ConstantBox(BoxSim, LBForcedSim):
+            def __init__(self, config):
+                super(ConstantBox, self).__init__(config)
+                self.add_body_force((1e-6, -2e-6, 3e-6))
+
+        for pattern in ('AA', 'AB'):
+            mill = dict(lat_nx=2048, lat_ny=2048, visc=0.01, max_v=0.02, precision='single', access_pattern=pattern,
+                        max_iters=int(6000 * it), benchmark_sample_from=int(2000 * it))
+            box = dict(lat_nx=256, lat_ny=256, lat_nz=256, periodic_x=True, periodic_y=True, periodic_z=True, visc=1.0 / 6.0,
+                       precision='single', access_pattern=pattern, grid='D3Q19', max_iters=int(3000 * it),
+                       benchmark_sample_from=int(1000 * it))
+            variant = os.environ.get('SLF_VARIANT', 'default')
+            if '15a' in only:
+                res.append(run('15a: four rolls mill D2Q9 2048^2, acceleration field (%s)' % pattern, QuietMill, LBGeometry2D, mill, 80))
+            if '15ac' in only:
+                res.append(run('15ac: the same box, constant force, SLF_VARIANT=%s (%s)' % (variant, pattern), ConstantMill,
+                               LBGeometry2D, mill, 72))
+            if '15b' in only:
+                res.append(run('15b: D3Q19 BGK periodic box 256^3, acceleration field (%s)' % pattern, FieldBox, LBGeometry3D, box, 164))
+            if '15bc' in only:
+                res.append(run('15bc: the same box, constant force, SLF_VARIANT=%s (%s)' % (variant, pattern), ConstantBox,
+                               LBGeometry3D, box, 152))
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
