@@ -633,6 +633,37 @@ int slf_force_objects(slf_module* m, const void* dist, const uint32_t* idx, cons
                       const uint32_t* seg, int n_objects, uint32_t max_links, void* workspace, double* out,
                       slf_stream* stream);
 
+/* ---- immersed boundary markers: the reference's LBIBMFluidSim (lb_single.py:350-411; kernels SpreadParticleForcesStiff
+ *      and UpdateParticlePosition, templates/ibm.mako; the sweep's force_field branch, kernel_common.mako:233-239).  Entry
+ *      points, not slf_kernel_get names.  An IBM module is an ordinary accel_field = 1 module: the calls rewrite the
+ *      contents of the buffer handed to slf_module_set_accel_field, which the unchanged sweep reads.  The semantics are
+ *      this library's, not the reference's bits.
+ *      n markers; pos and ref: [d][n] positions and reference positions in GLOBAL lattice coordinates (a node sits at
+ *      integer coordinates), stiffness: [n], all in the module's precision R; origin[d]: the global coordinate of the real
+ *      node with array index 1 along axis d (the subdomain's location; origin[2] is ignored in 2-D); acc: int64
+ *      [d][arr_nz][arr_ny][arr_nx], zero before the first call (slf_ibm_workspace_bytes, slf_memset).  The stencil of a
+ *      marker is the 2^dim nodes floor(x[d]) + {0, 1}, z outermost and x innermost, the weight of a node the product over
+ *      the axes of 1 - |x[d] - i[d]|, formed as (wx * wy) * wz.
+ *        slf_ibm_spread            acc[d][node] += llrint((double)(((-k) * (x[d] - ref[d])) * w) * 2^48), a 64-bit integer
+ *                                  atomic: the sums do not depend on the order of arrival (no floating-point atomics)
+ *        slf_ibm_gather            field[d][node] = (R)((double)acc[d][node] * 2^-48) at the stencil nodes of every marker
+ *        slf_ibm_clear_and_advect  acc = field = 0 at the stencil nodes; then v_p[d] = sum in stencil order of w * v[d][node]
+ *                                  (a node that is not wet by the node map counts as 0, its weight kept) and x[d] += v_p[d];
+ *                                  map may be NULL for a fluid-only module; vz is not read in 2-D
+ *      A step is spread, gather, the module's CollideAndPropagate with macroscopic output (option bit 0), clear_and_advect.
+ *      A stencil node that is not a real node of the subdomain is skipped by all three; a marker that has one does not
+ *      move and outside[p] = 1 (0 otherwise; uint32 [n]).  Positions that are not finite or beyond +-2^30 count as outside.
+ *      Every index is checked on the device before it is used.  All pointers but origin are device pointers; everything is
+ *      enqueued on `stream`.  SLF_ERR_INVALID: a NULL pointer, n_markers <= 0 or > 2^24, a module created without
+ *      accel_field or with no field set; SLF_ERR_UNSUPPORTED: D3Q15 / D3Q27, non-LBM models, indirect addressing. ---- */
+int slf_ibm_workspace_bytes(slf_module* m, size_t* bytes);
+int slf_ibm_spread(slf_module* m, int n_markers, const int32_t origin[3], const void* pos, const void* ref,
+                   const void* stiffness, void* acc, slf_stream* stream);
+int slf_ibm_gather(slf_module* m, int n_markers, const int32_t origin[3], const void* pos, const void* acc,
+                   slf_stream* stream);
+int slf_ibm_clear_and_advect(slf_module* m, int n_markers, const int32_t origin[3], void* pos, void* acc, const void* map,
+                             const void* vx, const void* vy, const void* vz, uint32_t* outside, slf_stream* stream);
+
 /* ---- step plans (extension): the launch list of ONE time step, built once, enqueued with one call.
  *      The reference enqueues every kernel, event and copy of a step from Python (SubdomainRunner.step(),
  *      subdomain_runner.py:960-974; the boundary / bulk overlap with its event chain, :1028-1058; _send_dists /

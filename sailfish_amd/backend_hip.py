@@ -708,6 +708,40 @@ class HIPBackend(placement.VmmMixin):
                                                       P(seg), int(n_objects), int(max_links), P(workspace or None), P(out),
                                                       stream.handle if stream else None), 'slf_force_objects')
 
+    # -- immersed boundary markers (C ABI slf_ibm_*; sailfish_amd/ibm.py) ---------------
+    supports_ibm = True
+
+    def ibm_accumulator_bytes(self, module):
+        """Size of the int64 accumulator of a module with an acceleration field: dim x 8 bytes per node of the arrays."""
+        n = ctypes.c_size_t()
+        _check(self._lib, self._lib.slf_ibm_workspace_bytes(module.handle, ctypes.byref(n)), 'slf_ibm_workspace_bytes')
+        return n.value
+
+    @staticmethod
+    def _ibm_origin(origin):
+        return (ctypes.c_int32 * 3)(*([int(x) for x in origin] + [0] * (3 - len(origin))))
+
+    def ibm_spread(self, module, n, origin, pos, ref, stiffness, acc, stream=None):
+        """Enqueues: the spring forces of the n markers, quantised, into the accumulator (slf_ibm_spread)."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_ibm_spread(module.handle, int(n), self._ibm_origin(origin), P(pos), P(ref), P(stiffness),
+                                                   P(acc), stream.handle if stream else None), 'slf_ibm_spread')
+
+    def ibm_gather(self, module, n, origin, pos, acc, stream=None):
+        """Enqueues: the accumulator at the stencil nodes of the markers into the module's acceleration field."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_ibm_gather(module.handle, int(n), self._ibm_origin(origin), P(pos), P(acc),
+                                                   stream.handle if stream else None), 'slf_ibm_gather')
+
+    def ibm_clear_and_advect(self, module, n, origin, pos, acc, gpu_map, gpu_v, outside, stream=None):
+        """Enqueues: accumulator and field back to zero at the stencil nodes, then the markers move with the interpolated
+        velocity (gpu_v: the device addresses of the velocity components; gpu_map: 0 for a fluid-only module)."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_ibm_clear_and_advect(module.handle, int(n), self._ibm_origin(origin), P(pos), P(acc),
+                                                             P(gpu_map or None), P(gpu_v[0]), P(gpu_v[1]),
+                                                             P(gpu_v[2] if len(gpu_v) > 2 else None), P(outside),
+                                                             stream.handle if stream else None), 'slf_ibm_clear_and_advect')
+
     @staticmethod
     def supports_row_classes(desc):
         """Modules the row classes exist for: D3Q19 single-fluid with a node map, direct addressing."""

@@ -1291,6 +1291,59 @@ int slf_force_objects(slf_module* m, const void* dist, const uint32_t* idx, cons
   return SLF_OK;
 }
 
+// ---- immersed boundary markers (slf_ibm.hip; argument checks: slf_bind.h ibm_check) ------------------------------
+static int check_ibm_call(const slf_module* m, const char* what, int n, const int32_t* origin, const void* const* ptrs,
+                          const char* const* names, int n_ptrs) {
+  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  std::string why;
+  if (int rc = slf::ibm_check(*m, m->accf != nullptr, what, n, origin, ptrs, names, n_ptrs, &why)) return fail(rc, why);
+  return SLF_OK;
+}
+
+int slf_ibm_workspace_bytes(slf_module* m, size_t* bytes) {
+  if (!m || !bytes) return fail(SLF_ERR_INVALID, "NULL argument");
+  if (!m->phys.accel_field)
+    return fail(SLF_ERR_INVALID, "slf_ibm_workspace_bytes: the module was created without an acceleration field (accel_field)");
+  *bytes = slf::ibm_accumulator_bytes(m->geo);
+  return SLF_OK;
+}
+
+int slf_ibm_spread(slf_module* m, int n_markers, const int32_t origin[3], const void* pos, const void* ref,
+                   const void* stiffness, void* acc, slf_stream* stream) {
+  const void* ptrs[] = {pos, ref, stiffness, acc};
+  const char* names[] = {"pos", "ref", "stiffness", "acc"};
+  if (int e = check_ibm_call(m, "slf_ibm_spread", n_markers, origin, ptrs, names, 4)) return e;
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  SLF_HIP(slf::launch_ibm_spread(m->sel, m->geo, origin, n_markers, pos, ref, stiffness, acc, native(stream)));
+  return SLF_OK;
+}
+
+int slf_ibm_gather(slf_module* m, int n_markers, const int32_t origin[3], const void* pos, const void* acc,
+                   slf_stream* stream) {
+  const void* ptrs[] = {pos, acc};
+  const char* names[] = {"pos", "acc"};
+  if (int e = check_ibm_call(m, "slf_ibm_gather", n_markers, origin, ptrs, names, 2)) return e;
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  SLF_HIP(slf::launch_ibm_gather(m->sel, m->geo, origin, n_markers, pos, acc, m->accf, native(stream)));
+  return SLF_OK;
+}
+
+int slf_ibm_clear_and_advect(slf_module* m, int n_markers, const int32_t origin[3], void* pos, void* acc, const void* map,
+                             const void* vx, const void* vy, const void* vz, uint32_t* outside, slf_stream* stream) {
+  const void* ptrs[] = {pos, acc, vx, vy, outside, vz};
+  const char* names[] = {"pos", "acc", "vx", "vy", "outside", "vz"};
+  if (int e = check_ibm_call(m, "slf_ibm_clear_and_advect", n_markers, origin, ptrs, names, m && m->geo.dim == 3 ? 6 : 5))
+    return e;
+  if (!map && m->sel.general)
+    return fail(SLF_ERR_INVALID, "slf_ibm_clear_and_advect: map is NULL, but the module has node types (which nodes are wet "
+                                 "is read off the node map)");
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  const void* v[3] = {vx, vy, vz};
+  SLF_HIP(slf::launch_ibm_clear_and_advect(m->sel, m->geo, origin, n_markers, pos, acc, m->accf, map, v, outside,
+                                           native(stream)));
+  return SLF_OK;
+}
+
 int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   if (!m || !name || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   const slf::KernelRow* row = nullptr;

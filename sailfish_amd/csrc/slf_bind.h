@@ -731,4 +731,33 @@ inline int face_box(const Geometry& g, KernelKind kind, const long long* ints, F
   return SLF_OK;
 }
 
+// ---- (d) immersed boundary markers (slf_ibm_*; kernels: slf_ibm.hip) ---------------------------------------------------
+// The arguments of one slf_ibm_* call.  `what`: the entry point's name, for the message.  has_field: the module holds an
+// acceleration field (slf_module_set_accel_field was called).  ptrs / names: the pointers that must not be NULL.
+constexpr int IBM_MAX_MARKERS = 1 << 24;
+inline int ibm_check(const ModuleConfig& c, bool has_field, const char* what, int n_markers, const int32_t* origin,
+                     const void* const* ptrs, const char* const* names, int n_ptrs, std::string* err) {
+  const std::string w = std::string(what) + ": ";
+  if (c.sel.lattice != SLF_D2Q9 && c.sel.lattice != SLF_D3Q19)
+    return refuse(err, SLF_ERR_UNSUPPORTED, w + "D2Q9 and D3Q19 modules only (D3Q15 / D3Q27 have no acceleration field)");
+  if (!c.phys.accel_field)
+    return refuse(err, SLF_ERR_INVALID, w + "the module was created without an acceleration field (accel_field): the markers "
+                                            "have nothing to spread their forces into");
+  if (c.sc.enabled || c.fe.enabled || c.sc3.enabled || c.geo.indirect)
+    return refuse(err, SLF_ERR_UNSUPPORTED, w + "single-fluid modules with direct addressing only");
+  if (!has_field)
+    return refuse(err, SLF_ERR_INVALID, w + "no field is set (slf_module_set_accel_field): the kernels rewrite that buffer");
+  if (n_markers <= 0) return refuse(err, SLF_ERR_INVALID, w + "the marker count must be positive");
+  if (n_markers > IBM_MAX_MARKERS) return refuse(err, SLF_ERR_INVALID, w + "at most 2^24 markers per call");
+  if (!origin) return refuse(err, SLF_ERR_INVALID, w + "origin is NULL");
+  for (int d = 0; d < 3; d++) {
+    if (origin[d] < -(1 << 30) || origin[d] > (1 << 30))
+      return refuse(err, SLF_ERR_INVALID, w + "origin beyond +-2^30");
+  }
+  for (int i = 0; i < n_ptrs; i++) {
+    if (!ptrs[i]) return refuse(err, SLF_ERR_INVALID, w + names[i] + " is NULL");
+  }
+  return SLF_OK;
+}
+
 }  // namespace slf

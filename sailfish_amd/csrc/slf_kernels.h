@@ -319,4 +319,16 @@ hipError_t launch_force_objects(const KernelSelector& sel, const void* dist, con
                                 const uint8_t* dir, const uint32_t* seg, int n_objects, uint32_t max_links,
                                 double* workspace, double* out, hipStream_t s);
 
+// ---- immersed boundary markers (slf_ibm.hip): D2Q9 / D3Q19 modules with an acceleration field, one lane per marker ----
+// pos / ref: [d][n], stiff: [n], in the module's precision; acc: int64 [d][arr_nz][arr_ny][arr_nx]; origin: the global
+// coordinates of the real node with array index 1 on every axis.  Operation order: the head of slf_ibm.hip.
+size_t ibm_accumulator_bytes(const Geometry& g);
+hipError_t launch_ibm_spread(const KernelSelector& sel, const Geometry& g, const int32_t origin[3], int n, const void* pos,
+                             const void* ref, const void* stiff, void* acc, hipStream_t s);
+hipError_t launch_ibm_gather(const KernelSelector& sel, const Geometry& g, const int32_t origin[3], int n, const void* pos,
+                             const void* acc, void* field, hipStream_t s);
+hipError_t launch_ibm_clear_and_advect(const KernelSelector& sel, const Geometry& g, const int32_t origin[3], int n, void* pos,
+                                       void* acc, void* field, const void* map, const void* const v[3], uint32_t* outside,
+                                       hipStream_t s);
+
 }  // namespace slf

@@ -194,6 +194,10 @@ SIGNATURES = {
     'slf_stats_profiles': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_size_t, c_size_t, c_void_p]),
     'slf_force_workspace_bytes': (c_int, [c_void_p, c_int, c_uint32, POINTER(c_size_t)]),
     'slf_force_objects': (c_int, [c_void_p] * 6 + [c_int, c_uint32, c_void_p, c_void_p, c_void_p]),
+    'slf_ibm_workspace_bytes': (c_int, [c_void_p, POINTER(c_size_t)]),
+    'slf_ibm_spread': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 5),
+    'slf_ibm_gather': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 3),
+    'slf_ibm_clear_and_advect': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 8),
     'slf_last_error': (c_char_p, []),
 }
 

@@ -278,3 +278,77 @@ class LBSingleFluidShanChen(LBFluidSim, LBForcedSim):
             macro_kernels.append(runner.get_kernel('PrepareMacroFields', args, sig, needs_iteration=ni))
         sim_kernels = super(LBSingleFluidShanChen, self).get_compute_kernels(runner, full_output, bulk)
         return list(zip(macro_kernels, sim_kernels))
+
+
+class Particle(object):
+    """An immersed boundary marker (reference lb_single.py:406-411): a position in global lattice coordinates -- those of
+    hx, hy, hz: a node sits at integer coordinates --, tied to ref_position (default: where it starts) by a spring of
+    the given stiffness.  `mass` is kept for script compatibility; nothing reads it (nor does the reference)."""
+
+    def __init__(self, position, mass=1.0, stiffness=1.0, ref_position=None):
+        self.position = tuple(float(x) for x in position)
+        self.mass = mass
+        self.ref_position = self.position if ref_position is None else tuple(float(x) for x in ref_position)
+        self.stiffness = float(stiffness)
+        assert len(self.ref_position) == len(self.position)
+
+
+class LBIBMFluidSim(LBFluidSim, LBForcedSim):
+    """Single-phase simulation with immersed boundary markers (reference lb_single.py:350-404).  The markers'
+    spring forces are spread into the module's acceleration field before every step and the markers move with the
+    interpolated fluid velocity after it (IBMSubdomainRunner; csrc/slf_ibm.hip).  The module is an ordinary accel_field
+    module, so what check_accel_field refuses is refused here too.  Uniform body forces (constant or time-dependent) add to
+    the field as for any such module; a position-dependent body force would own the same buffer and is refused.
+    `particle_positions` ([n, dim], the run's precision) is refreshed whenever the fields are copied to the host, and
+    travels with checkpoints."""
+    subdomain_runner = subdomain_runner.IBMSubdomainRunner
+    has_accel_field = True
+
+    def __init__(self, config):
+        super(LBIBMFluidSim, self).__init__(config)
+        self._particles = []
+        self.particle_positions = None
+
+    @classmethod
+    def fields(cls):
+        # `force`: the reference's per-node force field, kept so that scripts which name sim.force load; the kernels here read
+        # the module's acceleration field instead, and this one stays zero
+        return LBFluidSim.fields() + [VectorField('force')]
+
+    @property
+    def num_particles(self):
+        return len(self._particles)
+
+    def add_particle(self, particle):
+        assert isinstance(particle, Particle)
+        if len(particle.position) != self.grid.dim:
+            raise ValueError('a particle of a %d-D simulation has %d coordinates' % (self.grid.dim, self.grid.dim))
+        self._particles.append(particle)
+
+    def add_body_force(self, force, grid=0, accel=True):
+        from sailfish_amd import node_type as nt
+        if isinstance(force, nt.DynamicValue) and force.space_dependent():
+            raise NotImplementedError('LBIBMFluidSim: a body force that depends on position together with immersed boundary '
+                                      'markers is not supported -- both would own the acceleration field (uniform forces, '
+                                      'constant or time-dependent, are fine)')
+        super(LBIBMFluidSim, self).add_body_force(force, grid, accel)
+
+    def fill_module_desc(self, kw):
+        super(LBIBMFluidSim, self).fill_module_desc(kw)
+        kw['accel_field'] = 1
+        kw['has_force'] = 1
+
+    def accel_field_at(self, coords):
+        """The field starts from zero: the markers fill it before every step."""
+        return np.zeros((self.grid.dim, len(coords[0])), dtype=np.float64)
+
+    def get_state(self):
+        state = super(LBIBMFluidSim, self).get_state()
+        if self.particle_positions is not None:
+            state['particle_positions'] = np.array(self.particle_positions)
+        return state
+
+    def set_state(self, state):
+        super(LBIBMFluidSim, self).set_state(state)
+        if state.get('particle_positions') is not None:
+            self.particle_positions = np.array(state['particle_positions'])

@@ -1507,3 +1507,73 @@ class NNSubdomainRunner(SubdomainRunner):
         if self._nnx_serial(getattr(self, '_group', None)):
             return
         SubdomainRunner._program_back(self, q, it)
+
+
+class IBMSubdomainRunner(SubdomainRunner):
+    """Runner of lb_single.LBIBMFluidSim (reference subdomain_runner.py:1779-1837, which allocates the marker arrays and
+    never uploads them): uploads the markers, allocates the zero acceleration field and the int64 accumulator, and puts
+    the marker launches on the calc stream around the step's program -- spread and gather in front of it, clear-and-advect
+    behind it (sailfish_amd/ibm.py).  They are direct entry points of the C ABI, which a step plan has no
+    entry for, so they go around StepPlans.run: the same calls on the same stream whether the program between them is
+    replayed from a plan or performed entry by entry.  The sweep always stores rho and v (the markers read v after every
+    step, as the reference's force_field branch does), and steps are never replayed as graphs."""
+    _markers = None
+
+    def set_topology(self, all_specs, global_size, periodic):
+        if len(all_specs) > 1:
+            raise NotImplementedError('LBIBMFluidSim: more than one subdomain is not supported -- markers would cross the '
+                                      'seams and there is no exchange of markers (%d subdomains)' % len(all_specs))
+        super(IBMSubdomainRunner, self).set_topology(all_specs, global_size, periodic)
+
+    def _init_accel_field(self, alloc):
+        super(IBMSubdomainRunner, self)._init_accel_field(alloc)            # the zero field, handed to the module
+        sim = self._sim
+        if not sim.num_particles:
+            return
+        from sailfish_amd import ibm
+        self._markers = ibm.Markers(self.backend, self.module, self.float, self.dim, self._spec.location,
+                                    [p.position for p in sim._particles], [p.ref_position for p in sim._particles],
+                                    [p.stiffness for p in sim._particles])
+        sim.particle_positions = np.array(self._markers.position.T)
+
+    def _sweep_kernels(self, it, sync_req):
+        kernels = self._kernels_full
+        return kernels.primary if (it & 1) == 0 else kernels.secondary
+
+    def step(self, sync_req=False):
+        m = self._markers
+        if m is not None:
+            m.front(self._calc_stream)
+        super(IBMSubdomainRunner, self).step(True)
+        if m is not None:
+            gpu_map = 0 if int(self._desc.fluid_only) else self.gpu_geo_map()
+            m.back(gpu_map, self.gpu_field(self._sim.v), self._calc_stream)
+
+    def fast_forward(self):
+        return 0
+
+    def particle_positions(self):
+        """[n, dim] positions of the markers as they are after the last enqueued step, copied back from the device."""
+        if self._markers is None:
+            return np.zeros((0, self.dim), dtype=self.float)
+        return self._markers.positions(self._calc_stream)
+
+    @property
+    def ibm_outside(self):
+        """Markers the last step held in place: a node of their stencil is not a real node of the subdomain."""
+        return 0 if self._markers is None else self._markers.outside_count(self._calc_stream)
+
+    def _fields_to_host(self, sync=True):
+        super(IBMSubdomainRunner, self)._fields_to_host(sync)
+        if self._markers is not None:
+            self._sim.particle_positions = self.particle_positions()
+
+    def save_checkpoint(self):
+        if self._markers is not None:
+            self._sim.particle_positions = self.particle_positions()
+        super(IBMSubdomainRunner, self).save_checkpoint()
+
+    def restore_checkpoint(self, fname):
+        super(IBMSubdomainRunner, self).restore_checkpoint(fname)
+        if self._markers is not None and self._sim.particle_positions is not None:
+            self._markers.set_positions(self._sim.particle_positions)

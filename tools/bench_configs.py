@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place, 15a,15b acceleration field: four rolls mill 2048^2 / periodic box 256^3 with 15ac,15bc their constant-force baselines -- run those under SLF_VARIANT=0)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place, 15a,15b acceleration field: four rolls mill 2048^2 / periodic box 256^3 with 15ac,15bc their constant-force baselines -- run those under SLF_VARIANT=0, 16a immersed boundary markers: ibm_cylinder 512x128 with 16ac the same channel without markers)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -342,6 +342,31 @@ def main():
             if '15bc' in only:
                 res.append(run('15bc: the same box, constant force, SLF_VARIANT=%s (%s)' % (variant, pattern), ConstantBox,
                                LBGeometry3D, box, 152))
+    # config 16 (only with --only): immersed boundary markers (lb_single.LBIBMFluidSim; csrc/slf_ibm.hip).
+    # 16a: examples/ibm_cylinder.py, 512 x 128 with its 50 markers -- three marker launches around every sweep.  16ac: the
+    # same channel without markers, through the same runner: the ACCF full-output sweep alone, the like-for-like baseline.
+    # Launch-bound at this size: what matters is the time per step, 65536 / MLUPS microseconds.
+    if only & {'16a', '16ac'}:
+        from examples.ibm_cylinder import CylinderSimulation
+        from sailfish.lb_base import LBSim
+
+        class QuietCylinder(CylinderSimulation):
+            after_step = LBSim.after_step             # no probe line: the run is not synchronised every 20 steps
+
+        class NoMarkers(QuietCylinder):
+            def add_particle(self, particle):
+                pass
+
+        for pattern in ('AB',):                       # (the outlet's NTCopy nodes exist in the two-copy pattern only)
+            chan = dict(precision='single', access_pattern=pattern, max_iters=int(20000 * it), benchmark_sample_from=int(5000 * it))
+            per_step = lambda ctrl: {'us_per_step': round(ctrl.runners[0].num_fluid_nodes / ctrl.mlups_total, 3),       # noqa: E731
+                                     'markers': ctrl.runners[0]._sim.num_particles}
+            if '16a' in only:
+                res.append(run('16a: ibm_cylinder D2Q9 512x128, 50 markers (%s)' % pattern, QuietCylinder, LBGeometry2D, chan,
+                               80, extra=per_step))
+            if '16ac' in only:
+                res.append(run('16ac: the same channel, no markers, ACCF full-output sweep (%s)' % pattern, NoMarkers,
+                               LBGeometry2D, chan, 80, extra=per_step))
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
