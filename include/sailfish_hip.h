@@ -61,6 +61,7 @@ enum { SLF_ADDR_DIRECT = 0, SLF_ADDR_INDIRECT = 1 };
  * GUO: feq at u + a/2 plus Guo's source term; EDM (exact difference method): feq at u, then
  * f_i += feq_i(rho, u + a) - feq_i(rho, u).  The output velocity is u + a/2 in both. */
 enum { SLF_FORCE_GUO = 0, SLF_FORCE_EDM = 1 };
+enum { SLF_EQ_BGK = 0, SLF_EQ_SHALLOW_WATER = 1 };      /* slf_module_desc::equilibrium */
 enum { SLF_SUBGRID_NONE = 0, SLF_SUBGRID_LES_SMAGORINSKY = 1 };
 #define SLF_INVALID_NODE 0xffffffffu
 
@@ -120,6 +121,21 @@ typedef struct slf_module_desc {
   int32_t relaxation_enabled;  /* 0 = streaming only (regtest propagation KATs) */
   int32_t has_force;           /* body force present (lb_base.py:331-359) */
   int32_t fluid_only;          /* 1: no node map is read; every real node is a fluid node */
+  /* The equilibrium of the BGK relaxation.  SLF_EQ_BGK (0): the polynomial of every other module.  SLF_EQ_SHALLOW_WATER (1):
+   * the shallow-water model (reference lb_single.py:221-239 LBFreeSurface, sym_equilibrium.py:73-88): rho is the water depth
+   * h, the pressure is gravity h^2 / 2 (`gravity` below), and f_i relaxes towards
+   * w_i h (3/2 gravity h + 3 e.v + 9/2 (e.v)^2 - 3/2 v^2) for i >= 1 and towards h - sum_{i>=1} feq_i for the rest population
+   * -- Zhou's mass-conserving form, NOT the reference's rest population, whose equilibrium sums to h + 2 h v^2 (a stated
+   * difference).  Served: D2Q9, SLF_BGK, simtype = SLF_SIM_LBM, SLF_DENSITY_COMPRESSIBLE, direct addressing,
+   * both precisions and access patterns, body forces (Guo and EDM, constant and accel_field); fluid, ghost, unused,
+   * propagation-only, SLF_NK_FULL_BB, SLF_NK_HALF_BB and SLF_NK_SLIP nodes.  Everything else is refused with
+   * SLF_ERR_UNSUPPORTED, by name; a gravity that is not positive or an equilibrium outside 0 / 1 with SLF_ERR_INVALID.  The
+   * module answers to the kernel names of any single-fluid module; CollideAndPropagateResident does not exist in it.
+   * equilibrium = 0: every module there was before (gravity is not read).  The two members fill what were the four bytes of
+   * padding here and in front of node_params: no other member moves and the structure keeps its size, so struct_size does
+   * NOT tell this layout from the one before -- a caller built against that one must have zeroed the structure (as every
+   * initialiser `= {0}` / memset does) to get the polynomial.  That is why gravity is a float: no hole holds a double. */
+  int32_t equilibrium;
   double tau;                  /* (6 visc + 1)/2, sym.py:847-848 */
   double visc;
   double accel[3];             /* body-force acceleration */
@@ -133,6 +149,8 @@ typedef struct slf_module_desc {
   int32_t type_kind[SLF_MAX_NODE_TYPES]; /* dense type id -> SLF_NK_* */
   int32_t use_link_tags;       /* orientation field of half-BB nodes holds link tags (subdomain.py:593-642) */
   int32_t n_node_params;
+  float gravity;               /* equilibrium = SLF_EQ_SHALLOW_WATER: the gravity (--gravity), > 0; rounded to single
+                                  precision on the way in, whatever the module's precision */
   const double* node_params;   /* kernel_common.mako:523-536; copied at module creation */
   uint64_t dist_stride;        /* elements between consecutive direction arrays; 0 = arr_nx*arr_ny*arr_nz (the
                                   reference's DIST_SIZE, kernel_common.mako:506).  A larger stride only inserts

@@ -129,11 +129,51 @@ inline const char* accf_refusal(const slf_module_desc* d) {
   return nullptr;
 }
 
+// The shallow-water equilibrium (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER) exists in the SW instantiations of the
+// per-node sweep and of SetInitialConditions and nowhere else: what those do not cover is named here and refused.  The
+// value-carrying node types are among it: their reference expressions assume the pressure rho / 3 and would have to be
+// derived again for gravity h^2 / 2.  NULL: the BGK polynomial, or the descriptor is served.  *code: the error to return.
+inline const char* sw_refusal(const slf_module_desc* d, int* code) {
+  *code = SLF_ERR_INVALID;
+  if (d->equilibrium != SLF_EQ_BGK && d->equilibrium != SLF_EQ_SHALLOW_WATER) return "equilibrium must be SLF_EQ_BGK or SLF_EQ_SHALLOW_WATER";
+  if (d->equilibrium == SLF_EQ_BGK) return nullptr;      // (gravity is not read)
+  if (!(d->gravity > 0.0)) return "shallow water: gravity must be > 0";
+  *code = SLF_ERR_UNSUPPORTED;
+  if (d->lattice != SLF_D2Q9) return "shallow water: D2Q9 only (the equilibrium is written for that lattice)";
+  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
+    return "shallow water: the Shan-Chen models are not served; single-fluid modules only";
+  if (d->simtype == SLF_SIM_FREE_ENERGY) return "shallow water: the free-energy model is not served; single-fluid modules only";
+  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return "shallow water: the ternary Shan-Chen model is not served; single-fluid modules only";
+  if (d->simtype != SLF_SIM_LBM) return "shallow water: single-fluid modules only";
+  if (d->model == SLF_MRT) return "shallow water: --model=mrt is not served; the BGK collision only";
+  if (d->model == SLF_ELBM) return "shallow water: --model=elbm is not served; the BGK collision only";
+  if (d->model != SLF_BGK) return "shallow water: the BGK collision only";
+  if (d->entropic_equilibrium) return "shallow water: entropic_equilibrium belongs to --model=elbm, which is not served";
+  if (d->regularized) return "shallow water: --regularized is not served";
+  if (d->subgrid) return "shallow water: --subgrid is not served";
+  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return "shallow water: --minimize_roundoff is not served";
+  if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) return "shallow water: --incompressible is not served (the density is the water depth)";
+  if (d->node_addressing != SLF_ADDR_DIRECT) return "shallow water: --node_addressing=indirect is not served; direct addressing only";
+  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
+    const int k = d->type_kind[i];
+    if (k == SLF_NK_WALL_TMS) return "shallow water: NTWallTMS nodes are not served";
+    if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB ||
+          k == SLF_NK_HALF_BB || k == SLF_NK_SLIP))
+      return "shallow water: fluid, NTFullBBWall, NTHalfBBWall and NTSlip nodes only; the node types that carry a density or a "
+             "velocity (equilibrium, Zou-He, regularized, outflow, do-nothing) are not served";
+  }
+  return nullptr;
+}
+
 inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char** err) {
   *c = ModuleConfig{};
   if (d->struct_size != sizeof(slf_module_desc)) return refuse(err, SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
   if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19 && d->lattice != SLF_D3Q15 && d->lattice != SLF_D3Q27)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported lattice");
+  {
+    int code = SLF_OK;
+    if (const char* why = sw_refusal(d, &code)) return refuse(err, code, why);
+  }
   if (const char* why = accf_refusal(d)) return refuse(err, d->accel_field == 1 ? SLF_ERR_UNSUPPORTED : SLF_ERR_INVALID, why);
   if (const char* why = lat_refusal(d)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
@@ -234,6 +274,8 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   for (int i = 0; i < 27; i++) ph.mrt_rates[i] = d->mrt_rates[i];
   ph.incompressible = d->incompressible;
   ph.accel_field = d->accel_field;
+  ph.equilibrium = d->equilibrium;
+  ph.gravity = d->equilibrium == SLF_EQ_SHALLOW_WATER ? d->gravity : 0.0;
   ph.has_force = d->has_force || d->accel_field;      // a field is a body force
   ph.relaxation_enabled = d->relaxation_enabled;
   ph.force_edm = d->force_implementation == SLF_FORCE_EDM;
@@ -373,6 +415,7 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   }
   if (is_lat_lattice(d->lattice)) g.variant = 0;      // no tuned / whole-row D3Q19 kernels: the sweep of slf_lat.hip
   if (ph.accel_field) g.variant = 0;       // the acceleration field is read by the per-node kernels only (ACCF)
+  if (ph.equilibrium == SLF_EQ_SHALLOW_WATER) g.variant = 0;      // the tuned, whole-row and slot kernels implement the BGK polynomial (SW)
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
   // workgroup; longer rows are cut into 256-thread chunks.
   int bx = ((d->lat_nx - 2 + 63) / 64) * 64;
@@ -536,6 +579,9 @@ inline int resolve(const ModuleConfig& c, const char* name, const KernelRow** ou
     if (c.phys.accel_field)
       return refuse(err, SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: accel_field modules are not served (the resident kernel "
                                               "takes a constant acceleration)");
+    if (c.phys.equilibrium == SLF_EQ_SHALLOW_WATER)
+      return refuse(err, SLF_ERR_UNSUPPORTED, "CollideAndPropagateResident: shallow-water modules are not served (the resident kernel "
+                                              "implements the BGK polynomial)");
     if (int rc = resident_refusal(c, err)) return rc;
   }
   if ((kk == KK_PBC || kk == KK_PBC_SWAP) && c.geo.indirect)

@@ -70,6 +70,10 @@ struct Physics {
   // slf_module_desc::accel_field: the module reads an acceleration per node (SweepArgs::accf); the ACCF instantiations of
   // the per-node kernels run, has_force is set
   int accel_field;
+  // slf_module_desc::equilibrium / gravity: SLF_EQ_SHALLOW_WATER -- the SW instantiations of the per-node kernels and of
+  // init_kernel run (D2Q9, BGK); gravity is read by those only
+  int equilibrium;
+  double gravity;
 };
 
 struct ShanChen {

@@ -33,8 +33,13 @@ namespace slf {
 // BGK and MRT, direct addressing, none of ROUNDOFF, TURB, TMS; launched iff the module has the flag (launch_sweep2).
 // Workgroups of at most 512 threads as well: under the 128 VGPRs of a 1024-thread workgroup the D3Q19 odd-step
 // instantiations spill (20-32 bytes of scratch per lane in single, 84-136 in double precision: profiles/accf).
+// SW: the instantiations for shallow-water modules (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER): the BGK relaxation
+// takes sw_equilibrium (slf_node.h) instead of the polynomial, nothing else differs.  D2Q9, BGK, direct addressing, with and
+// without ACCF, none of ROUNDOFF, TURB, TMS; launched iff the module has the flag (launch_sweep2).  Nine populations and one
+// more equilibrium array: no scratch under the 128 VGPRs of a 1024-thread workgroup (profiles/sw), so the bound stays 1024;
+// the ACCF ones inherit 512.
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false,
-          bool TMS = false, bool ACCF = false>
+          bool TMS = false, bool ACCF = false, bool SW = false>
 __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const int gy = p.y0 + (int)blockIdx.y;
@@ -91,10 +96,11 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
   bool wet = true;
   if constexpr (ACCF) {
     static_for<0, L::dim>([&](auto D) { acc[D] = p.cp.accel[D] + acc[D]; });
-    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, 1, 2, ROUNDOFF, TURB, TMS, true>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet,
-                                                                                      si, &acc);
+    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, 1, 2, ROUNDOFF, TURB, TMS, true, SW>(p, f, code, kind, gi, ox, oy, oz, rho, v,
+                                                                                          wet, si, &acc);
   } else {
-    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS, false, SW>(p, f, code, kind, gi, ox, oy, oz,
+                                                                                                       rho, v, wet, si);
   }
 
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
@@ -234,18 +240,20 @@ static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, co
   pick<int, 0, 1, 2>(model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
     pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
       pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) { pick_bool(ph.tms_mask != 0, [&](auto TMS) {
-      pick_bool(ph.accel_field != 0, [&](auto ACCF) {
+      pick_bool(ph.accel_field != 0, [&](auto ACCF) { pick_bool(ph.equilibrium == SLF_EQ_SHALLOW_WATER, [&](auto SW) {
         // indirect addressing: the node map is always read; --minimize_roundoff and --regularized / --subgrid exclude
         // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only;
         // Tamm-Mott-Smith walls are node types: no such instantiation without the node map; an acceleration field:
-        // BGK / MRT with direct addressing and none of the three (refused at module creation otherwise, slf_bind.h)
+        // BGK / MRT with direct addressing and none of the three (refused at module creation otherwise, slf_bind.h); the
+        // shallow-water equilibrium: D2Q9, BGK, direct addressing, none of the three, with or without the field
         if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0) || (TMS && !G) ||
-                      (ACCF && (ROUNDOFF || TURB || TMS || IND || MODEL == 2))) return;
+                      (ACCF && (ROUNDOFF || TURB || TMS || IND || MODEL == 2)) ||
+                      (SW && (L::id != D2Q9::id || MODEL != 0 || ROUNDOFF || TURB || TMS || IND))) return;
         else {
-          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS, ACCF>), grid, block, 0, s, p);
+          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS, ACCF, SW>), grid, block, 0, s, p);
           e = hipGetLastError();
         }
-      });
+      }); });
       }); }); });
     }); });
   }); });

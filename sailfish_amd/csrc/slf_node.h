@@ -122,10 +122,37 @@ SLF_D R feq(R rho, R rho0, const R (&v)[3], R u15) {
   }
 }
 
+// The shallow-water equilibrium (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER; Zhou, Comput. Methods Appl. Mech.
+// Engrg. 191 (2002); reference sym_equilibrium.py:73-88 for i >= 1).  h: water depth, g: gravity.
+//   i >= 1:  fe_i = w_i * (h * (((1.5 g) h + eu (3 + 4.5 eu)) - 1.5 v^2))
+//   rest:    fe_0 = h - (((fe_1 + fe_2) + fe_3) + ... + fe_8)         -- LAST, index order: the populations sum to h
+// (Zhou's h - w_0 h (15/8 g h + 3/2 v^2) in exact arithmetic.  The reference's rest population carries -3 v^2 instead of
+// +3/2 v^2: its equilibrium sums to h + 2 h v^2 and every collision creates mass -- not ported)
+template <class L, class R>
+SLF_D void sw_equilibrium(R (&fe)[L::Q], R h, const R (&v)[3], R g) {
+  static_assert(L::dim == 2 && L::Q == 9, "the shallow-water equilibrium is written for D2Q9");
+  const R gh15 = ((R)1.5 * g) * h;
+  const R u15 = usq15<L, R>(v);
+  R sum = (R)0;
+  static_for<1, L::Q>([&](auto I) {
+    const R eu = edotv<L, R, I>(v);
+    fe[I] = Weights<L, R>::w(I) * (h * ((gh15 + eu * ((R)3 + (R)4.5 * eu)) - u15));
+    if constexpr (I == 1) sum = fe[I];
+    else sum = sum + fe[I];
+  });
+  fe[0] = h - sum;
+}
+
 template <class L, class R>
 struct CollideParams {
   R omega;        // 1/tau
-  R mrt_s[L::Q];  // MRT relaxation rates (0 for conserved moments)
+  // MRT relaxation rates (0 for conserved moments) -- or, in a shallow-water module (BGK by construction: no rates), its
+  // gravity, a wave-uniform scalar read by the SW instantiations only.  The two share the slot so that the kernel-argument
+  // layout of every kernel stays what it was (SweepParams, slf_sweep.h).
+  union {
+    R mrt_s[L::Q];
+    R gravity;
+  };
   R accel[3];     // body-force acceleration
   R guo_pref;     // 3 (1 - 1/(2 tau))
   int incompressible;
@@ -135,9 +162,43 @@ struct CollideParams {
 
 // C5 + C6: BGK relaxation with optional Guo forcing by the acceleration a.  v is updated to the
 // velocity used for the equilibrium (u + a/2), which is also the reference's output velocity.
-template <class L, class R>
+// SW: the shallow-water equilibrium (sw_equilibrium; rho is the depth, grav the gravity) takes the place of the polynomial
+// -- once in the relaxation, twice in the exact-difference force.  Nothing else changes: the Guo term's moments do not
+// depend on the pressure law, and the velocity shift and the output velocity are the same.
+template <class L, class R, bool SW = false>
 SLF_D void bgk_relax_accel(R (&f)[L::Q], R rho, R (&v)[3], R omega, R guo_pref, bool incompressible, bool has_force,
-                           const R (&a)[3], bool edm = false) {
+                           const R (&a)[3], bool edm = false, R grav = (R)0) {
+  if constexpr (SW) {
+    R fe[L::Q];
+    if (has_force && edm) {
+      R vs[3] = {v[0] + a[0], v[1] + a[1], (R)0};
+      R fs[L::Q];
+      sw_equilibrium<L, R>(fe, rho, v, grav);
+      sw_equilibrium<L, R>(fs, rho, vs, grav);
+      static_for<0, L::Q>([&](auto I) {
+        f[I] = f[I] + omega * (fe[I] - f[I]);
+        f[I] = f[I] + (fs[I] - fe[I]);
+      });
+      static_for<0, L::dim>([&](auto D) { v[D] = v[D] + (R)0.5 * a[D]; });
+      return;
+    }
+    if (has_force) {
+      static_for<0, L::dim>([&](auto D) { v[D] = v[D] + (R)0.5 * a[D]; });
+    }
+    sw_equilibrium<L, R>(fe, rho, v, grav);
+    static_for<0, L::Q>([&](auto I) { f[I] = f[I] + omega * (fe[I] - f[I]); });
+    if (has_force) {
+      const R pref = rho * guo_pref;
+      const R va = v[0] * a[0] + v[1] * a[1];
+      static_for<0, L::Q>([&](auto I) {
+        const R eu = edotv<L, R, I>(v);
+        const R ea = edotv<L, R, I>(a);
+        const R t = (ea - va) + (R)3 * eu * ea;
+        f[I] = f[I] + pref * Weights<L, R>::w(I) * t;
+      });
+    }
+    return;
+  }
   const R rho0 = incompressible ? (R)1 : rho;
   if (has_force && edm) {
     // exact difference method (relaxation_common.mako:66-73, sym_force.py:184-193): equilibrium at the
@@ -237,10 +298,13 @@ SLF_D void bgk_relax_roundoff(R (&f)[L::Q], R drho, R (&v)[3], R omega, R guo_pr
 //   1  the module has one (the launchers pick this instantiation iff Physics::has_force): no run-time "is there a
 //      force" test either -- 95-100 -> 74-82 VGPRs in the node-map row kernels;
 //   2  decided at run time (the per-node kernels, which exist once per module kind).
+// SW: a shallow-water module (bgk_relax_accel<..., SW>): the per-node kernels only, where FORCE is FORCE_RUNTIME.
 constexpr int FORCE_RUNTIME = 2;
-template <class L, class R, int FORCE = FORCE_RUNTIME>
+template <class L, class R, int FORCE = FORCE_RUNTIME, bool SW = false>
 SLF_D void bgk_relax(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L, R>& cp) {
-  if constexpr (FORCE == 0) {
+  if constexpr (SW) {
+    bgk_relax_accel<L, R, true>(f, rho, v, cp.omega, cp.guo_pref, false, cp.has_force != 0, cp.accel, cp.force_edm != 0, cp.gravity);
+  } else if constexpr (FORCE == 0) {
     bgk_relax_accel<L, R>(f, rho, v, cp.omega, cp.guo_pref, cp.incompressible != 0, false, cp.accel, false);
   } else {
     const bool has_force = (FORCE == 1) ? true : (cp.has_force != 0);
@@ -251,9 +315,10 @@ SLF_D void bgk_relax(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L, R>& 
 
 // The same with the acceleration as an argument (the ACCF instantiations of the per-node kernels: cp.accel + the node's
 // entry of the acceleration field, slf_sweep.h); the module has a force by construction.
-template <class L, class R>
+template <class L, class R, bool SW = false>
 SLF_D void bgk_relax(R (&f)[L::Q], R rho, R (&v)[3], const CollideParams<L, R>& cp, const R (&a)[3]) {
-  bgk_relax_accel<L, R>(f, rho, v, cp.omega, cp.guo_pref, cp.incompressible != 0, true, a, cp.force_edm != 0);
+  if constexpr (SW) bgk_relax_accel<L, R, true>(f, rho, v, cp.omega, cp.guo_pref, false, true, a, cp.force_edm != 0, cp.gravity);
+  else bgk_relax_accel<L, R>(f, rho, v, cp.omega, cp.guo_pref, cp.incompressible != 0, true, a, cp.force_edm != 0);
 }
 
 // C7 helpers: one row of the integer moment matrix applied to a vector.

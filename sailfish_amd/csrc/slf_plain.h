@@ -12,6 +12,22 @@ namespace slf {
 
 // SetInitialConditions: f_i = feq_i(rho, v) on *every* node of the lattice box,
 // no type test (ghost nodes carry the non-finite sentinels of the host fields).
+// SW: a shallow-water module (slf_module_desc::equilibrium): f = sw_equilibrium(h = rho, v, gravity), slf_node.h.  The switch
+// is a second kernel, not a template argument of init_kernel, whose name -- and with it the device code of slf_lat.hip,
+// which instantiates this header for D3Q15 and D3Q27 -- stays what it was; launch_init2 names it for D2Q9 only.
+template <class L, class R>
+__global__ void __launch_bounds__(256) init_kernel_sw(R* dist, const R* __restrict__ irho, const R* __restrict__ ivx,
+                                                      const R* __restrict__ ivy, Geometry g, R gravity) {
+  const int gx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int gy = (int)blockIdx.y;
+  if (gx > g.lat_nx - 1) return;
+  const uint32_t gi = (uint32_t)gx + (uint32_t)g.arr_nx * (uint32_t)gy;
+  const R v[3] = {ivx[gi], ivy[gi], (R)0};
+  R fe[L::Q];
+  sw_equilibrium<L, R>(fe, irho[gi], v, gravity);
+  static_for<0, L::Q>([&](auto I) { (dist + (size_t)g.dist_size * (size_t)I)[gi] = fe[I]; });
+}
+
 template <class L, class R>
 __global__ void __launch_bounds__(256) init_kernel(R* dist, const R* __restrict__ irho, const R* __restrict__ ivx,
                                                    const R* __restrict__ ivy, const R* __restrict__ ivz, Geometry g,
@@ -181,6 +197,14 @@ static hipError_t launch_init2(LR<L, R>, const Geometry& g, const Physics& ph, v
                                const void* const v[3], const void* nodes, hipStream_t s) {
   dim3 block(256, 1, 1);
   dim3 grid((g.lat_nx + 255) / 256, g.lat_ny, g.lat_nz);
+  if (ph.equilibrium == SLF_EQ_SHALLOW_WATER) {      // D2Q9, direct addressing (module_config); no other lattice has the kernel
+    if constexpr (L::id == D2Q9::id) {
+      hipLaunchKernelGGL((init_kernel_sw<L, R>), grid, block, 0, s, (R*)dist, (const R*)rho, (const R*)v[0], (const R*)v[1], g,
+                         (R)ph.gravity);
+      return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+  }
   hipLaunchKernelGGL((init_kernel<L, R>), grid, block, 0, s, (R*)dist, (const R*)rho, (const R*)v[0], (const R*)v[1],
                      (const R*)v[2], g, ph.incompressible, (const uint32_t*)nodes);
   return hipGetLastError();

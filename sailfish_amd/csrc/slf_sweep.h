@@ -396,14 +396,19 @@ __device__ __forceinline__ void tms_fix_missing(const Geometry& g, R (&f)[L::Q],
 // ACCF: the module has an acceleration field (slf_module_desc::accel_field): the collision takes the node's acceleration
 // from `acc` (the caller formed cp.accel + field[gi]) instead of cp.accel.  The per-node kernels only; MODEL = BGK or MRT,
 // none of INDIRECT, ROUNDOFF, TURB, TMS; `acc` is not read otherwise.
+// SW: a shallow-water module (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER): the BGK relaxation uses sw_equilibrium
+// (slf_node.h) with p.cp.gravity -- and that is all: moments, bounce-back, the half-way store, the slip reflection and
+// streaming are the code of every other module.  The per-node kernels only; D2Q9, MODEL = BGK, with or without ACCF, none
+// of INDIRECT, ROUNDOFF, TURB, TMS; the value-carrying node kinds are refused at module creation (slf_bind.h sw_refusal).
 template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, int FORCE = FORCE_RUNTIME, int BCL = 2,
-          bool ROUNDOFF = false, bool TURB = false, bool TMS = false, bool ACCF = false>
+          bool ROUNDOFF = false, bool TURB = false, bool TMS = false, bool ACCF = false, bool SW = false>
 __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L::Q], uint32_t code, int kind,
                                             uint32_t gi, const AxisOff& ox, const AxisOff& oy, const AxisOff& oz,
                                             R& rho, R (&v)[3], bool& wet, uint32_t si = INVALID_NODE,
                                             const R (*acc)[3] = nullptr) {
   static_assert(!ACCF || ((MODEL == 0 || MODEL == 1) && !INDIRECT && !ROUNDOFF && !TURB && !TMS),
                 "ACCF: BGK / MRT, direct addressing, none of ROUNDOFF, TURB, TMS");
+  static_assert(!SW || (MODEL == 0 && !INDIRECT && !ROUNDOFF && !TURB && !TMS), "SW: BGK, direct addressing, none of ROUNDOFF, TURB, TMS");
   if constexpr (!INDIRECT) si = gi;
   const Geometry& g = p.g;
   const size_t ds = g.dist_size;
@@ -473,15 +478,29 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (kind == NK_FULL_BB) bounce_back<L, R>(f);
     if (wet && p.relaxation_enabled) {
-      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
       else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
-      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
+      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
       else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
     }
+  } else if constexpr (GENERAL && SW) {
+    // The node kinds a shallow-water module can have (slf_bind.h sw_refusal): fluid, full-way and half-way bounce-back,
+    // slip -- the same functions in the same order as below, without the code of the kinds that carry a density or a
+    // velocity (the outflow nodes' reads of the input array cost the two-copy instantiations 32 bytes of scratch per lane).
+    wet = kind_is_wet(kind);
+    const int orientation = (int)(code >> g.orient_shift);
+    macro_standard<L, R>(f, false, rho, v);
+    if (kind == NK_FULL_BB) bounce_back<L, R>(f);
+    if (kind == NK_SLIP) slip_reflect<L, R>(f, orientation);
+    if (wet && p.relaxation_enabled) {
+      if constexpr (ACCF) bgk_relax<L, R, true>(f, rho, v, p.cp, *acc);
+      else bgk_relax<L, R, FORCE, true>(f, rho, v, p.cp);
+    }
+    if (kind == NK_HALF_BB) half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
   } else if constexpr (GENERAL) {
     wet = kind_is_wet(kind);
     const int orientation = (int)(code >> g.orient_shift);
-    const int pidx = (int)((code >> g.param_shift) & g.param_mask);
+    const int pidx =(int)((code >> g.param_shift) & g.param_mask);
     const bool inc = p.cp.incompressible != 0;
     R tg_rho = (R)0, tg_v[3] = {(R)0, (R)0, (R)0};
     bool tms = false;
@@ -581,7 +600,7 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     // ---- collision (relaxate, relaxation.mako:196-202: wet nodes only)
     if (wet && p.relaxation_enabled) {
       if constexpr (ACCF && MODEL == 0) {
-        bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+        bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
       } else if constexpr (ACCF) {
         mrt_relax<L, R, 1>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY, *acc);
       } else if constexpr (MODEL == 2) {
@@ -589,7 +608,7 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
       } else if constexpr (MODEL == 0 && TURB) {
         bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
       } else if constexpr (MODEL == 0) {
-        bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
+        bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
       } else {
         mrt_relax<L, R, FORCE>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY);
       }
@@ -605,11 +624,11 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
   } else {
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (p.relaxation_enabled) {
-      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R>(f, rho, v, p.cp, *acc);
+      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
       else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
       else if constexpr (MODEL == 2) elbm_collide<L, R>(p, f, rho, v, gi);
       else if constexpr (MODEL == 0 && TURB) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
-      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE>(f, rho, v, p.cp);
+      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
       else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
     }
   }
@@ -674,6 +693,7 @@ inline SweepParams<L, R> make_params(const Geometry& g, const Physics& ph, const
   p.cp.incompressible = ph.incompressible;
   p.cp.has_force = ph.has_force;
   p.cp.force_edm = ph.force_edm;
+  if (ph.equilibrium != 0) p.cp.gravity = (R)ph.gravity;      // shares the slot of mrt_s: such a module is BGK
   return p;
 }
 

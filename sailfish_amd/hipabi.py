@@ -14,6 +14,7 @@ SLF_MAX_Q = 27
 SLF_D2Q9, SLF_D3Q19, SLF_D3Q15, SLF_D3Q27 = 0, 1, 2, 3
 SLF_BGK, SLF_MRT, SLF_ELBM = 0, 1, 2
 SLF_AB, SLF_AA = 0, 1
+SLF_EQ_BGK, SLF_EQ_SHALLOW_WATER = 0, 1
 SLF_SIM_LBM, SLF_SIM_SHAN_CHEN_BINARY, SLF_SIM_SHAN_CHEN_SINGLE, SLF_SIM_FREE_ENERGY, SLF_SIM_SHAN_CHEN_TERNARY = 0, 1, 2, 3, 4
 (SLF_NK_FLUID, SLF_NK_GHOST, SLF_NK_UNUSED, SLF_NK_PROPAGATION_ONLY, SLF_NK_FULL_BB, SLF_NK_HALF_BB,
  SLF_NK_REGULARIZED_VELOCITY, SLF_NK_EQUILIBRIUM_DENSITY, SLF_NK_EQUILIBRIUM_VELOCITY, SLF_NK_ZOUHE_VELOCITY,
@@ -36,6 +37,7 @@ class SlfModuleDesc(Structure):
         ('periodic_fused', c_int32 * 3),
         ('incompressible', c_int32), ('relaxation_enabled', c_int32), ('has_force', c_int32),
         ('fluid_only', c_int32),
+        ('equilibrium', c_int32),       # SLF_EQ_BGK | SLF_EQ_SHALLOW_WATER (LBFreeSurface: rho is the water depth); fills a hole
         ('tau', c_double), ('visc', c_double),
         ('accel', c_double * 3),
         ('mrt_rates', c_double * SLF_MAX_Q),
@@ -45,6 +47,7 @@ class SlfModuleDesc(Structure):
         ('type_kind', c_int32 * SLF_MAX_NODE_TYPES),
         ('use_link_tags', c_int32),
         ('n_node_params', c_int32),
+        ('gravity', c_float),           # shallow water: the pressure is gravity h^2 / 2; fills the hole in front of node_params
         ('node_params', POINTER(c_double)),
         ('dist_stride', ctypes.c_uint64),
         ('periodic_local', c_int32 * 3),

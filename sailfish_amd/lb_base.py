@@ -219,6 +219,7 @@ class LBSim(object):
         same at module creation)."""
         cls.check_lattice(kw)
         cls.check_accel_field(kw)
+        cls.check_shallow_water(kw)
         if hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []) and kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
             raise NotImplementedError('NTWallTMS nodes: single-fluid simulations only (the Shan-Chen kernels serve fluid and '
                                       'full-way bounce-back nodes)')
@@ -286,6 +287,51 @@ class LBSim(object):
             why = 'NTWallTMS nodes are not served'
         if why:
             raise NotImplementedError('body forces that depend on position: %s' % why)
+
+    # what the shallow-water sweep serves: nodes whose code moves populations and carries neither a density nor a velocity
+    SW_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
+                hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB, hipabi.SLF_NK_SLIP)
+
+    @staticmethod
+    def check_shallow_water(kw):
+        """The shallow-water equilibrium (equilibrium = SLF_EQ_SHALLOW_WATER, LBFreeSurface) exists in one family of sweep
+        kernels (csrc/slf_kernels.hip, the SW instantiations of the per-node sweep): single fluid, D2Q9, BGK, the compressible
+        density model, dense addressing, fluid / bounce-back / slip nodes.  The rest is refused here, naming the option or the
+        node type (the library refuses the same at module creation)."""
+        if not kw.get('equilibrium'):
+            return
+        why = None
+        model = kw.get('model', hipabi.SLF_BGK)
+        kinds = list(kw.get('type_kind', []))
+        if not kw.get('gravity', 0.0) > 0.0:
+            raise ValueError('shallow water: --gravity must be positive')
+        if kw.get('lattice', hipabi.SLF_D2Q9) != hipabi.SLF_D2Q9:
+            why = 'D2Q9 only'
+        elif kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
+            why = 'single-fluid simulations only'
+        elif model != hipabi.SLF_BGK:
+            why = '--model=%s is not served; the BGK collision only' % {hipabi.SLF_MRT: 'mrt', hipabi.SLF_ELBM: 'elbm'}.get(model, model)
+        elif kw.get('entropic_equilibrium'):
+            why = '--entropic_equilibrium belongs to --model=elbm, which is not served'
+        elif kw.get('regularized'):
+            why = '--regularized is not served'
+        elif kw.get('subgrid'):
+            why = '--subgrid is not served'
+        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
+            why = '--minimize_roundoff is not served'
+        elif kw.get('incompressible'):
+            why = '--incompressible is not served (the density is the water depth)'
+        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
+            why = '--node_addressing=indirect is not served; direct addressing only'
+        elif hipabi.SLF_NK_WALL_TMS in kinds:
+            why = 'NTWallTMS nodes are not served'
+        elif any(k not in LBSim.SW_KINDS for k in kinds):
+            bad = set(kinds) - set(LBSim.SW_KINDS)
+            names = sorted(cls.__name__ for cls, k in nt.HIP_KIND.items() if k in bad)
+            why = '%s nodes are not served: fluid, NTFullBBWall, NTHalfBBWall and NTSlip nodes only (the node types that ' \
+                  'carry a density or a velocity assume the pressure rho / 3)' % ' / '.join(names)
+        if why:
+            raise NotImplementedError('shallow water (LBFreeSurface): %s' % why)
 
     def fill_module_desc(self, kw):
         """Contributes to the kernel-module descriptor (the counterpart of the reference's

@@ -230,6 +230,52 @@ class LBEntropicFluidSim(LBFluidSim):
         return [ScalarField('rho'), VectorField('v'), ScalarField('alpha', init=2.0)]
 
 
+class LBFreeSurface(LBFluidSim):
+    """Shallow-water (free surface) lattice Boltzmann model (reference lb_single.py:221-239).
+
+    `rho` is the water depth h and `v` the depth-averaged velocity; the pressure is gravity h^2 / 2 (--gravity), so small
+    waves on a layer of depth h0 travel at sqrt(gravity h0).  D2Q9 and BGK, whatever --grid and --model say.  The moving
+    populations relax towards the reference's equilibrium; the rest population relaxes towards h minus their sum, which
+    conserves the water volume exactly -- the reference's own rest population does not (its equilibrium sums to
+    h + 2 h v^2), and there is no switch back to it.  Walls are NTFullBBWall, NTHalfBBWall and NTSlip; the node types that
+    carry a density or a velocity are refused.  The kernels read --gravity rounded to single precision, in both precisions
+    (the module descriptor carries it as a float).  With LBForcedSim, body forces act as on any single fluid: a bed slope is
+    the acceleration -gravity grad z_b, a function of position (add_body_force(DynamicValue(...)))."""
+
+    @classmethod
+    def modify_config(cls, config):
+        # the reference overrides both silently; a collision model somebody asked for is refused by name instead (bgk is
+        # the default of --model, so anything else was typed)
+        model = getattr(config, 'model', 'bgk')
+        if model != 'bgk':
+            raise NotImplementedError('shallow water (LBFreeSurface): --model=%s is not served; the BGK collision only' % model)
+        config.grid = 'D2Q9'
+        config.model = 'bgk'
+
+    @classmethod
+    def add_options(cls, group, dim):
+        group.add_argument('--gravity', type=float, default=0.001, help='gravitational acceleration')
+
+    def constants(self):
+        ret = super(LBFreeSurface, self).constants()
+        ret['gravity'] = self.config.gravity
+        return ret
+
+    def fill_module_desc(self, kw):
+        super(LBFreeSurface, self).fill_module_desc(kw)
+        kw.update(equilibrium=hipabi.SLF_EQ_SHALLOW_WATER, gravity=float(self.config.gravity))
+        # what the command line alone decides is refused here, before the geometry is encoded (check_module_desc sees the
+        # node types later); the addressing is not part of `kw` yet
+        indirect = getattr(self.config, 'node_addressing', 'direct') == 'indirect'
+        self.check_shallow_water(dict(kw, node_addressing=hipabi.SLF_ADDR_INDIRECT if indirect else hipabi.SLF_ADDR_DIRECT))
+
+    # CollideAndPropagateResident implements the BGK polynomial and does not exist in a shallow-water module: the class
+    # has no such kernels (SubdomainRunner._resident_setup asks with hasattr), so small boxes run one launch per step
+    @property
+    def get_resident_kernels(self):
+        raise AttributeError('LBFreeSurface has no several-steps-per-launch kernels')
+
+
 class LBSingleFluidShanChen(LBFluidSim, LBForcedSim):
     """Single-component Shan-Chen model (reference lb_single.py:242-347): every step computes the density
     field first (PrepareMacroFields), then collides with the pseudopotential force added by Guo forcing."""
