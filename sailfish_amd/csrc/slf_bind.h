@@ -11,6 +11,7 @@
 #include "../../include/sailfish_hip.h"
 #include "slf_kernels.h"
 #include "slf_node.h"
+#include "slf_variant.h"
 
 #ifndef SLF_DEFAULT_VARIANT
 #define SLF_DEFAULT_VARIANT 11
@@ -161,6 +162,17 @@ inline const char* sw_refusal(const slf_module_desc* d, int* code) {
           k == SLF_NK_HALF_BB || k == SLF_NK_SLIP))
       return "shallow water: fluid, NTFullBBWall, NTHalfBBWall and NTSlip nodes only; the node types that carry a density or a "
              "velocity (equilibrium, Zou-He, regularized, outflow, do-nothing) are not served";
+  }
+  return nullptr;
+}
+
+// Single-fluid D2Q9 / D3Q19 modules can always end up in the per-node sweep (launch_sweep, slf_kernels.hip: whatever the tuned
+// and whole-row kernels decline).  NULL: every variant of it the module's steps select exists (slf_variant.h); otherwise the
+// rule the missing one breaks -- a combination that the refusals above let through and no instantiation serves.
+inline const char* per_node_variants_exist(const ModuleConfig& c) {
+  for (Prop prop : {PROP_AB, PROP_AA_EVEN, PROP_AA_ODD}) {
+    if ((prop == PROP_AB) != (c.access_pattern == SLF_AB)) continue;
+    if (const char* why = per_node_variant_conflict(c.sel.lattice, per_node_variant_of(c.sel, c.geo, c.phys, prop))) return why;
   }
   return nullptr;
 }
@@ -422,9 +434,16 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   if (bx > 1024) bx = 256;
   const char* env = getenv("SLF_BLOCK_X");
   if (env && atoi(env) >= 64 && atoi(env) <= 1024 && atoi(env) % 64 == 0) bx = atoi(env);
-  if (ph.accel_field && bx > 512) bx = 512;      // the ACCF instantiations are bounded to 512 threads (slf_kernels.hip)
+  const bool per_node = !c->sc.enabled && !c->fe.enabled && !c->sc3.enabled && !is_lat_lattice(d->lattice);
+  if (per_node) {      // the launch bound of the module's per-node instantiations (the same for every step)
+    const int bound = sweep_max_threads(per_node_variant_of(c->sel, g, ph, PROP_AB));
+    if (bx > bound) bx = bound;
+  }
   c->block_x = bx;
   c->n_node_params = d->n_node_params > 0 ? d->n_node_params : 0;
+  if (per_node) {
+    if (const char* why = per_node_variants_exist(*c)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  }
   return SLF_OK;
 }
 

@@ -3,6 +3,8 @@
 //   if constexpr (<combination nobody launches>) return; else hipLaunchKernelGGL(...)
 // and that condition is where "which instantiations exist" is written down: what it names is not instantiated.  A launcher
 // with such a condition returns hipErrorInvalidValue unless the launch was reached, so a wrong condition is an error.
+// The per-node sweep's condition is a constexpr function of a SweepVariant (slf_variant.h: per_node_variant_exists), which
+// module_config() (slf_bind.h) asks as well: there the error is reported at module creation, on a CPU.
 #pragma once
 #include <type_traits>
 #include "slf_kernels.h"

@@ -65,7 +65,7 @@ struct Physics {
   // NTWallTMS (Tamm-Mott-Smith wall): bit t set = dense type id t is a TMS wall; 0: the module has none.  Inside the kernels
   // such a type is a half-way bounce-back type (its entry in Geometry::type_lut) with this flag (SweepParams::tms_mask),
   // read only by the boundary-condition code of the instantiations launched for modules that have one
-  // (node_update<..., TMS = true>, slf_sweep.h).  Kept out of Geometry, which every kernel of the library takes by value.
+  // (node_update with V.tms, slf_sweep.h).  Kept out of Geometry, which every kernel of the library takes by value.
   uint32_t tms_mask;
   // slf_module_desc::accel_field: the module reads an acceleration per node (SweepArgs::accf); the ACCF instantiations of
   // the per-node kernels run, has_force is set

@@ -24,23 +24,12 @@
 
 namespace slf {
 
-// TURB (--regularized / --subgrid): workgroups of at most 512 threads, i.e. 256 VGPRs -- the non-equilibrium flux tensor on
-// top of the collision does not fit the 128 of a 1024-thread workgroup (76-152 bytes of scratch per lane in the odd step).
-// MODEL = 2 (--model=elbm): the same bound -- f and fneq stay live across the Newton solve.
-// TMS: the instantiations for modules with Tamm-Mott-Smith wall nodes (node_update<..., TMS>, slf_sweep.h).
-// ACCF: the instantiations for modules with an acceleration field (slf_module_desc::accel_field): the node's acceleration
-// is cp.accel + field[d][gi], one coalesced load per dimension next to the population loads, live across the collision.
-// BGK and MRT, direct addressing, none of ROUNDOFF, TURB, TMS; launched iff the module has the flag (launch_sweep2).
-// Workgroups of at most 512 threads as well: under the 128 VGPRs of a 1024-thread workgroup the D3Q19 odd-step
-// instantiations spill (20-32 bytes of scratch per lane in single, 84-136 in double precision: profiles/accf).
-// SW: the instantiations for shallow-water modules (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER): the BGK relaxation
-// takes sw_equilibrium (slf_node.h) instead of the polynomial, nothing else differs.  D2Q9, BGK, direct addressing, with and
-// without ACCF, none of ROUNDOFF, TURB, TMS; launched iff the module has the flag (launch_sweep2).  Nine populations and one
-// more equilibrium array: no scratch under the 128 VGPRs of a 1024-thread workgroup (profiles/sw), so the bound stays 1024;
-// the ACCF ones inherit 512.
-template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, bool ROUNDOFF = false, bool TURB = false,
-          bool TMS = false, bool ACCF = false, bool SW = false>
-__global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) sweep_kernel(const SweepParams<L, R> p) {
+// V: the variant (SweepVariant, slf_variant.h).  Which ones are instantiated: per_node_variant_exists(); launched iff the
+// module's run-time values name them (per_node_variant_of(), launch_sweep2); the launch bound: sweep_max_threads().
+// V.accf: the node's acceleration is cp.accel + field[d][gi], one coalesced load per dimension next to the population
+// loads, live across the collision.
+template <class L, class R, SweepVariant V>
+__global__ void __launch_bounds__(sweep_max_threads(V)) sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
   const int gy = p.y0 + (int)blockIdx.y;
   const int gz = (L::dim == 3) ? p.z0 + (int)blockIdx.z : 0;
@@ -55,13 +44,13 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
   // indirect addressing (reference kernel_common.mako:140-167): the distribution arrays hold active
   // nodes only; si = slot of this node, neighbours are translated through the same dense table
   uint32_t si = gi;
-  if constexpr (INDIRECT) {
+  if constexpr (V.indirect) {
     si = p.nodes[gi];
     if (si == INVALID_NODE) return;
   }
   int kind = NK_FLUID;
   uint32_t code = 0;
-  if constexpr (GENERAL) {
+  if constexpr (V.general) {
     code = p.map[gi];
     kind = node_kind(g.type_lut, g.type_mask, code);
     if (kind_is_excluded(kind)) return;
@@ -74,7 +63,7 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
 
   // the acceleration field: issued in front of the population loads, so that all of them are in flight together
   R acc[3] = {(R)0, (R)0, (R)0};
-  if constexpr (ACCF) {
+  if constexpr (V.accf) {
     const size_t fs = (size_t)g.arr_nxy * (size_t)g.arr_nz;
     static_for<0, L::dim>([&](auto D) { acc[D] = (p.accf + fs * (size_t)D)[gi]; });
   }
@@ -82,11 +71,11 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
   // ---- load (reference getDist, geo_helpers.mako:258-276)
   R f[L::Q];
   static_for<0, L::Q>([&](auto I) {
-    if constexpr (PROP == PROP_AA_ODD) {
+    if constexpr (V.prop == PROP_AA_ODD) {
       const int off = dir_offset<L, I>(ox, oy, oz, false);
       uint32_t sn = (uint32_t)((int)gi + off);
-      if constexpr (INDIRECT) sn = p.nodes[sn];
-      f[I] = (!INDIRECT || sn != INVALID_NODE) ? (p.din + ds * (size_t)L::opp(I))[sn] : (R)0;
+      if constexpr (V.indirect) sn = p.nodes[sn];
+      f[I] = (!V.indirect || sn != INVALID_NODE) ? (p.din + ds * (size_t)L::opp(I))[sn] : (R)0;
     } else {
       f[I] = (p.din + ds * (size_t)I)[si];
     }
@@ -94,14 +83,8 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
 
   R rho, v[3];
   bool wet = true;
-  if constexpr (ACCF) {
-    static_for<0, L::dim>([&](auto D) { acc[D] = p.cp.accel[D] + acc[D]; });
-    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, 1, 2, ROUNDOFF, TURB, TMS, true, SW>(p, f, code, kind, gi, ox, oy, oz, rho, v,
-                                                                                          wet, si, &acc);
-  } else {
-    node_update<L, R, MODEL, PROP, GENERAL, INDIRECT, FORCE_RUNTIME, 2, ROUNDOFF, TURB, TMS, false, SW>(p, f, code, kind, gi, ox, oy, oz,
-                                                                                                       rho, v, wet, si);
-  }
+  if constexpr (V.accf) static_for<0, L::dim>([&](auto D) { acc[D] = p.cp.accel[D] + acc[D]; });
+  node_update<L, R, V>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si, V.accf ? &acc : nullptr);
 
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   // ---- macroscopic output (save_macro_fields, kernel_common.mako:213-240)
@@ -114,13 +97,13 @@ __global__ void __launch_bounds__((TURB || MODEL == 2 || ACCF) ? 512 : 1024) swe
 
   // ---- streaming (propagate, propagation.mako:384-421)
   static_for<0, L::Q>([&](auto I) {
-    if constexpr (PROP == PROP_AA_EVEN) {
+    if constexpr (V.prop == PROP_AA_EVEN) {
       (p.dout + ds * (size_t)L::opp(I))[si] = f[I];
     } else {
       const int off = dir_offset<L, I>(ox, oy, oz, true);
       uint32_t t = (uint32_t)((int)gi + off);
-      if constexpr (INDIRECT) t = p.nodes[t];
-      if (!INDIRECT || t != INVALID_NODE) (p.dout + ds * (size_t)I)[t] = f[I];
+      if constexpr (V.indirect) t = p.nodes[t];
+      if (!V.indirect || t != INVALID_NODE) (p.dout + ds * (size_t)I)[t] = f[I];
     }
   });
 }
@@ -215,42 +198,31 @@ hipError_t launch_box(const KernelSelector& sel, const Geometry& g, bool collect
 // ---------------------------------------------------------------------------
 
 template <class L, class R>
-static hipError_t launch_sweep2(LR<L, R>, int model, Prop prop, bool general, const Geometry& g, const Physics& ph,
+static hipError_t launch_sweep2(LR<L, R>, const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
                                 const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
   const SweepParams<L, R> p = make_params<L, R>(g, ph, a, y0, z0);
+  const SweepVariant v = per_node_variant_of(sel, g, ph, prop);
+  if (block_x > sweep_max_threads(v)) block_x = sweep_max_threads(v);      // the instantiation's launch bound
   dim3 block(block_x, 1, 1);
   dim3 grid((g.lat_nx - 2 + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
   if (grid.y == 0 || grid.z == 0) return hipSuccess;
   if (ph.accel_field && !a.accf) return hipErrorInvalidValue;      // (slf_kernel_launch refuses first, with a message)
-  if (model != 0 && model != 2) model = 1;
-  // BGK only (checked at module creation): --minimize_roundoff; --regularized / --subgrid=les-smagorinsky
-  const bool roundoff = model == 0 && ph.incompressible == SLF_DENSITY_ROUNDOFF;
-  const bool turb = model == 0 && !roundoff && (ph.regularized || ph.subgrid);
-  if ((turb || model == 2 || ph.accel_field) && block.x > 512) {      // these instantiations: at most 512 threads per workgroup (launch bounds)
-    block.x = 512;
-    grid.x = (g.lat_nx - 2 + 511) / 512;
-  }
-  if (!roundoff && !turb && model != 2 && g.indirect && p.slot_gi) {       // one thread per slot (slot_sweep_kernel)
+  if (!v.roundoff && !v.turb && v.model != 2 && g.indirect && p.slot_gi) {       // one thread per slot (slot_sweep_kernel)
     SweepParams<L, R> q = p;
     q.y1 = y1;
     q.z1 = (L::dim == 3) ? z1 : 1;
-    return launch_slot_sweep<L, R>(model, prop, g.bc_level, q, s);      // slf_slots.hip
+    return launch_slot_sweep<L, R>(v.model, prop, g.bc_level, q, s);      // slf_slots.hip
   }
-  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a combination that does not exist
-  pick<int, 0, 1, 2>(model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
-    pick_bool(general || g.indirect, [&](auto G) { pick_bool(g.indirect, [&](auto IND) {
-      pick_bool(roundoff, [&](auto ROUNDOFF) { pick_bool(turb, [&](auto TURB) { pick_bool(ph.tms_mask != 0, [&](auto TMS) {
-      pick_bool(ph.accel_field != 0, [&](auto ACCF) { pick_bool(ph.equilibrium == SLF_EQ_SHALLOW_WATER, [&](auto SW) {
-        // indirect addressing: the node map is always read; --minimize_roundoff and --regularized / --subgrid exclude
-        // each other here (the round-off form comes first) and are BGK only; --model=elbm (2): per-node kernels only;
-        // Tamm-Mott-Smith walls are node types: no such instantiation without the node map; an acceleration field:
-        // BGK / MRT with direct addressing and none of the three (refused at module creation otherwise, slf_bind.h); the
-        // shallow-water equilibrium: D2Q9, BGK, direct addressing, none of the three, with or without the field
-        if constexpr ((IND && !G) || (ROUNDOFF && TURB) || ((ROUNDOFF || TURB) && MODEL != 0) || (TMS && !G) ||
-                      (ACCF && (ROUNDOFF || TURB || TMS || IND || MODEL == 2)) ||
-                      (SW && (L::id != D2Q9::id || MODEL != 0 || ROUNDOFF || TURB || TMS || IND))) return;
+  hipError_t e = hipErrorInvalidValue;      // stays if the run-time values name a variant that does not exist
+  pick<int, 0, 1, 2>(v.model, [&](auto MODEL) { pick_prop(prop, [&](auto P) {
+    pick_bool(v.general, [&](auto G) { pick_bool(v.indirect, [&](auto IND) {
+      pick_bool(v.roundoff, [&](auto ROUNDOFF) { pick_bool(v.turb, [&](auto TURB) { pick_bool(v.tms, [&](auto TMS) {
+      pick_bool(v.accf, [&](auto ACCF) { pick_bool(v.sw, [&](auto SW) {
+        constexpr SweepVariant V{.model = MODEL, .prop = P, .general = G, .indirect = IND, .roundoff = ROUNDOFF, .turb = TURB,
+                                 .tms = TMS, .accf = ACCF, .sw = SW};
+        if constexpr (!per_node_variant_exists(L::id, V)) return;
         else {
-          hipLaunchKernelGGL((sweep_kernel<L, R, MODEL, P, G, IND, ROUNDOFF, TURB, TMS, ACCF, SW>), grid, block, 0, s, p);
+          hipLaunchKernelGGL((sweep_kernel<L, R, V>), grid, block, 0, s, p);
           e = hipGetLastError();
         }
       }); });
@@ -268,7 +240,7 @@ hipError_t launch_sweep(const KernelSelector& sel, Prop prop, const Geometry& g,
     if (launch_sweep_row(sel, prop, g, ph, a, y0, y1, z0, z1, s, &fe)) return fe;
   }
   return pick_lr(sel, [&](auto lr) {
-    return launch_sweep2(lr, sel.model, prop, sel.general, g, ph, a, y0, y1, z0, z1, block_x, s);
+    return launch_sweep2(lr, sel, prop, g, ph, a, y0, y1, z0, z1, block_x, s);
   });
 }
 

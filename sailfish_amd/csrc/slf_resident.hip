@@ -57,7 +57,7 @@ __device__ __forceinline__ bool resident_coord(int c, int lat, int wrap, int& ou
 
 // per window node, decided once when the window is loaded
 constexpr uint32_t RI_ACTIVE = 1u;     // a node the sweep works on (real, not excluded by its node code)
-constexpr uint32_t RI_SIMPLE = 2u;     // ... whose code is the plain one: fluid or full-way bounce-back (node_update<BCL = 0>)
+constexpr uint32_t RI_SIMPLE = 2u;     // ... whose code is the plain one: fluid or full-way bounce-back (node_update with V.bcl = 0)
 constexpr uint32_t RI_TILE = 4u;       // node of the tile (the on-GPU invalid-value check looks at these only)
 constexpr uint32_t RI_WALL = 8u;       // a plain node that is a full-way bounce-back node
 constexpr int RI_DIST_SHIFT = 8;       // bits 8..: distance from the tile (0 inside it)
@@ -174,8 +174,8 @@ __global__ void __launch_bounds__(1024) resident_kernel(const ResidentParams<L, 
     }
     R rho, v[3];
     bool wet = true;
-    node_update<L, R, MODEL, PROP_AA_ODD, GENERAL, false, FORCE_RUNTIME, decltype(BCL)::value>(p, f, code, kind, 0u, none, none, none,
-                                                                                           rho, v, wet);
+    node_update<L, R, SweepVariant{.model = MODEL, .prop = PROP_AA_ODD, .general = GENERAL, .bcl = decltype(BCL)::value}>(
+        p, f, code, kind, 0u, none, none, none, rho, v, wet);
     if (wet && (p.options & OPTION_CHECK_INVALID) && (flags & RI_TILE)) {
       int gx, gy;
       resident_coord(tx0 - rp.halo + n % WW, g.lat_nx, g.wrap[0], gx);

@@ -154,7 +154,8 @@ __global__ void __launch_bounds__(1024, (row_min_waves<R, MODEL, GENERAL, FORCE,
   R rho, v[3];
   bool wet = true;
   if (active) {
-    node_update<L, R, MODEL, PROP, GENERAL, false, FORCE, BCL>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet);
+    node_update<L, R, SweepVariant{.model = MODEL, .prop = PROP, .general = GENERAL, .force = FORCE, .bcl = BCL}>(
+        p, f, code, kind, gi, ox, oy, oz, rho, v, wet);
     if (wet) check_invalid<R>(p.status, p.options, rho, x, gy, gz);
     if ((p.options & 1u) && wet) {
       p.rho[gi] = rho;
@@ -208,7 +209,8 @@ __global__ void __launch_bounds__(1024, (BCL == 0 ? row_min_waves<R, MODEL, GENE
   x_face_receive<L, R, false>(p, f, gx, g.lat_nx - 2, fr);
   R rho, v[3];
   bool wet = true;
-  node_update<L, R, MODEL, PROP_AA_EVEN, GENERAL, false, FORCE, BCL>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet);
+  node_update<L, R, SweepVariant{.model = MODEL, .prop = PROP_AA_EVEN, .general = GENERAL, .force = FORCE, .bcl = BCL}>(
+      p, f, code, kind, gi, ox, oy, oz, rho, v, wet);
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   if ((p.options & 1u) && wet) {
     p.rho[gi] = rho;

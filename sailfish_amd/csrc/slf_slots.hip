@@ -16,13 +16,13 @@ namespace slf {
 // of every wave idle and the active ones' accesses a third of a line (6.5 GMLUPS; profiles/r06/configs_indirect.jsonl).
 // The x-streaming steps translate every neighbour ONCE: node x - e_i (the pull) is node x + e_opp(i) (the push), so the
 // 18 entries of the dense table serve both; consecutive active nodes of a row have consecutive slots, so the gathers
-// through them are as good as dense.  Same node code (node_update<..., INDIRECT>), same results.
+// through them are as good as dense.  Same node code (node_update with V.indirect), same results.
 // BCL: the module's boundary-condition level (Geometry::bc_level, as the whole-row kernels): a porous medium or a pipe of
 // bounce-back walls is level 0 and carries none of the outflow / slip / do-nothing code, whose merged populations the
 // level-2 instantiation of the two-copy step keeps in 32 bytes of scratch per lane at its 128 VGPRs.
 // Double precision D3Q19: two waves per SIMD, i.e. 256 VGPRs -- at the 128 of four waves every instantiation kept 100-330
 // bytes per lane in scratch, more than the 304 bytes of populations a node moves.
-// TMS: the instantiation for modules with Tamm-Mott-Smith wall nodes (node_update<..., TMS>), at level 2 only.
+// TMS: the instantiation for modules with Tamm-Mott-Smith wall nodes (node_update with V.tms), at level 2 only.
 template <class L, class R, int MODEL, int PROP, int BCL = 2, bool TMS = false>
 __global__ void __launch_bounds__(256, (sizeof(R) == 8 && L::Q > 9) ? 2 : 4) slot_sweep_kernel(const SweepParams<L, R> p) {
   const Geometry& g = p.g;
@@ -59,7 +59,8 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 && L::Q > 9) ? 2 : 4) slo
   });
   R rho, v[3];
   bool wet = true;
-  node_update<L, R, MODEL, PROP, true, true, FORCE_RUNTIME, BCL, false, false, TMS>(p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
+  node_update<L, R, SweepVariant{.model = MODEL, .prop = PROP, .general = true, .indirect = true, .bcl = BCL, .tms = TMS}>(
+      p, f, code, kind, gi, ox, oy, oz, rho, v, wet, si);
   if (wet) check_invalid<R>(p.status, p.options, rho, gx, gy, gz);
   if ((p.options & 1u) && wet) {
     p.rho[gi] = rho;

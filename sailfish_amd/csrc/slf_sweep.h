@@ -4,6 +4,7 @@
 #pragma once
 #include "slf_kernels.h"
 #include "slf_node.h"
+#include "slf_variant.h"
 
 namespace slf {
 
@@ -382,39 +383,20 @@ __device__ __forceinline__ void tms_fix_missing(const Geometry& g, R (&f)[L::Q],
   });
 }
 
-// gi: dense node index; si: the node's slot in the distribution arrays (= gi unless INDIRECT).
-// MODEL: 0 BGK, 1 MRT, 2 entropic (slf_node.h elbm_relax; the per-node kernels only).
-// BCL: the module's Geometry::bc_level the instantiation is for (2 = everything; the outflow, do-nothing and full-slip nodes
-// exist at level 2 only, so that the level-1 kernels of the usual wall / inlet / outlet conditions do not carry their code).
-// ROUNDOFF: the --minimize_roundoff formulation (slf_node.h: macro_roundoff, bgk_relax_roundoff): BGK; fluid, full-way
-// and half-way bounce-back nodes (the module is refused otherwise); the per-node kernels only.
-// TURB: the BGK collision with the options of the reference's relaxation preamble (--regularized, --subgrid; which of
-// the two: SweepParams::turb_flags) -- slf_node.h bgk_relax_turb; the per-node kernels only, MODEL = BGK.
-// TMS: the module has Tamm-Mott-Smith wall nodes (SweepParams::tms_mask != 0): half-way bounce-back types with the flag run
-// tms_fix_missing before and tms_add_equilibrium_difference after the collision; the target state stays live across it.
-// The per-node kernels and the slot sweep only; instantiations of their own, so that the others do not carry the registers.
-// ACCF: the module has an acceleration field (slf_module_desc::accel_field): the collision takes the node's acceleration
-// from `acc` (the caller formed cp.accel + field[gi]) instead of cp.accel.  The per-node kernels only; MODEL = BGK or MRT,
-// none of INDIRECT, ROUNDOFF, TURB, TMS; `acc` is not read otherwise.
-// SW: a shallow-water module (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER): the BGK relaxation uses sw_equilibrium
-// (slf_node.h) with p.cp.gravity -- and that is all: moments, bounce-back, the half-way store, the slip reflection and
-// streaming are the code of every other module.  The per-node kernels only; D2Q9, MODEL = BGK, with or without ACCF, none
-// of INDIRECT, ROUNDOFF, TURB, TMS; the value-carrying node kinds are refused at module creation (slf_bind.h sw_refusal).
-template <class L, class R, int MODEL, int PROP, bool GENERAL, bool INDIRECT = false, int FORCE = FORCE_RUNTIME, int BCL = 2,
-          bool ROUNDOFF = false, bool TURB = false, bool TMS = false, bool ACCF = false, bool SW = false>
+// gi: dense node index; si: the node's slot in the distribution arrays (= gi unless V.indirect).
+// V: the compile-time switches, one field each (SweepVariant, slf_variant.h); callers name the fields they set.
+template <class L, class R, SweepVariant V>
 __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L::Q], uint32_t code, int kind,
                                             uint32_t gi, const AxisOff& ox, const AxisOff& oy, const AxisOff& oz,
                                             R& rho, R (&v)[3], bool& wet, uint32_t si = INVALID_NODE,
                                             const R (*acc)[3] = nullptr) {
-  static_assert(!ACCF || ((MODEL == 0 || MODEL == 1) && !INDIRECT && !ROUNDOFF && !TURB && !TMS),
-                "ACCF: BGK / MRT, direct addressing, none of ROUNDOFF, TURB, TMS");
-  static_assert(!SW || (MODEL == 0 && !INDIRECT && !ROUNDOFF && !TURB && !TMS), "SW: BGK, direct addressing, none of ROUNDOFF, TURB, TMS");
-  if constexpr (!INDIRECT) si = gi;
+  static_assert(node_variant_ok(V), "a variant node_update is not written for: node_variant_conflict(V) names the rule");
+  if constexpr (!V.indirect) si = gi;
   const Geometry& g = p.g;
   const size_t ds = g.dist_size;
   (void)ds;
-  if constexpr (ROUNDOFF) {
-    wet = GENERAL ? kind_is_wet(kind) : true;
+  if constexpr (V.roundoff) {
+    wet = V.general ? kind_is_wet(kind) : true;
     // equilibrium density / velocity nodes (boundary.mako:425-459, 492-504 with config.minimize_roundoff: the sum of the
     // shifted populations is rho - 1; the imposed density enters as par_rho - 1; sym.py:573-682): the two boundary
     // conditions whose reference expressions are consistent under the option (the regularized / Zou-He nodes are not:
@@ -422,12 +404,12 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     bool bc = false;
     R tg_rho = (R)0, tg_v[3] = {(R)0, (R)0, (R)0};
     bool tms = false;
-    if constexpr (GENERAL && TMS) {
+    if constexpr (V.general && V.tms) {
       tms = kind == NK_HALF_BB && (((p.tms_mask >> (code & g.type_mask)) & 1u) != 0u);
       if (tms) tms_fix_missing<L, R, true>(g, f, (int)(code >> g.orient_shift), false, tg_rho, tg_v);
     }
     (void)tg_rho; (void)tg_v; (void)tms;
-    if constexpr (GENERAL) {
+    if constexpr (V.general) {
       const int orientation = (int)(code >> g.orient_shift);
       if ((kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY) && orientation != 0) {
         const int pidx = (int)((code >> g.param_shift) & g.param_mask);
@@ -458,32 +440,32 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
       }
     }
     if (!bc) macro_roundoff<L, R>(f, rho, v);
-    if (GENERAL && (kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY)) {
+    if (V.general && (kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY)) {
       set_equilibrium<L, R>(f, rho, rho + (R)1, v);          // boundary.mako:797-809 with rho0 = rho + 1
     }
-    if (GENERAL && kind == NK_FULL_BB) bounce_back<L, R>(f);
+    if (V.general && kind == NK_FULL_BB) bounce_back<L, R>(f);
     if (wet && p.relaxation_enabled)
       bgk_relax_roundoff<L, R>(f, rho, v, p.cp.omega, p.cp.guo_pref, p.cp.has_force != 0, p.cp.accel, p.cp.force_edm != 0);
-    if (GENERAL && kind == NK_HALF_BB) {
+    if (V.general && kind == NK_HALF_BB) {
       const int orientation = (int)(code >> g.orient_shift);
-      if constexpr (TMS) {
+      if constexpr (V.tms) {
         if (tms) tms_add_equilibrium_difference<L, R>(f, tg_rho, tg_rho + (R)1, tg_v, rho, rho + (R)1, v);
       }
-      half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
+      half_bb_store<L, R, V.prop, V.indirect>(p, f, orientation, gi, si, ox, oy, oz);
     }
     return;
   }
-  if constexpr (GENERAL && BCL == 0) {
+  if constexpr (V.general && V.bcl == 0) {
     wet = kind_is_wet(kind);
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (kind == NK_FULL_BB) bounce_back<L, R>(f);
     if (wet && p.relaxation_enabled) {
-      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
-      else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
-      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
-      else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
+      if constexpr (V.accf && V.model == 0) bgk_relax<L, R, V.sw>(f, rho, v, p.cp, *acc);
+      else if constexpr (V.accf) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
+      else if constexpr (V.model == 0) bgk_relax<L, R, V.force, V.sw>(f, rho, v, p.cp);
+      else mrt_relax<L, R, V.force>(f, v, p.cp, false);
     }
-  } else if constexpr (GENERAL && SW) {
+  } else if constexpr (V.general && V.sw) {
     // The node kinds a shallow-water module can have (slf_bind.h sw_refusal): fluid, full-way and half-way bounce-back,
     // slip -- the same functions in the same order as below, without the code of the kinds that carry a density or a
     // velocity (the outflow nodes' reads of the input array cost the two-copy instantiations 32 bytes of scratch per lane).
@@ -493,32 +475,32 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     if (kind == NK_FULL_BB) bounce_back<L, R>(f);
     if (kind == NK_SLIP) slip_reflect<L, R>(f, orientation);
     if (wet && p.relaxation_enabled) {
-      if constexpr (ACCF) bgk_relax<L, R, true>(f, rho, v, p.cp, *acc);
-      else bgk_relax<L, R, FORCE, true>(f, rho, v, p.cp);
+      if constexpr (V.accf) bgk_relax<L, R, true>(f, rho, v, p.cp, *acc);
+      else bgk_relax<L, R, V.force, true>(f, rho, v, p.cp);
     }
-    if (kind == NK_HALF_BB) half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
-  } else if constexpr (GENERAL) {
+    if (kind == NK_HALF_BB) half_bb_store<L, R, V.prop, V.indirect>(p, f, orientation, gi, si, ox, oy, oz);
+  } else if constexpr (V.general) {
     wet = kind_is_wet(kind);
     const int orientation = (int)(code >> g.orient_shift);
     const int pidx =(int)((code >> g.param_shift) & g.param_mask);
     const bool inc = p.cp.incompressible != 0;
     R tg_rho = (R)0, tg_v[3] = {(R)0, (R)0, (R)0};
     bool tms = false;
-    if constexpr (TMS) {
+    if constexpr (V.tms) {
       tms = kind == NK_HALF_BB && (((p.tms_mask >> (code & g.type_mask)) & 1u) != 0u);
       if (tms) tms_fix_missing<L, R, false>(g, f, orientation, inc, tg_rho, tg_v);
     }
     (void)tg_rho; (void)tg_v; (void)tms;
     // ---- fixMissingDistributions (boundary.mako:509-603): outflow nodes fill their unknown populations from
     // the incoming state of the nodes one / two steps along the inward normal (two-copy pattern only)
-    if constexpr (PROP == PROP_AB && BCL == 2) {
+    if constexpr (V.prop == PROP_AB && V.bcl == 2) {
       if ((kind == NK_COPY || kind == NK_YU_OUTFLOW) && orientation != 0) {
         with_orientation<L>(orientation, [&](auto O) {
           constexpr int n = L::dir2vecidx(O);
           const int off1 = dir_offset<L, n>(ox, oy, oz, true);
           const int off2 = 2 * (L::ex(n) + L::ey(n) * g.arr_nx + L::ez(n) * g.arr_nxy);
           uint32_t s1 = (uint32_t)((int)gi + off1), s2 = (uint32_t)((int)gi + off2);
-          if constexpr (INDIRECT) {
+          if constexpr (V.indirect) {
             s1 = p.nodes[s1];
             s2 = p.nodes[s2];
           }
@@ -526,9 +508,9 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
             if constexpr (is_missing<L, I, O>()) {
               const R* d = p.din + ds * (size_t)I;
               if (kind == NK_COPY) {
-                if (!INDIRECT || s1 != INVALID_NODE) f[I] = d[s1];
+                if (!V.indirect || s1 != INVALID_NODE) f[I] = d[s1];
               } else {
-                if (!INDIRECT || (s1 != INVALID_NODE && s2 != INVALID_NODE)) f[I] = (R)2 * d[s1] - d[s2];
+                if (!V.indirect || (s1 != INVALID_NODE && s2 != INVALID_NODE)) f[I] = (R)2 * d[s1] - d[s2];
               }
             }
           });
@@ -573,19 +555,19 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
         with_orientation<L>(orientation, [&](auto O) { zouhe_bb<L, R, O>(f, rho, rho0, v); });
       }
     }
-    if constexpr (BCL == 2) {
+    if constexpr (V.bcl == 2) {
       if (kind == NK_SLIP) slip_reflect<L, R>(f, orientation);   // boundary.mako:837-855
     }
     // NTDoNothing, in-place pattern (boundary.mako:862-876): the unknown populations keep their value -- the node stores
     // what it has just read to where its NEXT step reads it: an odd step (the next one reads the node's own slots) into its
     // own slot, an even step (the next one pulls from the neighbours' opposite slots) into the opposite slot of the node
     // the population would have come from -- the ghost node behind the boundary.  Nobody else touches either slot.
-    if constexpr (PROP != PROP_AB && !INDIRECT && BCL == 2) {
+    if constexpr (V.prop != PROP_AB && !V.indirect && V.bcl == 2) {
       if (kind == NK_DO_NOTHING) {
         with_orientation<L>(orientation, [&](auto O) {
           static_for<1, L::Q>([&](auto I) {
             if constexpr (is_missing<L, I, O>()) {
-              if constexpr (PROP == PROP_AA_ODD) {
+              if constexpr (V.prop == PROP_AA_ODD) {
                 (p.dout + ds * (size_t)I)[si] = f[I];
               } else {
                 constexpr int J = L::opp(I);
@@ -599,37 +581,37 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
     }
     // ---- collision (relaxate, relaxation.mako:196-202: wet nodes only)
     if (wet && p.relaxation_enabled) {
-      if constexpr (ACCF && MODEL == 0) {
-        bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
-      } else if constexpr (ACCF) {
+      if constexpr (V.accf && V.model == 0) {
+        bgk_relax<L, R, V.sw>(f, rho, v, p.cp, *acc);
+      } else if constexpr (V.accf) {
         mrt_relax<L, R, 1>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY, *acc);
-      } else if constexpr (MODEL == 2) {
+      } else if constexpr (V.model == 2) {
         elbm_collide<L, R>(p, f, rho, v, gi);
-      } else if constexpr (MODEL == 0 && TURB) {
+      } else if constexpr (V.model == 0 && V.turb) {
         bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
-      } else if constexpr (MODEL == 0) {
-        bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
+      } else if constexpr (V.model == 0) {
+        bgk_relax<L, R, V.force, V.sw>(f, rho, v, p.cp);
       } else {
-        mrt_relax<L, R, FORCE>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY);
+        mrt_relax<L, R, V.force>(f, v, p.cp, kind == NK_EQUILIBRIUM_DENSITY || kind == NK_EQUILIBRIUM_VELOCITY);
       }
     }
     // ---- post-collision: half-way bounce-back (boundary.mako:653-683)
     // ... and the Tamm-Mott-Smith wall, which ends with the same store (boundary.mako:696-723)
     if (kind == NK_HALF_BB) {
-      if constexpr (TMS) {
+      if constexpr (V.tms) {
         if (tms) tms_add_equilibrium_difference<L, R>(f, tg_rho, inc ? (R)1 : tg_rho, tg_v, rho, inc ? (R)1 : rho, v);
       }
-      half_bb_store<L, R, PROP, INDIRECT>(p, f, orientation, gi, si, ox, oy, oz);
+      half_bb_store<L, R, V.prop, V.indirect>(p, f, orientation, gi, si, ox, oy, oz);
     }
   } else {
     macro_standard<L, R>(f, p.cp.incompressible != 0, rho, v);
     if (p.relaxation_enabled) {
-      if constexpr (ACCF && MODEL == 0) bgk_relax<L, R, SW>(f, rho, v, p.cp, *acc);
-      else if constexpr (ACCF) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
-      else if constexpr (MODEL == 2) elbm_collide<L, R>(p, f, rho, v, gi);
-      else if constexpr (MODEL == 0 && TURB) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
-      else if constexpr (MODEL == 0) bgk_relax<L, R, FORCE, SW>(f, rho, v, p.cp);
-      else mrt_relax<L, R, FORCE>(f, v, p.cp, false);
+      if constexpr (V.accf && V.model == 0) bgk_relax<L, R, V.sw>(f, rho, v, p.cp, *acc);
+      else if constexpr (V.accf) mrt_relax<L, R, 1>(f, v, p.cp, false, *acc);
+      else if constexpr (V.model == 2) elbm_collide<L, R>(p, f, rho, v, gi);
+      else if constexpr (V.model == 0 && V.turb) bgk_relax_turb<L, R>(f, rho, v, p.cp, p.turb_flags, p.turb_visc, p.turb_c2x36);
+      else if constexpr (V.model == 0) bgk_relax<L, R, V.force, V.sw>(f, rho, v, p.cp);
+      else mrt_relax<L, R, V.force>(f, v, p.cp, false);
     }
   }
 

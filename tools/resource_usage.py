@@ -24,4 +24,5 @@ if __name__ == '__main__':
     for r in rows:
         name = re.sub(r'slf::|\(slf::[^)]*\)|void ', '', r[0])
         if all(f in name for f in sys.argv[2:]):
-            print('%-100s vgpr %3s agpr %2s scratch %3s occ %s sgpr %3s lds %s' % ((name[:100],) + r[1:]))
+            # whole names: a SweepVariant template argument spells out its eleven fields, and variants differ in the last ones
+            print('%-100s vgpr %3s agpr %2s scratch %3s occ %s sgpr %3s lds %s' % ((name,) + r[1:]))
