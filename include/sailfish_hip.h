@@ -682,6 +682,42 @@ int slf_ibm_gather(slf_module* m, int n_markers, const int32_t origin[3], const 
 int slf_ibm_clear_and_advect(slf_module* m, int n_markers, const int32_t origin[3], void* pos, void* acc, const void* map,
                              const void* vx, const void* vy, const void* vz, uint32_t* outside, slf_stream* stream);
 
+/* ---- thermal flows: a temperature lattice beside the sweep (no counterpart in the reference; kernels:
+ *      slf_thermal.hip).  Entry points, not slf_kernel_get names.  The flow module is an ordinary accel_field = 1 module on
+ *      D2Q9 or D3Q19; the temperature lives on D2Q5 / D3Q7 (directions 0 rest, 1 +x, 2 -x, 3 +y, 4 -y, 5 +z, 6 -z; weights
+ *      1/3, 1/6 with k = 3 / 1/4, 1/8 with k = 4) in two arrays g[copy][i][node] the caller owns, each 2 dim + 1 direction
+ *      arrays with the layout and padding of rho, arr_nz * arr_ny * arr_nx elements apart, in the module's precision R.  A
+ *      node's slot holds its own post-collision values.
+ *        slf_thermal_init  at every wet node: g0[i] = geq_i(T, v), field[d] = b[d] * (T - T_ref)
+ *        slf_thermal_step  at every wet node x: pull g_i = g_src[i][x - e_i] (wrapped on the axes with periodic[d] != 0);
+ *                          from a real node that is not wet: Tw = wall_temperature[x - e_i], finite: g_i = (2 w_i) Tw -
+ *                          g_src[opp i][x] (a fixed temperature at the link mid-point), otherwise (NaN): g_i =
+ *                          g_src[opp i][x] (adiabatic); from beyond the real nodes on an axis that is not periodic: g_i =
+ *                          g_src[opp i][x].  T = ((g0 + g1) + g2) + ...; with a map and a finite wall_temperature[x] at the
+ *                          wet node itself: T = that value and g_i = geq_i.  geq_i = (w_i T) (1 + k e_i.v) with v as the
+ *                          sweep has just stored it; g_dst[i][x] = g_i + omega_T (geq_i - g_i); T[x] = T; field[d][x] =
+ *                          b[d] * (T - T_ref)
+ *      `field` is the buffer handed to slf_module_set_accel_field: the NEXT CollideAndPropagate reads it, so a step is the
+ *      module's CollideAndPropagate with macroscopic output (option bit 0), then slf_thermal_step, and the buoyancy lags the
+ *      temperature by one step.  Wet is what the sweep calls wet (node kinds by the module's type table); map may be NULL for
+ *      a fluid-only module, where every node is wet and wall_temperature[x] at the node itself is not read.  Nodes that are
+ *      not wet are never written.  omega_T, T_ref and b are rounded once to R.  vz is not read in 2-D.  All pointers but
+ *      params are device pointers; everything is enqueued on `stream`.  SLF_ERR_INVALID: a NULL pointer, a module created
+ *      without accel_field or with no field set, map NULL where the module has node types, g_src == g_dst, omega_T outside
+ *      (0, 2) or a constant that is not finite; SLF_ERR_UNSUPPORTED: D3Q15 / D3Q27, non-LBM models, indirect addressing. ---- */
+typedef struct slf_thermal_params {
+  double omega_T;        /* 1 / tau_T; diffusivity (tau_T - 1/2) / k */
+  double T_ref;
+  double b[3];           /* buoyancy: thermal expansion x gravity, pointing against gravity; b[2] is ignored in 2-D */
+  int32_t periodic[3];   /* the subdomain's locally periodic axes: the pull wraps there */
+  int32_t reserved;      /* 0 */
+} slf_thermal_params;
+int slf_thermal_init(slf_module* m, const slf_thermal_params* params, const void* map, const void* T, const void* vx,
+                     const void* vy, const void* vz, void* g0, slf_stream* stream);
+int slf_thermal_step(slf_module* m, const slf_thermal_params* params, const void* map, const void* g_src, void* g_dst,
+                     const void* vx, const void* vy, const void* vz, const void* wall_temperature, void* T,
+                     slf_stream* stream);
+
 /* ---- step plans (extension): the launch list of ONE time step, built once, enqueued with one call.
  *      The reference enqueues every kernel, event and copy of a step from Python (SubdomainRunner.step(),
  *      subdomain_runner.py:960-974; the boundary / bulk overlap with its event chain, :1028-1058; _send_dists /

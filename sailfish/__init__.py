@@ -7,7 +7,7 @@ import sys
 import sailfish_amd
 
 _MODULES = ['sym', 'util', 'config', 'node_type', 'geo_encoder', 'subdomain_connection', 'subdomain', 'geo',
-            'io', 'lb_base', 'subdomain_runner', 'lb_single', 'lb_binary', 'lb_ternary', 'connector', 'controller', 'backend_hip', 'hipabi',
+            'io', 'lb_base', 'subdomain_runner', 'lb_single', 'lb_binary', 'lb_ternary', 'lb_thermal', 'connector', 'controller', 'backend_hip', 'hipabi',
             'stats']
 
 __version__ = sailfish_amd.__version__

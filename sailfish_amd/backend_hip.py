@@ -742,6 +742,36 @@ class HIPBackend(placement.VmmMixin):
                                                              P(gpu_v[2] if len(gpu_v) > 2 else None), P(outside),
                                                              stream.handle if stream else None), 'slf_ibm_clear_and_advect')
 
+    # -- thermal flows (C ABI slf_thermal_*; sailfish_amd/thermal.py) ---------------
+    supports_thermal = True
+
+    @staticmethod
+    def thermal_params(omega_t, t_ref, b, periodic):
+        """The constants of the temperature lattice as the calls below take them (built once, not per step)."""
+        p = hipabi.SlfThermalParams()
+        p.omega_T, p.T_ref = float(omega_t), float(t_ref)
+        for d in range(3):
+            p.b[d] = float(b[d]) if d < len(b) else 0.0
+            p.periodic[d] = int(bool(periodic[d])) if d < len(periodic) else 0
+        return p
+
+    def thermal_init(self, module, params, gpu_map, gpu_t, gpu_v, g0, stream=None):
+        """Enqueues: g0 = the equilibrium at (T, v) and the buoyancy of T into the module's acceleration field, at every
+        wet node (slf_thermal_init).  params: thermal_params(); gpu_map: 0 for a fluid-only module."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_thermal_init(module.handle, ctypes.byref(params), P(gpu_map or None),
+                                                     P(gpu_t), P(gpu_v[0]), P(gpu_v[1]), P(gpu_v[2] if len(gpu_v) > 2 else None),
+                                                     P(g0), stream.handle if stream else None), 'slf_thermal_init')
+
+    def thermal_step(self, module, params, gpu_map, g_src, g_dst, gpu_v, gpu_wall_t, gpu_t, stream=None):
+        """Enqueues: one step of the temperature lattice from copy g_src into copy g_dst, with the velocity the sweep has
+        just stored; T and the module's acceleration field are rewritten at every wet node (slf_thermal_step)."""
+        P = ctypes.c_void_p
+        _check(self._lib, self._lib.slf_thermal_step(module.handle, ctypes.byref(params), P(gpu_map or None),
+                                                     P(g_src), P(g_dst), P(gpu_v[0]), P(gpu_v[1]),
+                                                     P(gpu_v[2] if len(gpu_v) > 2 else None), P(gpu_wall_t), P(gpu_t),
+                                                     stream.handle if stream else None), 'slf_thermal_step')
+
     @staticmethod
     def supports_row_classes(desc):
         """Modules the row classes exist for: D3Q19 single-fluid with a node map, direct addressing."""

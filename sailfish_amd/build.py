@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'libsailfish_hip.so')
 SOURCES = ['slf_kernels.hip', 'slf_slots.hip', 'slf_fast.hip', 'slf_pair.hip', 'slf_row.hip', 'slf_sc.hip', 'slf_fe.hip', 'slf_sc3.hip', 'slf_lat.hip', 'slf_resident.hip', 'slf_stats.hip',
-           'slf_force.hip', 'slf_ibm.hip', 'slf_api.hip']
+           'slf_force.hip', 'slf_ibm.hip', 'slf_thermal.hip', 'slf_api.hip']
 HEADERS = ['slf_kernels.h', 'slf_variant.h', 'slf_bind.h', 'slf_lattice.h', 'slf_node.h', 'slf_sweep.h', 'slf_rowpush.h', 'slf_nn.h', 'slf_plain.h', 'slf_dispatch.h', 'slf_reduce.h', os.path.join('..', '..', 'include', 'sailfish_hip.h')]
 
 # -ffp-contract=off: fixed IEEE operation order (DESIGN.md "arithmetic contract");

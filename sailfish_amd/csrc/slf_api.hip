@@ -1344,6 +1344,49 @@ int slf_ibm_clear_and_advect(slf_module* m, int n_markers, const int32_t origin[
   return SLF_OK;
 }
 
+// ---- thermal flows (slf_thermal.hip; argument checks: slf_bind.h thermal_check) -----------------------------------
+static int check_thermal_call(const slf_module* m, const char* what, const slf_thermal_params* params, const void* map,
+                              const void* const* ptrs, const char* const* names, int n_ptrs, const void* src, const void* dst) {
+  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
+  std::string why;
+  if (int rc = slf::thermal_check(*m, m->accf != nullptr, what, params, map, ptrs, names, n_ptrs, src, dst, &why))
+    return fail(rc, why);
+  return SLF_OK;
+}
+
+static slf::ThermalConstants thermal_constants(const slf_thermal_params* p) {
+  slf::ThermalConstants k{};
+  k.omega = p->omega_T, k.t_ref = p->T_ref;
+  for (int d = 0; d < 3; d++) k.b[d] = p->b[d], k.periodic[d] = p->periodic[d] != 0;
+  return k;
+}
+
+int slf_thermal_init(slf_module* m, const slf_thermal_params* params, const void* map, const void* T, const void* vx,
+                     const void* vy, const void* vz, void* g0, slf_stream* stream) {
+  const void* ptrs[] = {T, vx, vy, g0, vz};
+  const char* names[] = {"T", "vx", "vy", "g0", "vz"};
+  if (int e = check_thermal_call(m, "slf_thermal_init", params, map, ptrs, names, m && m->geo.dim == 3 ? 5 : 4, nullptr, nullptr))
+    return e;
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  const void* v[3] = {vx, vy, vz};
+  SLF_HIP(slf::launch_thermal_init(m->sel, m->geo, thermal_constants(params), map, T, v, g0, m->accf, native(stream)));
+  return SLF_OK;
+}
+
+int slf_thermal_step(slf_module* m, const slf_thermal_params* params, const void* map, const void* g_src, void* g_dst,
+                     const void* vx, const void* vy, const void* vz, const void* wall_temperature, void* T,
+                     slf_stream* stream) {
+  const void* ptrs[] = {g_src, g_dst, vx, vy, wall_temperature, T, vz};
+  const char* names[] = {"g_src", "g_dst", "vx", "vy", "wall_temperature", "T", "vz"};
+  if (int e = check_thermal_call(m, "slf_thermal_step", params, map, ptrs, names, m && m->geo.dim == 3 ? 7 : 6, g_src, g_dst))
+    return e;
+  SLF_HIP(hipSetDevice(m->ctx->device));
+  const void* v[3] = {vx, vy, vz};
+  SLF_HIP(slf::launch_thermal_step(m->sel, m->geo, thermal_constants(params), map, g_src, g_dst, v, wall_temperature, T, m->accf,
+                                   native(stream)));
+  return SLF_OK;
+}
+
 int slf_kernel_get(slf_module* m, const char* name, slf_kernel** out) {
   if (!m || !name || !out) return fail(SLF_ERR_INVALID, "NULL argument");
   const slf::KernelRow* row = nullptr;

@@ -825,4 +825,42 @@ inline int ibm_check(const ModuleConfig& c, bool has_field, const char* what, in
   return SLF_OK;
 }
 
+// ---- (e) thermal flows (slf_thermal_*; kernels: slf_thermal.hip) ----------------------------------------------------------
+// The arguments of one slf_thermal_* call.  `what`: the entry point's name, for the message.  has_field: the module holds an
+// acceleration field (slf_module_set_accel_field was called).  map: the node map argument.  ptrs / names: the pointers that
+// must not be NULL.  src / dst: the two copies of the temperature lattice (NULL / NULL where the call takes one: init).
+inline int thermal_check(const ModuleConfig& c, bool has_field, const char* what, const slf_thermal_params* params, const void* map,
+                         const void* const* ptrs, const char* const* names, int n_ptrs, const void* src, const void* dst,
+                         std::string* err) {
+  const std::string w = std::string(what) + ": ";
+  if (c.sel.lattice != SLF_D2Q9 && c.sel.lattice != SLF_D3Q19)
+    return refuse(err, SLF_ERR_UNSUPPORTED, w + "D2Q9 and D3Q19 modules only (D3Q15 / D3Q27 have no acceleration field)");
+  if (!c.phys.accel_field)
+    return refuse(err, SLF_ERR_INVALID, w + "the module was created without an acceleration field (accel_field): the buoyancy "
+                                            "has nothing to be written into");
+  if (c.sc.enabled || c.fe.enabled || c.sc3.enabled || c.geo.indirect)
+    return refuse(err, SLF_ERR_UNSUPPORTED, w + "single-fluid modules with direct addressing only");
+  if (!has_field)
+    return refuse(err, SLF_ERR_INVALID, w + "no field is set (slf_module_set_accel_field): the kernels rewrite that buffer");
+  if (!params) return refuse(err, SLF_ERR_INVALID, w + "params is NULL");
+  if (!(params->omega_T > 0.0 && params->omega_T < 2.0))
+    return refuse(err, SLF_ERR_INVALID, w + "omega_T must lie in (0, 2): tau_T > 1/2, a positive diffusivity");
+  const double consts[4] = {params->T_ref, params->b[0], params->b[1], params->b[2]};
+  for (double x : consts) {
+    if (!(x - x == 0.0)) return refuse(err, SLF_ERR_INVALID, w + "T_ref and b must be finite");
+  }
+  if (!map && c.sel.general)
+    return refuse(err, SLF_ERR_INVALID, w + "map is NULL, but the module has node types (which nodes are wet is read off the "
+                                            "node map)");
+  for (int i = 0; i < n_ptrs; i++) {
+    if (!ptrs[i]) return refuse(err, SLF_ERR_INVALID, w + names[i] + " is NULL");
+  }
+  if (src && src == dst)
+    return refuse(err, SLF_ERR_INVALID, w + "g_src == g_dst: the temperature lattice is two-copy, a step reads one copy and "
+                                            "writes the other");
+  if (c.geo.lat_ny - 2 > 4 * 65535 || c.geo.lat_nz - 2 > 65535)
+    return refuse(err, SLF_ERR_UNSUPPORTED, w + "more than 262140 rows or 65535 layers (the launch grid runs over them)");
+  return SLF_OK;
+}
+
 }  // namespace slf

@@ -335,4 +335,17 @@ hipError_t launch_ibm_clear_and_advect(const KernelSelector& sel, const Geometry
                                        void* acc, void* field, const void* map, const void* const v[3], uint32_t* outside,
                                        hipStream_t s);
 
+// ---- thermal flows (slf_thermal.hip): the temperature lattice D2Q5 / D3Q7 beside a D2Q9 / D3Q19 module with an acceleration
+// field, one lane per node.  g arrays: [i][arr_nz][arr_ny][arr_nx] in the module's precision; map NULL: every node is wet.
+// Operation order: the head of slf_thermal.hip.
+struct ThermalConstants {
+  double omega, t_ref, b[3];   // rounded once to the module's precision by the launchers
+  int periodic[3];
+};
+hipError_t launch_thermal_init(const KernelSelector& sel, const Geometry& g, const ThermalConstants& k, const void* map,
+                               const void* t_field, const void* const v[3], void* g0, void* field, hipStream_t s);
+hipError_t launch_thermal_step(const KernelSelector& sel, const Geometry& g, const ThermalConstants& k, const void* map,
+                               const void* src, void* dst, const void* const v[3], const void* wall_t, void* t_field,
+                               void* field, hipStream_t s);
+
 }  // namespace slf

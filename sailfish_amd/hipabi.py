@@ -94,6 +94,12 @@ class SlfRegion(Structure):
     _fields_ = [('y0', c_int32), ('y1', c_int32), ('z0', c_int32), ('z1', c_int32)]
 
 
+class SlfThermalParams(Structure):
+    """slf_thermal_params: the constants of the temperature lattice (slf_thermal_init / slf_thermal_step)."""
+    _fields_ = [('omega_T', c_double), ('T_ref', c_double), ('b', c_double * 3), ('periodic', c_int32 * 3),
+                ('reserved', c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/sailfish_hip.h declares.
 SIGNATURES = {
     'slf_abi_version': (c_int, []),
@@ -201,6 +207,8 @@ SIGNATURES = {
     'slf_ibm_spread': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 5),
     'slf_ibm_gather': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 3),
     'slf_ibm_clear_and_advect': (c_int, [c_void_p, c_int, POINTER(c_int32)] + [c_void_p] * 8),
+    'slf_thermal_init': (c_int, [c_void_p, POINTER(SlfThermalParams)] + [c_void_p] * 7),
+    'slf_thermal_step': (c_int, [c_void_p, POINTER(SlfThermalParams)] + [c_void_p] * 9),
     'slf_last_error': (c_char_p, []),
 }
 

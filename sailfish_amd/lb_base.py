@@ -18,8 +18,11 @@ class LBMixIn(object):
 
 
 class Field(object):
-    def __init__(self, name, expr=None, need_nn=False, init=0.0, gpu_array=False):
+    def __init__(self, name, expr=None, need_nn=False, init=0.0, gpu_array=False, output=True):
+        """output=False: an input of the simulation, not a result -- on the device like any field, but not registered with the
+        output (neither saved, masked nor verified)."""
         self.name = name
+        self.output = output
         self.expr = expr
         self.init = init
         self.need_nn = need_nn
@@ -138,7 +141,7 @@ class LBSim(object):
                     setattr(self, field.name + axis, component)
                 self._vector_fields.append(FieldPair(field, host))
             elif isinstance(field, ScalarField):
-                host, _ = runner.make_scalar_field(name=field.name, async_=True)
+                host, _ = runner.make_scalar_field(name=field.name if field.output else None, async_=True)
                 host[:] = field.init
                 self._scalar_fields.append(FieldPair(field, host))
             else:

@@ -1577,3 +1577,77 @@ class IBMSubdomainRunner(SubdomainRunner):
         super(IBMSubdomainRunner, self).restore_checkpoint(fname)
         if self._markers is not None and self._sim.particle_positions is not None:
             self._markers.set_positions(self._sim.particle_positions)
+
+
+class ThermalSubdomainRunner(SubdomainRunner):
+    """Runner of lb_thermal.LBThermalFluidSim: allocates the zero acceleration field and the two copies of
+    the temperature lattice, puts the init launch behind the flow's SetInitialConditions and the thermal launch on the calc
+    stream behind every step's program (sailfish_amd/thermal.py).  They are direct entry points of the C ABI, which a step
+    plan has no entry for, so they go around StepPlans.run: the same calls on the same stream whether the program in front
+    of them is replayed from a plan or performed entry by entry.  The sweep always stores rho and v (the temperature
+    collides with the v of every step), and steps are never replayed as graphs."""
+    _thermal = None
+
+    def set_topology(self, all_specs, global_size, periodic):
+        if len(all_specs) > 1:
+            raise NotImplementedError('LBThermalFluidSim: more than one subdomain is not supported -- the temperature '
+                                      'populations would have to be exchanged across the seams (%d subdomains)' % len(all_specs))
+        super(ThermalSubdomainRunner, self).set_topology(all_specs, global_size, periodic)
+
+    def _init_accel_field(self, alloc):
+        super(ThermalSubdomainRunner, self)._init_accel_field(alloc)        # the zero field, handed to the module
+        from sailfish_amd import thermal
+        sim = self._sim
+        self._thermal = thermal.ThermalLattice(self.backend, self.module, self.float, self.dim, self._physical_size,
+                                               self._local_periodic(), sim.thermal_diffusivity, sim.t_ref, sim.buoyancy)
+
+    def _thermal_map(self):
+        return 0 if int(self._desc.fluid_only) else self.gpu_geo_map()
+
+    def _gpu_initial_conditions(self):
+        super(ThermalSubdomainRunner, self)._gpu_initial_conditions()
+        sim = self._sim
+        if int(self._desc.fluid_only) and np.isfinite(sim.wall_temperature).any():
+            raise ValueError('LBThermalFluidSim: wall_temperature is finite at %d nodes of a subdomain without walls or boundary '
+                             'nodes: its kernels run without the node map and never read a wet node\'s own entry, so the '
+                             'temperatures would be ignored' % int(np.isfinite(sim.wall_temperature).sum()))
+        self._thermal.init(self._thermal_map(), self.gpu_field(sim.T), self.gpu_field(sim.v), self._calc_stream)
+
+    def _sweep_kernels(self, it, sync_req):
+        kernels = self._kernels_full
+        return kernels.primary if (it & 1) == 0 else kernels.secondary
+
+    def step(self, sync_req=False):
+        sim = self._sim
+        it = sim.iteration
+        super(ThermalSubdomainRunner, self).step(True)
+        self._thermal.back(it, self._thermal_map(), self.gpu_field(sim.v), self.gpu_field(sim.wall_temperature),
+                           self.gpu_field(sim.T), self._calc_stream)
+
+    def fast_forward(self):
+        return 0
+
+    def thermal_populations(self, copy=None):
+        """Copy `copy` of the temperature populations (default: the one the next step reads), [Q] + the padded array shape."""
+        if copy is None:
+            copy = self._sim.iteration & 1
+        return self._thermal.populations(copy, self._calc_stream)
+
+    def release(self):
+        self._thermal = None            # (the device copies go with every buffer of the backend; this drops the host mirrors)
+        super(ThermalSubdomainRunner, self).release()
+
+    def save_checkpoint(self):
+        # what the next step reads and no prepare() can form again: the source copy of the populations and the field
+        self._sim.thermal_g = self.thermal_populations()
+        self.backend.from_buf(self._gpu_accel_field)
+        self._sim.thermal_field = np.array(self._host_accel_field)
+        super(ThermalSubdomainRunner, self).save_checkpoint()
+
+    def restore_checkpoint(self, fname):
+        super(ThermalSubdomainRunner, self).restore_checkpoint(fname)
+        sim = self._sim
+        if sim.thermal_g is not None:
+            self._thermal.set_populations(sim.iteration & 1, sim.thermal_g)
+            self._host_accel_field[...] = sim.thermal_field
+            self.backend.to_buf(self._gpu_accel_field)

@@ -143,7 +143,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
     ap.add_argument('--quick', action='store_true')
-    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place, 15a,15b acceleration field: four rolls mill 2048^2 / periodic box 256^3 with 15ac,15bc their constant-force baselines -- run those under SLF_VARIANT=0, 16a immersed boundary markers: ibm_cylinder 512x128 with 16ac the same channel without markers)')
+    ap.add_argument('--only', default='', help='comma separated configuration ids (0,1,2,2b,2c,5a,5b,3,3b,3g8,3x8,3z8,4; not in the default set: 6xa,6xb,6za,6zb, 7a-7d indirect addressing, 8a,8b single-component Shan-Chen, 9a,9b cylinder / sphere, 9c the sphere with a force object read every step, 4x4,8x4,5x3 x-slabs of one process, 10a,10b entropic collision with 10c its BGK baseline, 11a,11b flow statistics on the device, 12a,12b ternary Shan-Chen with three sweeps / the fused sweep, 13a-13d D3Q15 / D3Q27 periodic box two-copy / in-place, 14a,14b free-energy binary fluid two-copy / in-place, 15a,15b acceleration field: four rolls mill 2048^2 / periodic box 256^3 with 15ac,15bc their constant-force baselines -- run those under SLF_VARIANT=0, 16a immersed boundary markers: ibm_cylinder 512x128 with 16ac the same channel without markers, 17a thermal flow: heated layer 256^3 with 17ac the same box without the thermal launch)')
     args = ap.parse_args()
     if not args.only:
         # one fresh process per configuration: what a configuration measures must not depend on what ran before it in
@@ -367,6 +367,60 @@ def main():
             if '16ac' in only:
                 res.append(run('16ac: the same channel, no markers, ACCF full-output sweep (%s)' % pattern, NoMarkers,
                                LBGeometry2D, chan, 80, extra=per_step))
+    # config 17 (only with --only): thermal flows (lb_thermal.LBThermalFluidSim; csrc/slf_thermal.hip).
+    # 17a: D3Q19 + D3Q7, 256^3, single precision, periodic along x and y, full-way walls on the z faces held at T = 1 / 0,
+    # Ra = 1e5, Pr = 1 -- the ACCF full-output sweep and the thermal launch behind it, every step.  17ac: the same box as a
+    # plain module with a zero field through the same full-output kernels, no thermal launch: the like-for-like baseline.
+    # Bytes per update: 164 + 16 (the sweep, its field and its stored rho and v) and + 92 with the temperature lattice.
+    if only & {'17a', '17ac'}:
+        from sailfish.lb_thermal import LBThermalFluidSim
+        from sailfish.node_type import NTFullBBWall
+        from sailfish.subdomain_runner import SubdomainRunner, ThermalSubdomainRunner
+
+        class HeatedLayer(Subdomain3D):
+            def boundary_conditions(self, hx, hy, hz):
+                self.set_node((hz == 0) | (hz == self.gz - 1), NTFullBBWall)
+
+            def initial_conditions(self, sim, hx, hy, hz):
+                import numpy as np
+                H = float(self.gz - 2)
+                sim.rho[:] = 1.0
+                sim.T[:] = 1.0 - (hz - 0.5) / H + 1e-3 * np.sin(2 * np.pi * hx / self.gx) * np.sin(np.pi * (hz - 0.5) / H)
+                sim.wall_temperature[hz == 0] = 1.0
+                sim.wall_temperature[hz == self.gz - 1] = 0.0
+
+        class ThermalLayer(LBThermalFluidSim):
+            subdomain = HeatedLayer
+
+            def __init__(self, config):
+                super(ThermalLayer, self).__init__(config)
+                H = float(config.lat_nz - 2)
+                self.set_buoyancy((0.0, 0.0, 1e5 * config.visc * config.thermal_diffusivity / H ** 3), t_ref=0.5)
+
+        class SweepOnlyRunner(ThermalSubdomainRunner):
+            """The thermal runner without its lattice and launches: the field stays zero."""
+            _init_accel_field = SubdomainRunner._init_accel_field
+            _gpu_initial_conditions = SubdomainRunner._gpu_initial_conditions
+
+            def step(self, sync_req=False):
+                SubdomainRunner.step(self, True)
+
+        class SweepOnlyLayer(ThermalLayer):
+            subdomain_runner = SweepOnlyRunner
+
+        layer = dict(lat_nx=256, lat_ny=256, lat_nz=256, periodic_x=True, periodic_y=True, visc=0.03, thermal_diffusivity=0.03,
+                     precision='single', access_pattern='AB', grid='D3Q19', max_iters=int(3000 * it),
+                     benchmark_sample_from=int(1000 * it))
+        per_step = lambda ctrl: {'us_per_step': round(ctrl.runners[0].num_fluid_nodes / ctrl.mlups_total, 3)}       # noqa: E731
+        # (the timed events of a step are the sweep's: a rate "of the kernels" that leaves the thermal launch out means nothing)
+        wall_clock = lambda ctrl: dict(per_step(ctrl), MLUPS_comp=None, GBps_comp=None, frac_of_8TBps=None,       # noqa: E731
+                                       frac_is='not given: the step\'s timed events cover the sweep only')
+        if '17a' in only:
+            res.append(run('17a: D3Q19 + D3Q7 heated layer 256^3, Ra = 1e5 (AB)', ThermalLayer, LBGeometry3D, layer, 272,
+                           extra=wall_clock))
+        if '17ac' in only:
+            res.append(run('17ac: the same box, zero field, ACCF full-output sweep, no thermal launch (AB)', SweepOnlyLayer,
+                           LBGeometry3D, layer, 180, extra=per_step))
     # not BASELINE configurations (only with --only): an open duct, inlet + do-nothing outlet on the x faces / the z faces
     for cid, sim_cls, pattern, per in (('6xa', DuctSimX, 'AA', dict(periodic_z=True)), ('6xb', DuctSimX, 'AB', dict(periodic_z=True)),
                                        ('6za', DuctSimZ, 'AA', dict(periodic_x=True)), ('6zb', DuctSimZ, 'AB', dict(periodic_x=True))):
