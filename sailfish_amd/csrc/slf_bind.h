@@ -78,90 +78,126 @@ struct ModuleConfig {
   int n_node_params;
 };
 
-// D3Q15 and D3Q27 run the BGK sweep of slf_lat.hip and nothing else: what it does not implement is named here and refused,
-// whatever the other checks of module_config() would have said.  NULL: the descriptor is served (or is another lattice's).
 inline bool is_lat_lattice(int lattice) { return lattice == SLF_D3Q15 || lattice == SLF_D3Q27; }
-inline const char* lat_refusal(const slf_module_desc* d) {
-  if (!is_lat_lattice(d->lattice)) return nullptr;
-#define SLF_LAT_MSG(text) (d->lattice == SLF_D3Q15 ? "D3Q15: " text : "D3Q27: " text)
-  if (d->model == SLF_MRT) return SLF_LAT_MSG("--model=mrt is not implemented on this lattice; the BGK collision only");
-  if (d->model == SLF_ELBM) return SLF_LAT_MSG("--model=elbm is not implemented on this lattice; the BGK collision only");
-  if (d->model != SLF_BGK) return SLF_LAT_MSG("the BGK collision only");
-  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
-    return SLF_LAT_MSG("the Shan-Chen models are not implemented on this lattice; single-fluid modules only");
-  if (d->simtype == SLF_SIM_FREE_ENERGY) return SLF_LAT_MSG("the free-energy model is not implemented on this lattice; single-fluid modules only");
-  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return SLF_LAT_MSG("the ternary Shan-Chen model is not implemented on this lattice; single-fluid modules only");
-  if (d->simtype != SLF_SIM_LBM) return SLF_LAT_MSG("single-fluid modules only");
-  if (d->regularized) return SLF_LAT_MSG("--regularized is not implemented on this lattice");
-  if (d->subgrid) return SLF_LAT_MSG("--subgrid is not implemented on this lattice");
-  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return SLF_LAT_MSG("--minimize_roundoff is not implemented on this lattice");
-  if (d->entropic_equilibrium) return SLF_LAT_MSG("entropic_equilibrium belongs to --model=elbm, which is not implemented on this lattice");
-  if (d->node_addressing != SLF_ADDR_DIRECT) return SLF_LAT_MSG("--node_addressing=indirect is not implemented on this lattice; direct addressing only");
-  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
-    const int k = d->type_kind[i];
-    if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB ||
-          k == SLF_NK_HALF_BB))
-      return SLF_LAT_MSG("fluid, NTFullBBWall and NTHalfBBWall nodes only; the other node types are not implemented on this lattice");
-  }
-#undef SLF_LAT_MSG
-  return nullptr;
-}
 
-// An acceleration field (slf_module_desc::accel_field) is read by the ACCF instantiations of the per-node sweep and by
-// nothing else: what those do not cover is named here and refused.  NULL: no field, or the descriptor is served.
-inline const char* accf_refusal(const slf_module_desc* d) {
-  if (!d->accel_field) return nullptr;
-  if (d->accel_field != 1) return "accel_field must be 0 or 1";
-  if (d->lattice == SLF_D3Q15) return "accel_field: D3Q15 is not served (the sweep of D3Q15 / D3Q27 takes a constant acceleration); D2Q9 and D3Q19 only";
-  if (d->lattice == SLF_D3Q27) return "accel_field: D3Q27 is not served (the sweep of D3Q15 / D3Q27 takes a constant acceleration); D2Q9 and D3Q19 only";
-  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
-    return "accel_field: the Shan-Chen models are not served; single-fluid modules only";
-  if (d->simtype == SLF_SIM_FREE_ENERGY) return "accel_field: the free-energy model is not served; single-fluid modules only";
-  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return "accel_field: the ternary Shan-Chen model is not served; single-fluid modules only";
-  if (d->simtype != SLF_SIM_LBM) return "accel_field: single-fluid modules only";
-  if (d->model == SLF_ELBM) return "accel_field: --model=elbm is not served (the entropic collision takes no body force); BGK and MRT only";
-  if (d->regularized) return "accel_field: --regularized is not served";
-  if (d->subgrid) return "accel_field: --subgrid is not served";
-  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return "accel_field: --minimize_roundoff is not served";
-  if (d->node_addressing != SLF_ADDR_DIRECT) return "accel_field: --node_addressing=indirect is not served; direct addressing only";
-  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
-    if (d->type_kind[i] == SLF_NK_WALL_TMS) return "accel_field: NTWallTMS nodes are not served";
-  }
-  return nullptr;
-}
+// ---- what each feature is served with ------------------------------------------------------------------------------
+// A column is one field of the descriptor, with its values as the user knows them (`names`; NULL: not worth listing).
+enum Column { COL_LATTICE, COL_SIMTYPE, COL_MODEL, COL_ENTROPIC, COL_REGULARIZED, COL_SUBGRID, COL_DENSITY, COL_ADDRESSING,
+              COL_FORCE, COL_ACCEL_FIELD, COL_EDM, COL_KINDS, N_COLUMNS };
+inline constexpr struct { int32_t slf_module_desc::*field; const char* field_name; int n; const char* names[17]; } COLUMNS[N_COLUMNS] = {
+  {&slf_module_desc::lattice, "lattice", 4, {"D2Q9", "D3Q19", "D3Q15", "D3Q27"}},
+  {&slf_module_desc::simtype, "simtype", 5, {"single-fluid modules", "the Shan-Chen models", "the Shan-Chen models", "the free-energy model",
+                                             "the ternary Shan-Chen model"}},
+  {&slf_module_desc::model, "model", 3, {"--model=bgk", "--model=mrt", "--model=elbm"}},
+  {&slf_module_desc::entropic_equilibrium, "entropic_equilibrium", 2, {nullptr, "entropic_equilibrium"}},
+  {&slf_module_desc::regularized, "regularized", 2, {nullptr, "--regularized"}},
+  {&slf_module_desc::subgrid, "subgrid", 2, {nullptr, "--subgrid"}},
+  {&slf_module_desc::incompressible, "incompressible", 3, {"the compressible density model", "--incompressible", "--minimize_roundoff"}},
+  {&slf_module_desc::node_addressing, "node_addressing", 2, {"--node_addressing=direct", "--node_addressing=indirect"}},
+  {&slf_module_desc::has_force, "has_force", 2, {nullptr, "body forces"}},
+  {&slf_module_desc::accel_field, "accel_field", 2, {nullptr, "accel_field"}},
+  {&slf_module_desc::force_implementation, "force_implementation", 2, {nullptr, "force_implementation = EDM"}},
+  {nullptr, "type_kind", 17,      // one value per node type
+   {"fluid", nullptr, nullptr, nullptr, "NTFullBBWall", "NTHalfBBWall", "NTRegularizedVelocity", "NTEquilibriumDensity", "NTEquilibriumVelocity",
+    "NTZouHeVelocity", "NTZouHeDensity", "NTRegularizedDensity", "NTCopy", "NTYuOutflow", "NTDoNothing", "NTSlip", "NTWallTMS"}},
+};
 
-// The shallow-water equilibrium (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER) exists in the SW instantiations of the
-// per-node sweep and of SetInitialConditions and nowhere else: what those do not cover is named here and refused.  The
-// value-carrying node types are among it: their reference expressions assume the pressure rho / 3 and would have to be
-// derived again for gravity h^2 / 2.  NULL: the BGK polynomial, or the descriptor is served.  *code: the error to return.
-inline const char* sw_refusal(const slf_module_desc* d, int* code) {
-  *code = SLF_ERR_INVALID;
-  if (d->equilibrium != SLF_EQ_BGK && d->equilibrium != SLF_EQ_SHALLOW_WATER) return "equilibrium must be SLF_EQ_BGK or SLF_EQ_SHALLOW_WATER";
-  if (d->equilibrium == SLF_EQ_BGK) return nullptr;      // (gravity is not read)
-  if (!(d->gravity > 0.0)) return "shallow water: gravity must be > 0";
-  *code = SLF_ERR_UNSUPPORTED;
-  if (d->lattice != SLF_D2Q9) return "shallow water: D2Q9 only (the equilibrium is written for that lattice)";
-  if (d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE)
-    return "shallow water: the Shan-Chen models are not served; single-fluid modules only";
-  if (d->simtype == SLF_SIM_FREE_ENERGY) return "shallow water: the free-energy model is not served; single-fluid modules only";
-  if (d->simtype == SLF_SIM_SHAN_CHEN_TERNARY) return "shallow water: the ternary Shan-Chen model is not served; single-fluid modules only";
-  if (d->simtype != SLF_SIM_LBM) return "shallow water: single-fluid modules only";
-  if (d->model == SLF_MRT) return "shallow water: --model=mrt is not served; the BGK collision only";
-  if (d->model == SLF_ELBM) return "shallow water: --model=elbm is not served; the BGK collision only";
-  if (d->model != SLF_BGK) return "shallow water: the BGK collision only";
-  if (d->entropic_equilibrium) return "shallow water: entropic_equilibrium belongs to --model=elbm, which is not served";
-  if (d->regularized) return "shallow water: --regularized is not served";
-  if (d->subgrid) return "shallow water: --subgrid is not served";
-  if (d->incompressible == SLF_DENSITY_ROUNDOFF) return "shallow water: --minimize_roundoff is not served";
-  if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) return "shallow water: --incompressible is not served (the density is the water depth)";
-  if (d->node_addressing != SLF_ADDR_DIRECT) return "shallow water: --node_addressing=indirect is not served; direct addressing only";
-  for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++) {
-    const int k = d->type_kind[i];
-    if (k == SLF_NK_WALL_TMS) return "shallow water: NTWallTMS nodes are not served";
-    if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB ||
-          k == SLF_NK_HALF_BB || k == SLF_NK_SLIP))
-      return "shallow water: fluid, NTFullBBWall, NTHalfBBWall and NTSlip nodes only; the node types that carry a density or a "
-             "velocity (equilibrium, Zou-He, regularized, outflow, do-nothing) are not served";
+// A row is a feature that restricts what a module combines it with: per column, the mask of the field's values it is served
+// with (bit v: the value v; a yes / no field is served switched OFF only, or with ANY value).  `has`: the descriptor has the
+// feature.  `per_node_only`: the tuned, whole-row and slot kernels do not implement it (module_config clears
+// Geometry::variant).  `notes`: a reason worth telling, by column.  A new feature is one row here and one in sailfish_amd/serves.py.
+constexpr uint32_t bit(int v) { return 1u << ((v >= 0 && v < 31) ? v : 31); }      // (bit 31: every other value)
+constexpr uint32_t ANY = ~0u, OFF = bit(0), NO_EDM = ~bit(SLF_FORCE_EDM), NO_ELBM = ~bit(SLF_ELBM), NO_ROUNDOFF = ~bit(SLF_DENSITY_ROUNDOFF);
+constexpr uint32_t LBM = bit(SLF_SIM_LBM), BGK = bit(SLF_BGK), DIRECT = bit(SLF_ADDR_DIRECT), COMPRESSIBLE = bit(SLF_DENSITY_COMPRESSIBLE),
+                   INCOMPRESSIBLE = bit(SLF_DENSITY_INCOMPRESSIBLE);
+constexpr uint32_t KINDS_PLAIN = bit(SLF_NK_FLUID) | bit(SLF_NK_GHOST) | bit(SLF_NK_UNUSED) | bit(SLF_NK_PROPAGATION_ONLY) | bit(SLF_NK_FULL_BB),
+                   HALF_BB = bit(SLF_NK_HALF_BB), SLIP = bit(SLF_NK_SLIP), TMS = bit(SLF_NK_WALL_TMS),
+                   EQUILIBRIUM = bit(SLF_NK_EQUILIBRIUM_DENSITY) | bit(SLF_NK_EQUILIBRIUM_VELOCITY);
+struct Serves {
+  const char* name;
+  bool (*has)(const slf_module_desc*);
+  bool per_node_only;
+  uint32_t serves[N_COLUMNS];
+  struct { int column; const char* text; } notes[2];
+};
+#define SLF_HAS(expr) [](const slf_module_desc* d) -> bool { return expr; }
+#define SLF_LAT_ROW(name, id) /* the BGK sweep of slf_lat.hip and nothing else */ \
+  {name, SLF_HAS(d->lattice == id), true, {ANY, LBM, BGK, OFF, OFF, OFF, NO_ROUNDOFF, DIRECT, ANY, ANY, ANY, KINDS_PLAIN | HALF_BB}, {}}
+enum Row { ROW_SHALLOW_WATER, ROW_ACCEL_FIELD, ROW_D3Q15, ROW_D3Q27, ROW_REGULARIZED_SUBGRID, ROW_TMS, ROW_ELBM, ROW_ROUNDOFF, ROW_SHAN_CHEN,
+           ROW_FREE_ENERGY, ROW_TERNARY, N_ROWS };
+inline const Serves SERVES[N_ROWS] = {
+  // masks: lattice, simtype, model, entropic, regularized, subgrid, density, addressing, force, accel_field, edm, kinds
+  {"shallow water", SLF_HAS(d->equilibrium == SLF_EQ_SHALLOW_WATER), true,      // the SW instantiations of the per-node sweep
+   {bit(SLF_D2Q9), LBM, BGK, OFF, OFF, OFF, COMPRESSIBLE, DIRECT, ANY, ANY, ANY, KINDS_PLAIN | HALF_BB | SLIP},
+   {{COL_DENSITY, "the density is the water depth"},
+    {COL_KINDS, "the node types that carry a density or a velocity assume the pressure rho / 3"}}},
+  {"accel_field", SLF_HAS(d->accel_field == 1), true,                           // the ACCF instantiations of the per-node sweep
+   {bit(SLF_D2Q9) | bit(SLF_D3Q19), LBM, NO_ELBM, ANY, OFF, OFF, NO_ROUNDOFF, DIRECT, ANY, ANY, ANY, ~TMS},
+   {{COL_LATTICE, "the sweep of D3Q15 / D3Q27 takes a constant acceleration"}, {COL_MODEL, "the entropic collision takes no body force"}}},
+  SLF_LAT_ROW("D3Q15", SLF_D3Q15),
+  SLF_LAT_ROW("D3Q27", SLF_D3Q27),
+  // the options of the BGK relaxation preamble (relaxation_common.mako:166-237): the reference's MRT relaxation does not call it
+  // (its kernels would silently ignore both flags), and its expressions were never written for the rest
+  {"regularized / subgrid", SLF_HAS(d->regularized || d->subgrid), true,
+   {ANY, LBM, BGK, ANY, ANY, ANY, NO_ROUNDOFF, ANY, ANY, ANY, NO_EDM, ANY}, {}},
+  // the per-node kernels and the slot sweep carry the walls' code; module_config does not walk this row: the other models' own
+  // rows refuse the type among their node kinds, where the ladders did
+  {"NTWallTMS", [](const slf_module_desc* d) -> bool {
+     for (int i = 0; i < d->n_types && i < SLF_MAX_NODE_TYPES; i++)
+       if (d->type_kind[i] == SLF_NK_WALL_TMS) return true;
+     return false;
+   }, true, {ANY, LBM, ANY, ANY, ANY, ANY, ANY, ANY, ANY, ANY, ANY, ANY}, {}},
+  // what ELBM_relaxate (relaxation.mako:56-97) was written for, and what this library has fixtures for
+  {"elbm", SLF_HAS(d->model == SLF_ELBM), true, {ANY, LBM, ANY, ANY, OFF, OFF, NO_ROUNDOFF, ANY, OFF, ANY, ANY, ANY},
+   {{COL_DENSITY, "it stores f_i - w_i, the entropy needs the populations themselves"}}},
+  // "BGK-like models" in the reference (lb_base.py:72-76), whose regularized and Zou-He expressions are inconsistent under the option
+  {"minimize_roundoff", SLF_HAS(d->incompressible == SLF_DENSITY_ROUNDOFF), true,
+   {ANY, LBM, BGK, ANY, ANY, ANY, ANY, ANY, ANY, ANY, ANY, KINDS_PLAIN | HALF_BB | TMS | EQUILIBRIUM}, {}},
+  {"Shan-Chen", SLF_HAS(d->simtype == SLF_SIM_SHAN_CHEN_BINARY || d->simtype == SLF_SIM_SHAN_CHEN_SINGLE), false,
+   {ANY, ANY, BGK, ANY, ANY, ANY, ANY, ANY, ANY, ANY, ANY, KINDS_PLAIN}, {}},
+  {"free energy", SLF_HAS(d->simtype == SLF_SIM_FREE_ENERGY), false,          // slf_fe.hip, of the reference's lb_binary.py:139-372
+   {ANY, ANY, BGK, ANY, ANY, ANY, COMPRESSIBLE, DIRECT, OFF, ANY, ANY, KINDS_PLAIN},
+   {{COL_MODEL, "the FE-MRT collision, relaxation.mako:15-54"}, {COL_FORCE, "free_energy_external_force, use_force_for_equilibrium"}}},
+  {"ternary Shan-Chen", SLF_HAS(d->simtype == SLF_SIM_SHAN_CHEN_TERNARY), false,      // slf_sc3.hip, of the reference's lb_ternary.py
+   {ANY, ANY, BGK, ANY, ANY, ANY, COMPRESSIBLE, DIRECT, ANY, ANY, ANY, KINDS_PLAIN}, {}},
+};
+#undef SLF_LAT_ROW
+#undef SLF_HAS
+
+// The first conflict of the descriptor with those of the rows first .. last that apply to it, rows and columns in table order:
+// "<feature>: <offender> is not served (<note>); <what the row serves> only".  NULL: served.  The message lives in a buffer of
+// the calling thread until its next call.  module_config walks each row where the descriptor is well-formed enough for it.
+inline const char* serves_conflict(const slf_module_desc* d, int first, int last) {
+  thread_local char msg[512];
+  for (int r = first; r <= last; r++) {
+    const Serves& row = SERVES[r];
+    for (int col = 0; row.has(d) && col < N_COLUMNS; col++) {
+      const auto& c = COLUMNS[col];
+      const uint32_t serves = row.serves[col];
+      for (int i = 0; i < (c.field ? 1 : d->n_types) && i < SLF_MAX_NODE_TYPES; i++) {
+        const int v = c.field ? d->*c.field : d->type_kind[i];
+        if (serves & bit(v)) continue;
+        size_t len = 0;
+        auto say = [&len](const char* a, const char* b, const char* end) {
+          if (len < sizeof msg) len += snprintf(msg + len, sizeof msg - len, "%s%s%s", a, b, end);
+        };
+        const char* offender = v >= 0 && v < c.n ? c.names[v] : nullptr;
+        char value[32];
+        snprintf(value, sizeof value, " = %d", v);
+        say(row.name, ": ", offender ? offender : c.field_name);
+        say(offender ? "" : value, offender && offender[strlen(offender) - 1] == 's' ? " are" : " is", " not served");
+        for (const auto& note : row.notes)      // (a value without a name is malformed: the reason is not about it)
+          if (note.text && note.column == col && offender) say(" (", note.text, ")");
+        const char* listed[17];
+        int n = 0;
+        for (int s = 0; s < c.n; s++)
+          if ((serves & bit(s)) && c.names[s]) listed[n++] = c.names[s];
+        if (n > 6) n = 0;      // (a longer list says little more than the offender did)
+        for (int k = 0; k < n; k++) say(k == 0 ? "; " : (k == n - 1 ? " and " : ", "), listed[k], "");
+        if (n) say(c.field ? " only" : " nodes only", "", "");
+        return msg;
+      }
+    }
   }
   return nullptr;
 }
@@ -182,12 +218,13 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   if (d->struct_size != sizeof(slf_module_desc)) return refuse(err, SLF_ERR_INVALID, "slf_module_desc size mismatch (ABI)");
   if (d->lattice != SLF_D2Q9 && d->lattice != SLF_D3Q19 && d->lattice != SLF_D3Q15 && d->lattice != SLF_D3Q27)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported lattice");
-  {
-    int code = SLF_OK;
-    if (const char* why = sw_refusal(d, &code)) return refuse(err, code, why);
-  }
-  if (const char* why = accf_refusal(d)) return refuse(err, d->accel_field == 1 ? SLF_ERR_UNSUPPORTED : SLF_ERR_INVALID, why);
-  if (const char* why = lat_refusal(d)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  if (d->equilibrium != SLF_EQ_BGK && d->equilibrium != SLF_EQ_SHALLOW_WATER)
+    return refuse(err, SLF_ERR_INVALID, "equilibrium must be SLF_EQ_BGK or SLF_EQ_SHALLOW_WATER");
+  if (d->equilibrium == SLF_EQ_SHALLOW_WATER && !(d->gravity > 0.0)) return refuse(err, SLF_ERR_INVALID, "shallow water: gravity must be > 0");
+  // which options each feature is served with: the table SERVES, each row walked where its ladder stood
+  if (const char* why = serves_conflict(d, ROW_SHALLOW_WATER, ROW_SHALLOW_WATER)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  if (d->accel_field != 0 && d->accel_field != 1) return refuse(err, SLF_ERR_INVALID, "accel_field must be 0 or 1");
+  if (const char* why = serves_conflict(d, ROW_ACCEL_FIELD, ROW_D3Q27)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   if (d->model != SLF_BGK && d->model != SLF_MRT && d->model != SLF_ELBM)
     return refuse(err, SLF_ERR_UNSUPPORTED, "unsupported collision model");
   if (d->precision != 4 && d->precision != 8) return refuse(err, SLF_ERR_UNSUPPORTED, "precision must be 4 or 8");
@@ -214,7 +251,7 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   if (d->node_addressing == SLF_ADDR_INDIRECT) {
     if (d->fluid_only) return refuse(err, SLF_ERR_INVALID, "indirect addressing needs the node map (fluid_only = 0)");
     if (d->simtype != SLF_SIM_LBM && d->simtype != SLF_SIM_SHAN_CHEN_BINARY && d->simtype != SLF_SIM_SHAN_CHEN_SINGLE &&
-        d->simtype != SLF_SIM_FREE_ENERGY && d->simtype != SLF_SIM_SHAN_CHEN_TERNARY) {      // (free energy, ternary: refused below, with their own messages)
+        d->simtype != SLF_SIM_FREE_ENERGY && d->simtype != SLF_SIM_SHAN_CHEN_TERNARY) {      // (free energy, ternary: refused below, by their rows)
       return refuse(err, SLF_ERR_UNSUPPORTED, "indirect addressing: unknown simtype");
     }
   }
@@ -265,8 +302,7 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   g.bc_level = 0;
   for (int i = 0; i < d->n_types; i++) {
     const int k = d->type_kind[i];
-    const bool plain = k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-                       k == SLF_NK_FULL_BB;
+    const bool plain = (KINDS_PLAIN & bit(k)) != 0;
     const int level = (k == SLF_NK_COPY || k == SLF_NK_YU_OUTFLOW || k == SLF_NK_DO_NOTHING || k == SLF_NK_SLIP) ? 2 : (plain ? 0 : 1);
     if (level > g.bc_level) g.bc_level = level;
   }
@@ -279,6 +315,8 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   g.variant = SLF_DEFAULT_VARIANT;
   if (d->sparse_geometry) g.variant |= 64;
   if (const char* ev = getenv("SLF_VARIANT")) g.variant = atoi(ev);
+  for (const Serves& row : SERVES)
+    if (row.per_node_only && row.has(d)) g.variant = 0;      // the tuned, whole-row and slot kernels implement the plain module (wins over the knob)
   slf::Physics& ph = c->phys;
   ph.tau = d->tau;
   ph.visc = d->visc;
@@ -298,76 +336,39 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
   ph.smagorinsky_const = d->smagorinsky_const;
   if (d->subgrid != SLF_SUBGRID_NONE && d->subgrid != SLF_SUBGRID_LES_SMAGORINSKY)
     return refuse(err, SLF_ERR_INVALID, "subgrid must be one of SLF_SUBGRID_*");
-  if (ph.regularized || ph.subgrid) {
-    // the options of the BGK relaxation preamble (relaxation_common.mako:166-237).  The reference's MRT relaxation does not
-    // call the preamble (its kernels would silently ignore both flags); here that is an error, as are the combinations the
-    // preamble's expressions were never written for
-    if (d->model != SLF_BGK || d->simtype != SLF_SIM_LBM || d->incompressible == SLF_DENSITY_ROUNDOFF || ph.force_edm)
-      return refuse(err, SLF_ERR_UNSUPPORTED, "regularized / subgrid: single-fluid BGK modules, standard or incompressible density "
-                                       "model, Guo forcing or no body force");
-    if (ph.subgrid && !(d->smagorinsky_const > 0.0))
-      return refuse(err, SLF_ERR_INVALID, "subgrid = les-smagorinsky needs smagorinsky_const > 0");
-    g.variant = 0;       // per-node kernels: the tuned / whole-row ones implement the plain collision
-  }
+  if (const char* why = serves_conflict(d, ROW_REGULARIZED_SUBGRID, ROW_REGULARIZED_SUBGRID)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  if (ph.subgrid && !(d->smagorinsky_const > 0.0))
+    return refuse(err, SLF_ERR_INVALID, "subgrid = les-smagorinsky needs smagorinsky_const > 0");
   if (ph.tms_mask && d->fluid_only)
     return refuse(err, SLF_ERR_UNSUPPORTED, "NTWallTMS nodes are node types: the module must read the node map (fluid_only = 0)");
-  if (ph.tms_mask) g.variant = 0;       // Tamm-Mott-Smith walls: the per-node kernels and the slot sweep carry their code
   ph.entropic_equilibrium = d->entropic_equilibrium != 0;
   ph.entropy_tolerance = d->entropy_tolerance;
   ph.alpha_tolerance = d->alpha_tolerance;
   if (ph.entropic_equilibrium && d->model != SLF_ELBM)
     return refuse(err, SLF_ERR_INVALID, "entropic_equilibrium needs model = SLF_ELBM");
   if (d->model == SLF_ELBM) {
-    // what ELBM_relaxate (relaxation.mako:56-97) was written for, and what this library has fixtures for (regularized /
-    // subgrid, the options of the BGK preamble it never runs, were refused above)
-    const char* why = nullptr;
     bool rates = false;            // a host that filled in MRT relaxation rates expects them to act
     for (int i = 0; i < 27; i++) rates = rates || d->mrt_rates[i] != 0.0;
-    if (rates) why = "elbm: MRT relaxation rates are set (mrt_rates must be all zero: the entropic collision has one rate)";
-    else if (d->simtype != SLF_SIM_LBM) why = "elbm: single-fluid modules only (the Shan-Chen models use the BGK collision)";
-    else if (d->incompressible == SLF_DENSITY_ROUNDOFF) why = "elbm: minimize_roundoff stores f_i - w_i, the entropy needs the populations themselves";
-    else if (d->incompressible == SLF_DENSITY_INCOMPRESSIBLE && ph.entropic_equilibrium)
-      why = "elbm: the product-form equilibrium (entropic_equilibrium) is compressible; not with the incompressible density model";
-    else if (d->has_force) why = "elbm: body forces under the entropic collision are not served";
-    else if (!(d->entropy_tolerance > 0.0) || !(d->alpha_tolerance >= 0.0)) why = "elbm: entropy_tolerance must be > 0 and alpha_tolerance >= 0";
-    if (why) return refuse(err, SLF_ERR_UNSUPPORTED, why);
-    g.variant = 0;       // per-node kernels only
+    if (rates)
+      return refuse(err, SLF_ERR_UNSUPPORTED, "elbm: MRT relaxation rates are set (mrt_rates must be all zero: the entropic collision has one rate)");
+    if (const char* why = serves_conflict(d, ROW_ELBM, ROW_ELBM)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+    if (d->incompressible == SLF_DENSITY_INCOMPRESSIBLE && ph.entropic_equilibrium)
+      return refuse(err, SLF_ERR_UNSUPPORTED, "elbm: the product-form equilibrium (entropic_equilibrium) is compressible; not with the "
+                                              "incompressible density model");
+    if (!(d->entropy_tolerance > 0.0) || !(d->alpha_tolerance >= 0.0))
+      return refuse(err, SLF_ERR_UNSUPPORTED, "elbm: entropy_tolerance must be > 0 and alpha_tolerance >= 0");
   }
-  if (d->incompressible == SLF_DENSITY_ROUNDOFF) {
-    // --minimize_roundoff: "BGK-like models" in the reference (lb_base.py:72-76); here BGK, single fluid, fluid and
-    // bounce-back nodes, through the per-node kernels (slf_node.h: macro_roundoff, bgk_relax_roundoff)
-    bool ok = d->model == SLF_BGK && d->simtype == SLF_SIM_LBM;
-    for (int i = 0; ok && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      ok = k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-           k == SLF_NK_FULL_BB || k == SLF_NK_HALF_BB || k == SLF_NK_WALL_TMS || k == SLF_NK_EQUILIBRIUM_DENSITY ||
-           k == SLF_NK_EQUILIBRIUM_VELOCITY;
-    }
-    if (!ok)
-      return refuse(err, SLF_ERR_UNSUPPORTED, "minimize_roundoff: BGK single-fluid modules with fluid, bounce-back, TMS wall and equilibrium "
-                                       "density / velocity nodes only (the reference's regularized and Zou-He expressions are "
-                                       "inconsistent under the option)");
-    g.variant = 0;       // no tuned / whole-row kernels: they implement the standard formulation
-  } else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE && d->incompressible != SLF_DENSITY_INCOMPRESSIBLE) {
+  if (const char* why = serves_conflict(d, ROW_ROUNDOFF, ROW_ROUNDOFF)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  if (d->incompressible < SLF_DENSITY_COMPRESSIBLE || d->incompressible > SLF_DENSITY_ROUNDOFF)
     return refuse(err, SLF_ERR_INVALID, "incompressible must be one of SLF_DENSITY_*");
-  }
   c->sc.enabled = (d->simtype == SLF_SIM_SHAN_CHEN_BINARY) ? 1 : ((d->simtype == SLF_SIM_SHAN_CHEN_SINGLE) ? 2 : 0);
   c->sc.tau_phi = d->tau_phi;
   for (int i = 0; i < 4; i++) c->sc.G[i] = d->sc_G[i];
   c->sc.potential = d->sc_potential;
   for (int i = 0; i < 3; i++) c->sc.accel1[i] = d->accel1[i];
-  if (c->sc.enabled) {
-    if (d->model != SLF_BGK) return refuse(err, SLF_ERR_UNSUPPORTED, "Shan-Chen modules use the BGK collision");
-    if (c->sc.enabled == 1 && d->tau_phi <= 0.5) return refuse(err, SLF_ERR_INVALID, "tau_phi must be > 0.5");
-    if (c->sc.enabled == 2) c->sc.tau_phi = d->tau;
-    for (int i = 0; i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY ||
-            k == SLF_NK_FULL_BB)) {
-        return refuse(err, SLF_ERR_UNSUPPORTED, "Shan-Chen modules support fluid and full-way bounce-back nodes only");
-      }
-    }
-  }
+  if (const char* why = serves_conflict(d, ROW_SHAN_CHEN, ROW_TERNARY)) return refuse(err, SLF_ERR_UNSUPPORTED, why);
+  if (c->sc.enabled == 1 && d->tau_phi <= 0.5) return refuse(err, SLF_ERR_INVALID, "tau_phi must be > 0.5");
+  if (c->sc.enabled == 2) c->sc.tau_phi = d->tau;
   c->fe = slf::FreeEnergy{};
   if (d->simtype == SLF_SIM_FREE_ENERGY) {
     // what slf_fe.hip implements of the reference's model (lb_binary.py:139-372); everything else is named and refused
@@ -379,25 +380,13 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
     fe.wall_order = d->bc_wall_grad_order;
     for (int i = 0; i < 3; i++) fe.rim[i] = d->fe_zero_grad_rim[i];
     const char* why = nullptr;
-    if (d->model == SLF_MRT) why = "free energy: --model=mrt (the FE-MRT collision, relaxation.mako:15-54) is not implemented; BGK only";
-    else if (d->model != SLF_BGK) why = "free energy: the BGK collision only";
-    else if (d->has_force || d->accel1[0] != 0.0 || d->accel1[1] != 0.0 || d->accel1[2] != 0.0)
+    if (d->accel1[0] != 0.0 || d->accel1[1] != 0.0 || d->accel1[2] != 0.0)
       why = "free energy: body forces (free_energy_external_force, use_force_for_equilibrium) are not implemented";
-    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "free energy: indirect addressing is not implemented; direct addressing only";
-    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "free energy: --incompressible / --minimize_roundoff are not implemented";
     else if (!(d->fe_tau_a > 0.5) || !(d->fe_tau_b > 0.5) || !(d->tau_phi > 0.5)) why = "free energy: tau_a, tau_b and tau_phi must be > 0.5";
     else if (d->bc_wall_grad_order != 1 && d->bc_wall_grad_order != 2) why = "free energy: bc_wall_grad_order must be 1 or 2";
     for (int i = 0; !why && i < 3; i++) {
       if (d->fe_zero_grad_rim[i] < 0 || d->fe_zero_grad_rim[i] > 2) why = "free energy: fe_zero_grad_rim entries are 0, 1 (low rim) or 2 (high rim)";
     }
-    for (int i = 0; !why && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (k == SLF_NK_HALF_BB) why = "free energy: NTHalfBBWall wetting walls are not implemented; full-way bounce-back walls only";
-      else if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
-        why = "free energy: fluid and full-way bounce-back (NTFullBBWall) nodes only; NTGuoDensity and the other boundary "
-              "conditions are not implemented";
-    }
-    // (--regularized / --subgrid were refused above: single-fluid modules only)
     if (why) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   }
   c->sc3 = slf::ShanChen3{};
@@ -411,23 +400,10 @@ inline int module_config(const slf_module_desc* d, ModuleConfig* c, const char**
     t.potential = d->sc_potential;
     for (int i = 0; i < 3; i++) { t.accel1[i] = d->accel1[i]; t.accel2[i] = d->accel2[i]; }
     const char* why = nullptr;
-    if (d->model != SLF_BGK) why = "ternary Shan-Chen: --model other than bgk is not implemented; the BGK collision only";
-    else if (d->node_addressing != SLF_ADDR_DIRECT) why = "ternary Shan-Chen: --node_addressing=indirect is not implemented; direct addressing only";
-    else if (d->incompressible != SLF_DENSITY_COMPRESSIBLE) why = "ternary Shan-Chen: --incompressible / --minimize_roundoff are not implemented";
-    else if (!(d->tau_phi > 0.5) || !(d->tau_theta > 0.5)) why = "ternary Shan-Chen: tau_phi and tau_theta must be > 0.5";
+    if (!(d->tau_phi > 0.5) || !(d->tau_theta > 0.5)) why = "ternary Shan-Chen: tau_phi and tau_theta must be > 0.5";
     else if (d->sc_potential != 0 && d->sc_potential != 1) why = "ternary Shan-Chen: sc_potential is 0 (linear) or 1 (classic)";
-    for (int i = 0; !why && i < d->n_types; i++) {
-      const int k = d->type_kind[i];
-      if (!(k == SLF_NK_FLUID || k == SLF_NK_GHOST || k == SLF_NK_UNUSED || k == SLF_NK_PROPAGATION_ONLY || k == SLF_NK_FULL_BB))
-        why = "ternary Shan-Chen: fluid and full-way bounce-back (NTFullBBWall) nodes only; the other boundary conditions "
-              "are not implemented";
-    }
-    // (--regularized / --subgrid / --model=elbm were refused above: single-fluid modules only)
     if (why) return refuse(err, SLF_ERR_UNSUPPORTED, why);
   }
-  if (is_lat_lattice(d->lattice)) g.variant = 0;      // no tuned / whole-row D3Q19 kernels: the sweep of slf_lat.hip
-  if (ph.accel_field) g.variant = 0;       // the acceleration field is read by the per-node kernels only (ACCF)
-  if (ph.equilibrium == SLF_EQ_SHALLOW_WATER) g.variant = 0;      // the tuned, whole-row and slot kernels implement the BGK polynomial (SW)
   // Workgroup = an x-chunk of one row.  Whole rows up to 1024 nodes are one
   // workgroup; longer rows are cut into 256-thread chunks.
   int bx = ((d->lat_nx - 2 + 63) / 64) * 64;

@@ -466,7 +466,7 @@ __device__ __forceinline__ void node_update(const SweepParams<L, R>& p, R (&f)[L
       else mrt_relax<L, R, V.force>(f, v, p.cp, false);
     }
   } else if constexpr (V.general && V.sw) {
-    // The node kinds a shallow-water module can have (slf_bind.h sw_refusal): fluid, full-way and half-way bounce-back,
+    // The node kinds a shallow-water module can have (slf_bind.h SERVES): fluid, full-way and half-way bounce-back,
     // slip -- the same functions in the same order as below, without the code of the kinds that carry a density or a
     // velocity (the outflow nodes' reads of the input array cost the two-copy instantiations 32 bytes of scratch per lane).
     wet = kind_is_wet(kind);

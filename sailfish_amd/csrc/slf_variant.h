@@ -26,7 +26,7 @@ namespace slf {
 // sw: a shallow-water module (slf_module_desc::equilibrium = SLF_EQ_SHALLOW_WATER): the BGK relaxation uses sw_equilibrium
 // (slf_node.h) with p.cp.gravity -- and that is all: moments, bounce-back, the half-way store, the slip reflection and
 // streaming are the code of every other module.  The per-node sweep only; the value-carrying node kinds are refused at
-// module creation (slf_bind.h sw_refusal).
+// module creation (slf_bind.h SERVES).
 struct SweepVariant {
   int model = 0;
   int prop = PROP_AB;

@@ -7,7 +7,7 @@ import numpy as np
 from sailfish_amd import hipabi
 
 from sailfish_amd import node_type as nt
-from sailfish_amd import sym, util
+from sailfish_amd import serves, sym, util
 
 FieldPair = namedtuple('FieldPair', 'abstract buffer')
 KernelPair = namedtuple('KernelPair', 'primary secondary')
@@ -219,122 +219,31 @@ class LBSim(object):
     @classmethod
     def check_module_desc(cls, kw):
         """Refuses, on the host and with a clear message, what no kernel of the library covers (the library refuses the
-        same at module creation)."""
+        same at module creation): the rows of sailfish_amd/serves.py every model shares."""
         cls.check_lattice(kw)
         cls.check_accel_field(kw)
         cls.check_shallow_water(kw)
-        if hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []) and kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
-            raise NotImplementedError('NTWallTMS nodes: single-fluid simulations only (the Shan-Chen kernels serve fluid and '
-                                      'full-way bounce-back nodes)')
-
-    # what the sweep of D3Q15 / D3Q27 (csrc/slf_lat.hip) serves: the BGK collision of a single fluid over these node kinds
-    LAT_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                 hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB)
+        serves.check(kw, ('NTWallTMS',))
 
     @staticmethod
     def check_lattice(kw):
-        """D3Q15 and D3Q27: everything but the BGK collision of a single fluid with fluid, full-way and half-way wall nodes,
-        dense addressing and the standard or incompressible density model is refused, naming the lattice."""
-        name = {hipabi.SLF_D3Q15: 'D3Q15', hipabi.SLF_D3Q27: 'D3Q27'}.get(kw.get('lattice'))
-        if name is None:
-            return
-        why = None
-        model = kw.get('model', hipabi.SLF_BGK)
-        simtype = kw.get('simtype', hipabi.SLF_SIM_LBM)
-        if model != hipabi.SLF_BGK:
-            why = '--model=%s is not implemented; the BGK collision only' % {hipabi.SLF_MRT: 'mrt', hipabi.SLF_ELBM: 'elbm'}.get(model, model)
-        elif simtype != hipabi.SLF_SIM_LBM:
-            why = 'the %s model is not implemented; single-fluid simulations only' % {
-                hipabi.SLF_SIM_SHAN_CHEN_BINARY: 'Shan-Chen', hipabi.SLF_SIM_SHAN_CHEN_SINGLE: 'Shan-Chen',
-                hipabi.SLF_SIM_FREE_ENERGY: 'free-energy', hipabi.SLF_SIM_SHAN_CHEN_TERNARY: 'ternary Shan-Chen'}.get(simtype, simtype)
-        elif kw.get('regularized'):
-            why = '--regularized is not implemented'
-        elif kw.get('subgrid'):
-            why = '--subgrid is not implemented'
-        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
-            why = '--minimize_roundoff is not implemented'
-        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
-            why = '--node_addressing=indirect is not implemented; direct addressing only'
-        elif any(k not in LBSim.LAT_KINDS for k in kw.get('type_kind', [])):
-            why = 'fluid, NTFullBBWall and NTHalfBBWall nodes only; the other node types are not implemented'
-        if why:
-            raise NotImplementedError('%s: %s on this lattice' % (name, why))
+        """D3Q15 and D3Q27: what the sweep of csrc/slf_lat.hip does not serve is refused, naming the lattice."""
+        serves.check(kw, ('D3Q15', 'D3Q27'))
 
     @staticmethod
     def check_accel_field(kw):
         """A body force that depends on position (accel_field) is read by one family of sweep kernels (csrc/slf_kernels.hip,
-        the ACCF instantiations of the per-node sweep): single fluid, D2Q9 / D3Q19, BGK and MRT, dense addressing.  The rest
-        is refused here, naming the option (the library refuses the same at module creation)."""
-        if not kw.get('accel_field'):
-            return
-        why = None
-        simtype = kw.get('simtype', hipabi.SLF_SIM_LBM)
-        lat = {hipabi.SLF_D3Q15: 'D3Q15', hipabi.SLF_D3Q27: 'D3Q27'}.get(kw.get('lattice'))
-        if lat is not None:
-            why = '--grid=%s is not served; D2Q9 and D3Q19 only' % lat
-        elif simtype != hipabi.SLF_SIM_LBM:
-            why = 'the %s model is not served; single-fluid simulations only' % {
-                hipabi.SLF_SIM_SHAN_CHEN_BINARY: 'Shan-Chen', hipabi.SLF_SIM_SHAN_CHEN_SINGLE: 'Shan-Chen',
-                hipabi.SLF_SIM_FREE_ENERGY: 'free-energy', hipabi.SLF_SIM_SHAN_CHEN_TERNARY: 'ternary Shan-Chen'}.get(simtype, simtype)
-        elif kw.get('model', hipabi.SLF_BGK) == hipabi.SLF_ELBM:
-            why = '--model=elbm is not served; BGK and MRT only'
-        elif kw.get('regularized'):
-            why = '--regularized is not served'
-        elif kw.get('subgrid'):
-            why = '--subgrid is not served'
-        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
-            why = '--minimize_roundoff is not served'
-        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
-            why = '--node_addressing=indirect is not served; direct addressing only'
-        elif hipabi.SLF_NK_WALL_TMS in kw.get('type_kind', []):
-            why = 'NTWallTMS nodes are not served'
-        if why:
-            raise NotImplementedError('body forces that depend on position: %s' % why)
-
-    # what the shallow-water sweep serves: nodes whose code moves populations and carries neither a density nor a velocity
-    SW_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB, hipabi.SLF_NK_SLIP)
+        the ACCF instantiations of the per-node sweep).  The rest is refused here, naming the option."""
+        serves.check(kw, ('accel_field',))
 
     @staticmethod
     def check_shallow_water(kw):
         """The shallow-water equilibrium (equilibrium = SLF_EQ_SHALLOW_WATER, LBFreeSurface) exists in one family of sweep
-        kernels (csrc/slf_kernels.hip, the SW instantiations of the per-node sweep): single fluid, D2Q9, BGK, the compressible
-        density model, dense addressing, fluid / bounce-back / slip nodes.  The rest is refused here, naming the option or the
-        node type (the library refuses the same at module creation)."""
-        if not kw.get('equilibrium'):
-            return
-        why = None
-        model = kw.get('model', hipabi.SLF_BGK)
-        kinds = list(kw.get('type_kind', []))
-        if not kw.get('gravity', 0.0) > 0.0:
+        kernels (csrc/slf_kernels.hip, the SW instantiations of the per-node sweep).  The rest is refused here, naming the
+        option or the node type."""
+        if kw.get('equilibrium') and not kw.get('gravity', 0.0) > 0.0:
             raise ValueError('shallow water: --gravity must be positive')
-        if kw.get('lattice', hipabi.SLF_D2Q9) != hipabi.SLF_D2Q9:
-            why = 'D2Q9 only'
-        elif kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
-            why = 'single-fluid simulations only'
-        elif model != hipabi.SLF_BGK:
-            why = '--model=%s is not served; the BGK collision only' % {hipabi.SLF_MRT: 'mrt', hipabi.SLF_ELBM: 'elbm'}.get(model, model)
-        elif kw.get('entropic_equilibrium'):
-            why = '--entropic_equilibrium belongs to --model=elbm, which is not served'
-        elif kw.get('regularized'):
-            why = '--regularized is not served'
-        elif kw.get('subgrid'):
-            why = '--subgrid is not served'
-        elif kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
-            why = '--minimize_roundoff is not served'
-        elif kw.get('incompressible'):
-            why = '--incompressible is not served (the density is the water depth)'
-        elif kw.get('node_addressing', hipabi.SLF_ADDR_DIRECT) != hipabi.SLF_ADDR_DIRECT:
-            why = '--node_addressing=indirect is not served; direct addressing only'
-        elif hipabi.SLF_NK_WALL_TMS in kinds:
-            why = 'NTWallTMS nodes are not served'
-        elif any(k not in LBSim.SW_KINDS for k in kinds):
-            bad = set(kinds) - set(LBSim.SW_KINDS)
-            names = sorted(cls.__name__ for cls, k in nt.HIP_KIND.items() if k in bad)
-            why = '%s nodes are not served: fluid, NTFullBBWall, NTHalfBBWall and NTSlip nodes only (the node types that ' \
-                  'carry a density or a velocity assume the pressure rho / 3)' % ' / '.join(names)
-        if why:
-            raise NotImplementedError('shallow water (LBFreeSurface): %s' % why)
+        serves.check(kw, ('shallow water',))
 
     def fill_module_desc(self, kw):
         """Contributes to the kernel-module descriptor (the counterpart of the reference's

@@ -4,7 +4,7 @@ from collections import defaultdict, namedtuple
 
 import numpy as np
 
-from sailfish_amd import hipabi, subdomain_runner, sym
+from sailfish_amd import hipabi, serves, subdomain_runner, sym
 from sailfish_amd.lb_base import LBForcedSim, LBSim, ScalarField, VectorField
 
 MacroKernels = namedtuple('MacroKernels', 'distributions macro')
@@ -113,16 +113,8 @@ class LBBinaryFluidFreeEnergy(LBBinaryFluidBase):
     def fill_module_desc(self, kw):
         super(LBBinaryFluidFreeEnergy, self).fill_module_desc(kw)
         c = self.config
-        if getattr(c, 'model', 'bgk') != 'bgk':
-            raise NotImplementedError('free-energy model: --model=%s (the FE-MRT collision, reference relaxation.mako:15-54) '
-                                      'is not implemented by the HIP backend; use --model=bgk' % c.model)
-        if getattr(c, 'node_addressing', 'direct') != 'direct':
-            raise NotImplementedError('free-energy model: --node_addressing=indirect is not implemented by the HIP backend')
-        for opt in ('minimize_roundoff', 'regularized', 'incompressible'):
-            if getattr(c, opt, False):
-                raise NotImplementedError('free-energy model: --%s is not implemented by the HIP backend' % opt)
-        if getattr(c, 'subgrid', 'none') not in ('none', None, ''):
-            raise NotImplementedError('free-energy model: --subgrid=%s is not implemented by the HIP backend' % c.subgrid)
+        serves.check(serves.config_fields(c, simtype=hipabi.SLF_SIM_FREE_ENERGY), ('regularized / subgrid', 'free energy'),
+                     columns=serves.COLUMNS)
         if c.bc_wall_grad_order not in (1, 2):
             raise ValueError('--bc_wall_grad_order must be 1 or 2')
         kw.update(lattice=self.grid.slf_id, simtype=hipabi.SLF_SIM_FREE_ENERGY,
@@ -134,15 +126,7 @@ class LBBinaryFluidFreeEnergy(LBBinaryFluidBase):
     @classmethod
     def check_module_desc(cls, kw):
         super(LBBinaryFluidFreeEnergy, cls).check_module_desc(kw)
-        plain = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                 hipabi.SLF_NK_FULL_BB)
-        for kind in kw.get('type_kind', []):
-            if kind == hipabi.SLF_NK_HALF_BB:
-                raise NotImplementedError('free-energy model: NTHalfBBWall wetting walls are not implemented by the HIP '
-                                          'backend; use NTFullBBWall')
-            if kind not in plain:
-                raise NotImplementedError('free-energy model: fluid and NTFullBBWall nodes only (node kind %d is not '
-                                          'implemented by the free-energy kernels)' % kind)
+        serves.check(kw, ('free energy',), always=True)
 
     @staticmethod
     def zero_gradient_rims(spec, dim):

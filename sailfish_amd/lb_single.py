@@ -3,7 +3,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from sailfish_amd import hipabi, subdomain_runner, sym
+from sailfish_amd import hipabi, serves, subdomain_runner, sym
 from sailfish_amd.lb_base import KernelPair, LBForcedSim, LBSim, ScalarField, VectorField
 
 
@@ -90,39 +90,24 @@ class LBFluidSim(LBSim):
             return hipabi.SLF_DENSITY_ROUNDOFF
         return hipabi.SLF_DENSITY_COMPRESSIBLE
 
-    ROUNDOFF_KINDS = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                      hipabi.SLF_NK_FULL_BB, hipabi.SLF_NK_HALF_BB, hipabi.SLF_NK_WALL_TMS,
-                      hipabi.SLF_NK_EQUILIBRIUM_DENSITY, hipabi.SLF_NK_EQUILIBRIUM_VELOCITY)
+    ROUNDOFF_KINDS = tuple(k for k in range(32) if serves.BY_NAME['minimize_roundoff'].serves[-1] >> k & 1)
 
     @classmethod
     def check_module_desc(cls, kw):
         """Refuses, on the host and with a clear message, what the kernels of the chosen formulation do not cover
         (the library refuses the same at module creation)."""
         super(LBFluidSim, cls).check_module_desc(kw)
-        if kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
-            bad = [k for k in kw.get('type_kind', []) if k not in cls.ROUNDOFF_KINDS]
-            if bad:
-                raise NotImplementedError('--minimize_roundoff: fluid, bounce-back, TMS wall and equilibrium density / velocity nodes '
-                                          'only (node kinds %s are not covered: the reference\'s own regularized / Zou-He '
-                                          'expressions are inconsistent under the option, DESIGN.md)' % sorted(set(bad)))
+        serves.check(kw, ('minimize_roundoff',))
         if kw.get('entropic_equilibrium') and kw.get('model') != hipabi.SLF_ELBM:
             raise NotImplementedError('entropic_equilibrium needs model = elbm')
         if kw.get('model') == hipabi.SLF_ELBM:
             # what ELBM_relaxate (relaxation.mako:56-97) covers and this backend has fixtures for
             if any(float(x) != 0.0 for x in kw.get('mrt_rates', [])):
                 raise NotImplementedError('--model=elbm: MRT relaxation rates are set; the entropic collision has one rate')
-            if kw.get('regularized') or kw.get('subgrid'):
-                raise NotImplementedError('--model=elbm: --regularized / --subgrid belong to the BGK relaxation preamble, which '
-                                          'the entropic collision never runs')
-            if kw.get('simtype', hipabi.SLF_SIM_LBM) != hipabi.SLF_SIM_LBM:
-                raise NotImplementedError('--model=elbm: single-fluid simulations only (the Shan-Chen models use BGK)')
-            if kw.get('incompressible') == hipabi.SLF_DENSITY_ROUNDOFF:
-                raise NotImplementedError('--model=elbm: --minimize_roundoff stores f - w; the entropy needs the populations')
+            serves.check(kw, ('elbm',))
             if kw.get('incompressible') == hipabi.SLF_DENSITY_INCOMPRESSIBLE and kw.get('entropic_equilibrium'):
                 raise NotImplementedError('--model=elbm: --entropic_equilibrium (compressible product form) does not go with '
                                           '--incompressible')
-            if kw.get('has_force'):
-                raise NotImplementedError('--model=elbm: body forces under the entropic collision are not supported')
 
     def initial_conditions(self, runner):
         """f = feq(rho, v) on every copy of the distributions (reference lb_single.py:72-94)."""

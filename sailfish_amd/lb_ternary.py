@@ -4,7 +4,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from sailfish_amd import hipabi, subdomain_runner, sym
+from sailfish_amd import hipabi, serves, subdomain_runner, sym
 from sailfish_amd.lb_base import LBForcedSim, LBSim, ScalarField, VectorField
 from sailfish_amd.lb_binary import MacroKernels, SHAN_CHEN_POTENTIALS
 
@@ -122,17 +122,8 @@ class LBTernaryFluidShanChen(LBTernaryFluidBase, LBForcedSim):
     def fill_module_desc(self, kw):
         super(LBTernaryFluidShanChen, self).fill_module_desc(kw)
         c = self.config
-        if getattr(c, 'model', 'bgk') != 'bgk':
-            raise NotImplementedError('ternary Shan-Chen model: --model=%s is not implemented by the HIP backend; the BGK '
-                                      'collision only' % c.model)
-        if getattr(c, 'node_addressing', 'direct') != 'direct':
-            raise NotImplementedError('ternary Shan-Chen model: --node_addressing=indirect is not implemented by the HIP '
-                                      'backend')
-        for opt in ('minimize_roundoff', 'regularized', 'incompressible'):
-            if getattr(c, opt, False):
-                raise NotImplementedError('ternary Shan-Chen model: --%s is not implemented by the HIP backend' % opt)
-        if getattr(c, 'subgrid', 'none') not in ('none', None, ''):
-            raise NotImplementedError('ternary Shan-Chen model: --subgrid=%s is not implemented by the HIP backend' % c.subgrid)
+        serves.check(serves.config_fields(c, simtype=hipabi.SLF_SIM_SHAN_CHEN_TERNARY), ('regularized / subgrid', 'ternary Shan-Chen'),
+                     columns=serves.COLUMNS)
         G = self.constants()
         kw.update(lattice=self.grid.slf_id, simtype=hipabi.SLF_SIM_SHAN_CHEN_TERNARY,
                   tau=sym.relaxation_time(c.visc), visc=c.visc, incompressible=0,
@@ -142,12 +133,7 @@ class LBTernaryFluidShanChen(LBTernaryFluidBase, LBForcedSim):
     @classmethod
     def check_module_desc(cls, kw):
         super(LBTernaryFluidShanChen, cls).check_module_desc(kw)
-        plain = (hipabi.SLF_NK_FLUID, hipabi.SLF_NK_GHOST, hipabi.SLF_NK_UNUSED, hipabi.SLF_NK_PROPAGATION_ONLY,
-                 hipabi.SLF_NK_FULL_BB)
-        for kind in kw.get('type_kind', []):
-            if kind not in plain:
-                raise NotImplementedError('ternary Shan-Chen model: fluid and NTFullBBWall nodes only (node kind %d is not '
-                                          'implemented by the ternary kernels)' % kind)
+        serves.check(kw, ('ternary Shan-Chen',), always=True)
 
     def get_compute_kernels(self, runner, full_output, bulk):
         """[(macro kernel, [collide kernels])] for the primary (A->B) and the secondary (B->A) half step, with the

@@ -1,7 +1,7 @@
 // Walks the host logic of the C ABI (sailfish_amd/csrc/slf_bind.h) on the CPU and prints one line per case:
 //   section \t subject \t configuration \t try \t code \t message \t detail
 // tests/test_abi_bind.py builds it with AddressSanitizer and UBSan, runs it and compares the lines with
-// tests/golden/abi_binding.json.  Nothing here touches a GPU.
+// tests/golden/abi_binding.json and tests/golden/abi_support.tsv.  Nothing here touches a GPU.
 #include <stdio.h>
 
 #include <string>
@@ -69,7 +69,7 @@ slf_module_desc base_desc(int lattice, int access, int simtype, int model, int a
   slf_module_desc d = {};
   d.struct_size = sizeof(slf_module_desc);
   d.lattice = lattice; d.model = model; d.precision = 4; d.access_pattern = access;
-  d.lat_nx = 6; d.lat_ny = 5; d.lat_nz = lattice == SLF_D3Q19 ? 4 : 1;
+  d.lat_nx = 6; d.lat_ny = 5; d.lat_nz = lattice == SLF_D2Q9 ? 1 : 4;
   d.arr_nx = 8; d.arr_ny = 5; d.arr_nz = d.lat_nz;
   d.envelope = 1;
   d.relaxation_enabled = 1;
@@ -194,6 +194,99 @@ std::vector<Config> all_configs() {
   REFUSAL("sc3-potential", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.sc_potential = 2)
   REFUSAL("sc3-node-kind", SLF_D2Q9, SLF_AB, SLF_SIM_SHAN_CHEN_TERNARY, B, DIR, d.type_kind[4] = SLF_NK_HALF_BB)
 #undef REFUSAL
+  return out;
+}
+
+// The support matrix: every feature that restricts what a module combines it with (in its served base case) x every
+// option that can offend it, one at a time: the `cross` section, which answers with what the support table decides of a module.
+std::vector<Config> cross_configs() {
+  struct Change { std::string name; void (*apply)(slf_module_desc*); };
+  typedef slf_module_desc D;
+  const Change features[] = {
+    {"d2q9", [](D*) {}}, {"d3q19", [](D* d) { *d = base_desc(SLF_D3Q19, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); }},
+    {"d3q15", [](D* d) { *d = base_desc(SLF_D3Q15, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); }},
+    {"d3q27", [](D* d) { *d = base_desc(SLF_D3Q27, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); }},
+    {"accf-d2q9", [](D* d) { d->accel_field = 1; }},
+    {"accf-d3q19", [](D* d) { *d = base_desc(SLF_D3Q19, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); d->accel_field = 1; }},
+    {"sw", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; }},
+    {"sc2", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; }}, {"scs", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_SINGLE; }},
+    {"fe", [](D* d) { d->simtype = SLF_SIM_FREE_ENERGY; }}, {"sc3", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_TERNARY; }},
+    {"roundoff", [](D* d) { d->incompressible = SLF_DENSITY_ROUNDOFF; }}, {"elbm", [](D* d) { d->model = SLF_ELBM; }},
+    {"regularized", [](D* d) { d->regularized = 1; }},
+    {"subgrid", [](D* d) { d->subgrid = SLF_SUBGRID_LES_SMAGORINSKY; d->smagorinsky_const = 0.1; }},
+    {"tms", [](D* d) { d->n_types = 6; d->type_kind[5] = SLF_NK_WALL_TMS; }},
+  };
+  std::vector<Change> offenders = {
+    {"model-bgk", [](D* d) { d->model = SLF_BGK; for (double& r : d->mrt_rates) r = 0.0; }},
+    {"model-mrt", [](D* d) { d->model = SLF_MRT; for (int i = 0; i < 19; i++) d->mrt_rates[i] = 1.0 + 0.01 * i; }},
+    {"model-elbm", [](D* d) { d->model = SLF_ELBM; for (double& r : d->mrt_rates) r = 0.0; }},
+    {"simtype-lbm", [](D* d) { d->simtype = SLF_SIM_LBM; }}, {"simtype-sc2", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; }},
+    {"simtype-scs", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_SINGLE; }}, {"simtype-fe", [](D* d) { d->simtype = SLF_SIM_FREE_ENERGY; }},
+    {"simtype-sc3", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_TERNARY; }},
+    {"regularized", [](D* d) { d->regularized = 1; }},
+    {"subgrid", [](D* d) { d->subgrid = SLF_SUBGRID_LES_SMAGORINSKY; d->smagorinsky_const = 0.1; }},
+    {"density-compressible", [](D* d) { d->incompressible = SLF_DENSITY_COMPRESSIBLE; }},
+    {"density-incompressible", [](D* d) { d->incompressible = SLF_DENSITY_INCOMPRESSIBLE; }},
+    {"density-roundoff", [](D* d) { d->incompressible = SLF_DENSITY_ROUNDOFF; }},
+    {"indirect", [](D* d) { d->node_addressing = SLF_ADDR_INDIRECT; d->dist_stride = 100; d->fluid_only = 0; }},
+    {"edm", [](D* d) { d->force_implementation = SLF_FORCE_EDM; }},
+    {"force", [](D* d) { d->has_force = 1; d->accel[0] = 1e-5; }},
+    {"accel-field", [](D* d) { d->accel_field = 1; }},
+    {"shallow-water", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; }},
+    {"entropic-equilibrium", [](D* d) { d->entropic_equilibrium = 1; }},
+    {"access-ab", [](D* d) { d->access_pattern = SLF_AB; }}, {"access-aa", [](D* d) { d->access_pattern = SLF_AA; }},
+    {"fluid-only", [](D* d) { d->fluid_only = 1; }},
+  };
+  std::vector<Config> out;
+  for (const Change& f : features) {
+    for (int o = 0; o < (int)offenders.size() + slf::NK_COUNT; o++) {
+      slf_module_desc d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+      f.apply(&d);
+      std::string name;
+      if (o < (int)offenders.size()) {
+        offenders[o].apply(&d);
+        name = offenders[o].name;
+      } else {      // one more node type, of each kind
+        d.type_kind[d.n_types++] = o - (int)offenders.size();
+        name = "node-kind-" + num(o - (int)offenders.size());
+      }
+      out.push_back(Config{"x-" + f.name + "+" + name, d, {}, 0});
+    }
+  }
+  // malformed fields and double faults: which check answers first decides the code
+  const Change malformed[] = {
+    {"regularized+density-7", [](D* d) { d->regularized = 1; d->incompressible = 7; }},
+    {"elbm+density-negative", [](D* d) { d->model = SLF_ELBM; d->incompressible = -1; }},
+    {"d3q15+density-7", [](D* d) { *d = base_desc(SLF_D3Q15, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); d->incompressible = 7; }},
+    {"accf+density-7", [](D* d) { d->accel_field = 1; d->incompressible = 7; }},
+    {"sw+density-7", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; d->incompressible = 7; }},
+    {"sw+addressing-5", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; d->node_addressing = 5; }},
+    {"sw+model-7", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; d->model = 7; }},
+    {"sw+mrt+accel-field-2", [](D* d) { d->equilibrium = SLF_EQ_SHALLOW_WATER; d->gravity = 0.001; d->model = SLF_MRT; d->accel_field = 2; }},
+    {"accf+model-7", [](D* d) { d->accel_field = 1; d->model = 7; }},
+    {"fe+addressing-5", [](D* d) { d->simtype = SLF_SIM_FREE_ENERGY; d->node_addressing = 5; }},
+    {"sc3+addressing-5", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_TERNARY; d->node_addressing = 5; }},
+    {"fe+indirect+fluid-only", [](D* d) { d->simtype = SLF_SIM_FREE_ENERGY; d->node_addressing = SLF_ADDR_INDIRECT; d->dist_stride = 100; d->fluid_only = 1; }},
+    {"fe+density-7", [](D* d) { d->simtype = SLF_SIM_FREE_ENERGY; d->incompressible = 7; }},
+    {"sc2+mrt+tau", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; d->model = SLF_MRT; d->tau = 0.4; }},
+    {"sc2+mrt+tau-phi", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; d->model = SLF_MRT; d->tau_phi = 0.4; }},
+    {"sc2+node-kind+tau-phi", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; d->type_kind[4] = SLF_NK_HALF_BB; d->tau_phi = 0.4; }},
+    {"sc2+node-kind+entropic", [](D* d) { d->simtype = SLF_SIM_SHAN_CHEN_BINARY; d->type_kind[4] = SLF_NK_HALF_BB; d->entropic_equilibrium = 1; }},
+    {"elbm+force+size", [](D* d) { d->model = SLF_ELBM; d->has_force = 1; d->lat_nx = 1; }},
+    {"elbm+force+precision", [](D* d) { d->model = SLF_ELBM; d->has_force = 1; d->precision = 2; }},
+    {"regularized+mrt+subgrid-9", [](D* d) { d->regularized = 1; d->model = SLF_MRT; d->subgrid = 9; }},
+    {"regularized+simtype-9", [](D* d) { d->regularized = 1; d->simtype = 9; }},
+    {"roundoff+zouhe+entropic", [](D* d) { d->incompressible = SLF_DENSITY_ROUNDOFF; d->type_kind[4] = SLF_NK_ZOUHE_VELOCITY; d->entropic_equilibrium = 1; }},
+    {"tms+simtype-9", [](D* d) { d->n_types = 6; d->type_kind[5] = SLF_NK_WALL_TMS; d->simtype = 9; }},
+    {"tms+sc2+entropic", [](D* d) { d->n_types = 6; d->type_kind[5] = SLF_NK_WALL_TMS; d->simtype = SLF_SIM_SHAN_CHEN_BINARY; d->entropic_equilibrium = 1; }},
+    {"d3q27+node-kind-20", [](D* d) { *d = base_desc(SLF_D3Q27, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT); d->type_kind[4] = 20; }},
+    {"d3q15+mrt+access-2", [](D* d) { *d = base_desc(SLF_D3Q15, SLF_AB, SLF_SIM_LBM, SLF_MRT, SLF_ADDR_DIRECT); d->access_pattern = 2; }},
+  };
+  for (const Change& m : malformed) {
+    slf_module_desc d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, SLF_ADDR_DIRECT);
+    m.apply(&d);
+    out.push_back(Config{"m-" + m.name, d, {}, 0});
+  }
   return out;
 }
 
@@ -324,6 +417,20 @@ int main() {
     const char* err = "";
     c.code = slf::module_config(&c.desc, &c.cfg, &err);
     line("config", "-", c.name, "-", c.code, err, c.code ? "" : dump(c.cfg));
+  }
+  for (Config& c : cross_configs()) {
+    const char* err = "";
+    c.code = slf::module_config(&c.desc, &c.cfg, &err);
+    line("cross", "-", c.name, "-", c.code, err,
+         c.code ? "" : "variant=" + num(c.cfg.geo.variant) + " bc_level=" + num(c.cfg.geo.bc_level) + " block_x=" + num(c.cfg.block_x) +
+                           " has_force=" + num(c.cfg.phys.has_force));
+  }
+  // the support table as sailfish_amd/serves.py must hold it: name, position, per_node_only, the masks in the order of slf::Column
+  int position = 0;
+  for (const slf::Serves& row : slf::SERVES) {
+    std::string masks;
+    for (int col = 0; col < slf::N_COLUMNS; col++) masks += (col ? " " : "") + std::to_string(row.serves[col]);
+    line("serves", row.name, "-", "row" + num(position++), row.per_node_only, "", masks);
   }
   std::vector<std::string> names;
   for (const slf::KernelRow& r : slf::KERNEL_TABLE) {

@@ -5,20 +5,13 @@
 
 #include <string>
 
+#include "bind_desc.h"
 #include "slf_bind.h"
 
 namespace {
 
 slf_module_desc base_desc(int lattice) {
-  slf_module_desc d = {};
-  d.struct_size = sizeof(slf_module_desc);
-  d.lattice = lattice; d.model = SLF_BGK; d.precision = 4; d.access_pattern = SLF_AB;
-  d.lat_nx = 6; d.lat_ny = 5; d.lat_nz = lattice == SLF_D2Q9 ? 1 : 4;
-  d.arr_nx = 8; d.arr_ny = 5; d.arr_nz = d.lat_nz;
-  d.envelope = 1;
-  d.relaxation_enabled = 1;
-  d.tau = 0.8; d.visc = 0.1;
-  d.fluid_only = 1;
+  slf_module_desc d = bind_fluid_only_desc(lattice);
   d.accel_field = (lattice == SLF_D2Q9 || lattice == SLF_D3Q19) ? 1 : 0;
   return d;
 }

@@ -10,26 +10,14 @@
 #include <set>
 #include <string>
 
+#include "bind_desc.h"
 #include "slf_bind.h"
 
 namespace {
 
 slf_module_desc base_desc() {
-  slf_module_desc d = {};
-  d.struct_size = sizeof(slf_module_desc);
-  d.lattice = SLF_D2Q9; d.model = SLF_BGK; d.precision = 4; d.access_pattern = SLF_AB;
-  d.lat_nx = 6; d.lat_ny = 5; d.lat_nz = 1;
-  d.arr_nx = 8; d.arr_ny = 5; d.arr_nz = 1;
-  d.envelope = 1;
-  d.relaxation_enabled = 1;
-  d.tau = 0.8; d.visc = 0.1;
-  d.nt_type_mask = 7; d.nt_misc_shift = 3;
-  d.n_types = 7;
-  for (int i = 0; i < 6; i++) d.type_kind[i] = i;      // fluid, ghost, unused, propagation-only, full-way, half-way
-  d.type_kind[6] = SLF_NK_SLIP;
-  d.tau_phi = 0.9; d.tau_theta = 1.1;
-  d.fe_Gamma = 0.5; d.fe_kappa = 0.04; d.fe_A = 0.03; d.fe_tau_a = 0.9; d.fe_tau_b = 0.7; d.bc_wall_grad_order = 1;
-  d.entropy_tolerance = 1e-6; d.alpha_tolerance = 1e-10;
+  slf_module_desc d = bind_base_desc(SLF_D2Q9);
+  d.type_kind[d.n_types++] = SLF_NK_SLIP;
   d.equilibrium = SLF_EQ_SHALLOW_WATER;
   d.gravity = 0.05;
   return d;

@@ -1,33 +1,32 @@
 """The host logic of the C ABI that needs no GPU (sailfish_amd/csrc/slf_bind.h): module descriptors into module
 configurations, kernel names into rows of the kernel table, argument lists into launch arguments, and the index
 arithmetic of the reference's face kernels.  tests/abi_bind_main.cpp walks all of it as a stand-alone program built
-with AddressSanitizer and UBSan; its output must equal tests/golden/abi_binding.json, recorded from the chain of
-string compares and the switches this table replaced.  Nothing is loaded into Python.
+with AddressSanitizer and UBSan.  Nothing is loaded into Python.  Its output must equal two records:
 
-    python tests/test_abi_bind.py --record      rewrites the fixture from the present code
+tests/golden/abi_binding.json: the sections resolve, bind and face, recorded from the chain of string compares and the
+switches the kernel table replaced (its `config` section is the ladders' and is no longer read: the next record drops it);
+
+tests/golden/abi_support.tsv, one line of text per case: the section `config`, the section `cross` (every feature x every
+option that can offend it, malformed fields and double faults; recorded first from the refusal ladders the support table
+replaced, whose codes and details it keeps) and the section `serves` (the rows of the support table, which
+tests/test_serves.py compares with sailfish_amd/serves.py).
+
+    python tests/test_abi_bind.py --record [json] [tsv]      rewrites the named records (both if none) from the present code
 """
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'sailfish_amd', 'csrc')
-MAIN = os.path.join(ROOT, 'tests', 'abi_bind_main.cpp')
+sys.path.insert(0, ROOT)      # (run as a script, --record)
+from tests import _bind  # noqa: E402
 FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'abi_binding.json')
-ROCM_INCLUDE = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')
+SUPPORT = os.path.join(ROOT, 'tests', 'golden', 'abi_support.tsv')
+JSON_SECTIONS = ('resolve', 'bind', 'face')
 
 
 def run_program(workdir):
-    exe = os.path.join(str(workdir), 'abi_bind')
-    # the sanitizers' runtimes are linked into the program: it does not depend on what else the process environment loads
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-D__HIP_PLATFORM_AMD__', '-I', ROCM_INCLUDE,
-                           '-I', CSRC, '-o', exe, MAIN])
-    env = {k: v for k, v in os.environ.items() if k not in ('SLF_BC_LEVEL', 'SLF_VARIANT', 'SLF_BLOCK_X')}
-    done = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
-    assert done.returncode == 0, 'abi_bind_main failed (%d):\n%s' % (done.returncode, done.stderr[-4000:])
-    return done.stdout
+    return _bind.build_and_run('abi_bind_main.cpp', workdir)
 
 
 def compact(text):
@@ -66,31 +65,47 @@ def expand(fix):
     return out
 
 
+def split(text):
+    """The program's lines: those of abi_binding.json, in its compact form, and those of abi_support.tsv, as they are."""
+    lines = text.splitlines()
+    return (compact('\n'.join(ln for ln in lines if ln.split('\t')[0] in JSON_SECTIONS)),
+            [ln for ln in lines if ln.split('\t')[0] not in JSON_SECTIONS])
+
+
 def test_binding_equals_the_recorded_behaviour(tmp_path):
-    got = compact(run_program(tmp_path))
+    got, got_support = split(run_program(tmp_path))
     want = json.load(open(FIXTURE))
-    if got != want:
-        g, w = expand(got), expand(want)
-        assert sorted(g) == sorted(w), ('cases differ', sorted(set(g) ^ set(w))[:10])
-        wrong = [(k, g[k], w[k]) for k in sorted(w) if g[k] != w[k]]
-        assert not wrong, ('%d cases differ; (case, got, recorded):' % len(wrong), wrong[:5])
-    assert got == want
-    # the matrix is the one the fixture was recorded for: nothing fell out of it unnoticed
-    w = expand(want)
-    sections = {s: sum(1 for k in w if k[0] == s) for s in ('config', 'resolve', 'bind', 'face')}
+    want['cases'] = {s: want['cases'][s] for s in JSON_SECTIONS}
+    g, w = expand(got), expand(want)
+    assert sorted(g) == sorted(w), ('cases differ', sorted(set(g) ^ set(w))[:10])
+    wrong = [(k, g[k], w[k]) for k in sorted(w) if g[k] != w[k]]
+    assert not wrong, ('%d cases differ; (case, got, recorded):' % len(wrong), wrong[:5])
+    want_support = open(SUPPORT).read().splitlines()
+    assert len(got_support) == len(want_support), (len(got_support), len(want_support))
+    wrong = [(a, b) for a, b in zip(got_support, want_support) if a != b]
+    assert not wrong, ('%d lines differ; (got, recorded):' % len(wrong), wrong[:5])
+    # the matrix is the one the records were made for: nothing fell out of it unnoticed
+    sections = {s: sum(1 for k in w if k[0] == s) for s in JSON_SECTIONS}
+    sections.update({s: sum(1 for ln in want_support if ln.startswith(s + '\t')) for s in ('config', 'cross', 'serves')})
     assert sections['config'] >= 48 + 40 and sections['resolve'] >= 1500 and sections['bind'] >= 6000 and sections['face'] >= 100, sections
-    refusals = set(m for (s, _, _, _), (code, m, _) in w.items() if s == 'config' and code)
+    assert sections['cross'] >= 16 * 39 + 20 and sections['serves'] >= 11, sections
+    refusals = set(ln.split('\t')[5] for ln in want_support if ln.startswith('config\t') and ln.split('\t')[4] != '0')
     assert len(refusals) >= 40, len(refusals)
     assert not any(k[3] == 'no-signature' for k in w)
 
 
 if __name__ == '__main__':
-    if sys.argv[1:] != ['--record']:
+    if sys.argv[1:2] != ['--record'] or set(sys.argv[2:]) - {'json', 'tsv'}:
         sys.exit(__doc__)
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        fix = compact(run_program(tmp))
-    with open(FIXTURE, 'w') as fh:
-        json.dump(fix, fh, separators=(',', ':'), sort_keys=True)
-        fh.write('\n')
-    print('%s: %d bytes' % (FIXTURE, os.path.getsize(FIXTURE)))
+        fix, support = split(run_program(tmp))
+    if 'json' in sys.argv[2:] or not sys.argv[2:]:
+        with open(FIXTURE, 'w') as fh:
+            json.dump(fix, fh, separators=(',', ':'), sort_keys=True)
+            fh.write('\n')
+        print('%s: %d bytes' % (FIXTURE, os.path.getsize(FIXTURE)))
+    if 'tsv' in sys.argv[2:] or not sys.argv[2:]:
+        with open(SUPPORT, 'w') as fh:
+            fh.write('\n'.join(support) + '\n')
+        print('%s: %d lines, %d bytes' % (SUPPORT, len(support), os.path.getsize(SUPPORT)))

@@ -384,8 +384,8 @@ def test_refusals(backend):
     for i, r in enumerate(sym.mrt_rates(sym.D3Q19, 0.01)):
         d.mrt_rates[i] = r
     refused(d, 'MRT relaxation rates')
-    refused(_desc(regularized=True), 'regularized / subgrid: single-fluid BGK')
-    refused(_desc(subgrid=True), 'regularized / subgrid: single-fluid BGK')
+    refused(_desc(regularized=True), 'regularized / subgrid: --model=elbm is not served; --model=bgk only')
+    refused(_desc(subgrid=True), 'regularized / subgrid: --model=elbm is not served; --model=bgk only')
     for simtype in (hipabi.SLF_SIM_SHAN_CHEN_BINARY, hipabi.SLF_SIM_SHAN_CHEN_SINGLE):
         d = _desc()
         d.simtype = simtype

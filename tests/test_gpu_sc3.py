@@ -311,7 +311,7 @@ def test_body_force_of_lattice_two_is_set_through_the_abi():
 
 
 MODULE_REFUSALS = [
-    (dict(model=hipabi.SLF_MRT), 'model other than bgk'),
+    (dict(model=hipabi.SLF_MRT), 'ternary Shan-Chen: --model=mrt'),
     (dict(node_addressing=hipabi.SLF_ADDR_INDIRECT, dist_stride=4096), 'node_addressing=indirect'),
     (dict(type_kind=[hipabi.SLF_NK_FLUID, hipabi.SLF_NK_HALF_BB]), 'NTFullBBWall'),
     (dict(type_kind=[hipabi.SLF_NK_FLUID, hipabi.SLF_NK_EQUILIBRIUM_DENSITY]), 'NTFullBBWall'),

@@ -4,7 +4,6 @@ full-output sweep; what is not served is refused by name; positions travel with 
 ibm_cylinder.py loads.  Through a recording backend (tests/_ibm_backend.py): no GPU."""
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +14,7 @@ from sailfish_amd import hipabi
 from sailfish_amd.lb_single import LBIBMFluidSim, Particle
 from sailfish_amd.node_type import DynamicValue
 from sailfish_amd.sym import S
-from tests import _host, _ibm, _ibm_backend
+from tests import _bind, _host, _ibm, _ibm_backend
 from tests.test_accf_host import runners_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,13 +211,7 @@ def test_reference_ibm_cylinder_loads_unchanged():
 def test_bind_program_walks_the_argument_checks(tmp_path):
     """tests/ibm_bind_main.cpp against csrc/slf_bind.h, built with the address and undefined-behaviour sanitizers and run as a
     child process: nothing is loaded into Python."""
-    exe = str(tmp_path / 'ibm_bind')
-    rocm = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-D__HIP_PLATFORM_AMD__', '-I', rocm, '-I', CSRC,
-                           '-o', exe, os.path.join(ROOT, 'tests', 'ibm_bind_main.cpp')])
-    env = {k: v for k, v in os.environ.items() if k not in ('SLF_BC_LEVEL', 'SLF_VARIANT', 'SLF_BLOCK_X')}
-    done = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    done = _bind.run('ibm_bind_main.cpp', tmp_path)
     assert done.returncode == 0, done.stderr[-4000:]
     rows = {ln.split('\t')[0]: ln.split('\t') for ln in done.stdout.splitlines()}
     OK, INVALID, UNSUPPORTED = 0, 1, 3

@@ -4,26 +4,19 @@ descriptor with both members zero gives what it gave before, and which kernel na
 tests/sw_bind_main.cpp is built stand-alone, with the address and undefined-behaviour sanitizers, and run directly."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from tests import _bind
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'sailfish_amd', 'csrc')
-ROCM_INCLUDE = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')
 OK, INVALID, UNSUPPORTED, NOT_FOUND = 0, 1, 3, 4
 
 
 @pytest.fixture(scope='module')
 def bind_lines(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp('sw_bind')), 'sw_bind')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-D__HIP_PLATFORM_AMD__', '-I', ROCM_INCLUDE,
-                           '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'sw_bind_main.cpp')])
-    env = {k: v for k, v in os.environ.items() if k not in ('SLF_BC_LEVEL', 'SLF_VARIANT', 'SLF_BLOCK_X')}
-    done = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
-    assert done.returncode == 0, done.stderr[-4000:]
-    return [ln.split('\t') for ln in done.stdout.splitlines()]
+    return _bind.lines('sw_bind_main.cpp', tmp_path_factory.mktemp('sw_bind'))
 
 
 # subject -> (has_force, accel_field, block_x): a 4-node row is one wave; a 1000-node row one workgroup of 1024 threads, of
@@ -119,5 +112,6 @@ def test_header_binding_and_predicate_in_step():
     plain = hipabi.make_desc()
     assert plain.equilibrium == 0 and plain.gravity == 0.0 and plain.struct_size == 760
     bind = open(os.path.join(CSRC, 'slf_bind.h')).read()
-    assert bind.index('inline const char* lat_refusal') < bind.index('inline const char* accf_refusal') < \
-        bind.index('inline const char* sw_refusal') < bind.index('inline int module_config')
+    # the rows that serve the feature are in the support table, in front of module_config() which walks it
+    assert bind.index('{"shallow water", SLF_HAS(') < bind.index('{"accel_field", SLF_HAS(') < bind.index('SLF_LAT_ROW("D3Q15", ') < \
+        bind.index('inline const char* serves_conflict') < bind.index('inline int module_config')

@@ -4,26 +4,20 @@ child process: nothing is loaded into Python."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
 from sailfish_amd import hipabi
+from tests import _bind
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'sailfish_amd', 'csrc')
-ROCM_INCLUDE = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')
 OK, INVALID, UNSUPPORTED = 0, 1, 3
 
 
 @pytest.fixture(scope='module')
 def rows(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp('thermal_bind')), 'thermal_bind')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-D__HIP_PLATFORM_AMD__', '-I', ROCM_INCLUDE,
-                           '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'thermal_bind_main.cpp')])
-    env = {k: v for k, v in os.environ.items() if k not in ('SLF_BC_LEVEL', 'SLF_VARIANT', 'SLF_BLOCK_X')}
-    done = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    done = _bind.run('thermal_bind_main.cpp', tmp_path_factory.mktemp('thermal_bind'))
     assert done.returncode == 0, done.stderr[-4000:]
     return {ln.split('\t')[0]: ln.split('\t') for ln in done.stdout.splitlines()}
 

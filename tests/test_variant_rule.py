@@ -9,19 +9,15 @@ import subprocess
 
 import pytest
 
+from tests import _bind
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'sailfish_amd', 'csrc')
-ROCM_INCLUDE = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include')
 
 
 @pytest.fixture(scope='module')
 def rule_run(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp('variant_rule')), 'variant_rule')
-    subprocess.check_call(['g++', '-std=c++20', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-static-libasan', '-static-libubsan', '-Wall', '-D__HIP_PLATFORM_AMD__', '-I', ROCM_INCLUDE,
-                           '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'variant_rule_main.cpp')])
-    env = {k: v for k, v in os.environ.items() if k not in ('SLF_BC_LEVEL', 'SLF_VARIANT', 'SLF_BLOCK_X')}
-    done = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    done = _bind.run('variant_rule_main.cpp', tmp_path_factory.mktemp('variant_rule'), std='c++20')
     return done.returncode, [ln.split('\t') for ln in done.stdout.splitlines()], done.stderr
 
 
