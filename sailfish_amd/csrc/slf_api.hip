@@ -78,9 +78,7 @@ struct slf_kernel {
   int needs_iteration;
   uint32_t iteration;
   bool bound;
-  int pair_rows = 0, pair_zc = 0;   // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); 0: single steps
-  int pair_prefetch = 0;            // ... with this load path in phase A (SLF_PAIR_PREFETCH)
-  int pair_xcd_log2 = 0, pair_march = 0;      // ... this strip placement and row order (SLF_PAIR_XCD_LOG2, SLF_PAIR_MARCH)
+  slf::PairKnobs pair = {};    // slf_kernel_set_pair: every launch advances two steps (slf_pair.hip); rows == 0: single steps
 };
 
 static hipStream_t native(slf_stream* s) { return s ? s->s : (hipStream_t)0; }
@@ -1126,27 +1124,20 @@ int slf_module_poll_invalid(slf_module* m, slf_stream* stream, int32_t out[4]) {
   return SLF_OK;
 }
 
-static int check_xface_buffers(const slf_module* m, void* send_low, void* send_high, void* recv_low, void* recv_high) {
-  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
-  if (send_low || send_high || recv_low || recv_high) {
-    const slf::Geometry& g = m->geo;
-    if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(lat_name(m)) + ": x-face buffers are not implemented on this lattice (D3Q19 only)");
-    if (m->sel.lattice != 1 || g.indirect || m->sc.enabled || m->fe.enabled || m->sc3.enabled || !(g.variant & 8))
-      return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: D3Q19 single-fluid modules with direct addressing (whole-row kernels) only");
-    if (g.wrap[0]) return fail(SLF_ERR_INVALID, "x-face buffers make no sense with x wrapped inside the sweep");
-    if (g.lat_nx - 2 > 1024) return fail(SLF_ERR_UNSUPPORTED, "x-face buffers: rows of at most 1024 nodes");
-    if ((send_low == nullptr) != (recv_low == nullptr) || (send_high == nullptr) != (recv_high == nullptr))
-      return fail(SLF_ERR_INVALID, "a connected face needs both its send and its receive buffer");
-  }
-  return SLF_OK;
+// The four pointers of a module's x-face buffers (set < 0) or of its plane set `set` (0 / 1: lattice, 2: densities), in the
+// order send low, send high, receive low, receive high (checked by slf_bind.h part (f)).
+static void store_xface(slf_module* m, int set, void* const xf[4]) {
+  void** send = set < 0 ? m->xsend : m->sc_send[set];
+  void** recv = set < 0 ? m->xrecv : m->sc_recv[set];
+  send[0] = xf[0]; send[1] = xf[1];
+  recv[0] = xf[2]; recv[1] = xf[3];
 }
 
 int slf_module_set_xface_buffers(slf_module* m, void* send_low, void* send_high, void* recv_low, void* recv_high) {
-  if (int e = check_xface_buffers(m, send_low, send_high, recv_low, recv_high)) return e;
-  m->xsend[0] = send_low;
-  m->xsend[1] = send_high;
-  m->xrecv[0] = recv_low;
-  m->xrecv[1] = recv_high;
+  void* const xf[4] = {send_low, send_high, recv_low, recv_high};
+  std::string why;
+  if (int rc = slf::xface_buffers_check(m, xf, &why)) return fail(rc, why);
+  store_xface(m, -1, xf);
   return SLF_OK;
 }
 
@@ -1160,34 +1151,12 @@ static void sc_planes_of(const slf_module* m, slf::SweepArgs& a) {
   }
 }
 
-static int check_xface_planes(const slf_module* m, int32_t which, void* send_low, void* send_high, void* recv_low,
-                              void* recv_high) {
-  if (!m) return fail(SLF_ERR_INVALID, "module is NULL");
-  if (which < 0 || which > 2) return fail(SLF_ERR_INVALID, "x-face planes: 0 / 1 = populations of lattice 0 / 1, 2 = densities");
-  if (send_low || send_high || recv_low || recv_high) {
-    const slf::Geometry& g = m->geo;
-    if (m->sc3.enabled)
-      return fail(SLF_ERR_UNSUPPORTED, "x-face planes: not implemented for simtype = SLF_SIM_SHAN_CHEN_TERNARY (the planes carry two "
-                                       "lattices and two density fields); connected x faces go through ghost columns and index lists");
-    if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string(lat_name(m)) + ": x-face planes are not implemented on this lattice (D3Q19 only)");
-    if (m->sel.lattice != 1 || g.indirect || !m->sc.enabled || !(g.variant & 8))
-      return fail(SLF_ERR_UNSUPPORTED, "x-face planes: D3Q19 Shan-Chen modules with direct addressing (whole-row kernels)");
-    if (m->sc.enabled == 2 && which == 1) return fail(SLF_ERR_INVALID, "x-face planes: the single-component model has one lattice");
-    if (g.wrap[0]) return fail(SLF_ERR_INVALID, "x-face planes make no sense with x wrapped inside the sweep");
-    if (g.lat_nx - 2 > 1024 || g.lat_nx - 2 < 2) return fail(SLF_ERR_UNSUPPORTED, "x-face planes: rows of 2 .. 1024 nodes");
-    if ((send_low == nullptr) != (recv_low == nullptr) || (send_high == nullptr) != (recv_high == nullptr))
-      return fail(SLF_ERR_INVALID, "a connected face needs both its send and its receive plane");
-  }
-  return SLF_OK;
-}
-
 int slf_module_set_xface_planes(slf_module* m, int32_t which, void* send_low, void* send_high, void* recv_low,
                                 void* recv_high) {
-  if (int e = check_xface_planes(m, which, send_low, send_high, recv_low, recv_high)) return e;
-  m->sc_send[which][0] = send_low;
-  m->sc_send[which][1] = send_high;
-  m->sc_recv[which][0] = recv_low;
-  m->sc_recv[which][1] = recv_high;
+  void* const xf[4] = {send_low, send_high, recv_low, recv_high};
+  std::string why;
+  if (int rc = slf::xface_planes_check(m, which, xf, &why)) return fail(rc, why);
+  store_xface(m, which, xf);
   return SLF_OK;
 }
 
@@ -1405,40 +1374,16 @@ int slf_kernel_destroy(slf_kernel* k) {
   return SLF_OK;
 }
 
-// CollideAndPropagateResident: what its integer arguments (options, steps, tile x, tile y, halo) and arrays must satisfy
-static int check_resident_args(const slf_module* m, const slf::BoundArgs& b, int needs_iteration) {
-  const slf::SweepArgs& a = b.sweep;      // dist_in / dist_in2: source a / b, dist_out / dist_out2: destination a / b
-  const bool aa = m->access_pattern == SLF_AA;
-  const int steps = (int)b.ints[1], tx = (int)b.ints[2], ty = (int)b.ints[3], halo = (int)b.ints[4];
-  if (!needs_iteration) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident needs the iteration argument (its first step)");
-  if (steps < 1 || tx < 1 || ty < 1 || halo < 1) return fail(SLF_ERR_INVALID, "steps, tile and halo must be positive");
-  if (!a.dist_in || !a.dist_out || (!aa && (!a.dist_in2 || !a.dist_out2)))
-    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination arrays (both copies of the two-copy pattern)");
-  if (a.dist_in == a.dist_out || (!aa && a.dist_in2 == a.dist_out2))
-    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination must be different buffers");
-  // the halo that `steps` steps need depends on the parity of the first one: the worse of the two must fit
-  const int need = std::max(slf::resident_halo(aa, 0, steps), slf::resident_halo(aa, 1, steps));
-  if (halo < need) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: halo too small for this many steps");
-  const long long nw = (long long)(tx + 2 * halo) * (long long)(ty + 2 * halo);
-  if (nw > 2 * 1024) return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window larger than 2048 nodes");
-  const int q = 9;
-  // the window (dynamic LDS) + the kernel's own tables (static: the list of a window's boundary-condition nodes,
-  // slf_resident.hip) share the 160 KiB of a workgroup
-  if (slf::resident_lds_bytes(q, m->sel.precision, aa, tx + 2 * halo, ty + 2 * halo) + 4352 > 160 * 1024)
-    return fail(SLF_ERR_INVALID, "CollideAndPropagateResident: window does not fit the 160 KiB of LDS");
-  return SLF_OK;
-}
-
 int slf_kernel_set_args(slf_kernel* k, const char* fmt, const void* const* argv, int argc, int needs_iteration) {
   if (!k || !fmt || (!argv && argc > 0)) return fail(SLF_ERR_INVALID, "NULL argument");
   slf::BoundArgs b;
   std::string why;
   if (int rc = slf::bind(*k->mod, *k->row, fmt, argv, argc, &b, &why)) return fail(rc, why);
   if (k->kind == slf::KK_RESIDENT) {
-    if (int rc = check_resident_args(k->mod, b, needs_iteration)) return rc;
+    if (int rc = slf::resident_check(*k->mod, b, needs_iteration, &why)) return fail(rc, why);
   }
   k->args = b;
-  k->pair_rows = k->pair_zc = 0;     // new arguments: slf_kernel_set_pair has to look at them again
+  k->pair = {};     // new arguments: slf_kernel_set_pair has to look at them again
   k->needs_iteration = needs_iteration;
   k->bound = true;
   if (b.build_slots) {
@@ -1458,61 +1403,45 @@ int slf_kernel_set_iteration(slf_kernel* k, uint32_t iteration) {
 
 namespace {
 
-// What the sweep cases of slf_kernel_launch share.  Each returns SLF_OK or the failure it has recorded.
-
-// where and how a sweep runs: the propagation step of this launch, from the module's access pattern and the kernel's
-// iteration, and the rows [y0, y1) x [z0, z1): the region, or all real nodes (whole_box: the kernel takes no region)
-struct SweepShape {
-  slf::Prop prop;
-  int y0, y1, z0, z1;
-};
-int sweep_shape(const slf_kernel* k, const slf_region* region, bool whole_box, SweepShape* sh) {
-  const slf::Geometry& g = k->mod->geo;
-  sh->prop = slf::PROP_AB;
-  if (k->mod->access_pattern == SLF_AA) {
-    if (!k->needs_iteration) return fail(SLF_ERR_INVALID, "AA kernels need the iteration argument");
-    sh->prop = (k->iteration & 1u) ? slf::PROP_AA_ODD : slf::PROP_AA_EVEN;
-  }
-  sh->y0 = 1; sh->y1 = g.lat_ny - 1; sh->z0 = 1; sh->z1 = g.lat_nz - 1;
-  if (g.dim == 2) { sh->z0 = 0; sh->z1 = 1; }
-  if (region && !whole_box) {
-    sh->y0 = region->y0; sh->y1 = region->y1;
-    if (g.dim == 3) { sh->z0 = region->z0; sh->z1 = region->z1; }
-    if (sh->y0 < 1 || sh->y1 > g.lat_ny - 1 || sh->y0 > sh->y1 ||
-        (g.dim == 3 && (sh->z0 < 1 || sh->z1 > g.lat_nz - 1 || sh->z0 > sh->z1)))
-      return fail(SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
-  }
-  return SLF_OK;
-}
-
-// the module's tables into the launch arguments; the bound ones (map, options, ...) are in `a` by now
-int sweep_common(const slf_kernel* k, slf::SweepArgs& a) {
-  a.node_params = k->mod->node_params;
-  a.status = k->mod->status;
-  if (k->mod->sel.general && !a.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
-  return SLF_OK;
-}
-
-int nodes_given(const slf_kernel* k) {
-  if (k->mod->geo.indirect && !k->args.sweep.nodes) return fail(SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
-  return SLF_OK;
-}
-
-// the launch arguments of a pair sweep (slf_kernel_set_pair) from the bound arguments of a CollideAndPropagate kernel
-void pair_args(const slf_kernel* k, slf::SweepArgs& a) {
+// The launch arguments of a kernel: the bound ones, then the module state that may have changed since (the one place that
+// copies it).  The single-fluid sweeps take the x-face buffers, the row classes, the field and the slot table (built when
+// the arguments were bound, slf_kernel_set_args: a launch may be part of a graph capture); the Shan-Chen kinds the planes.
+slf::SweepArgs launch_args(const slf_kernel* k) {
   const slf_module* m = k->mod;
-  const slf::SweepArgs& b = k->args.sweep;
-  a.nodes = b.nodes;
-  a.map = b.map;
-  a.dist_in = b.dist_in;
-  a.dist_out = b.dist_out;
+  slf::SweepArgs a = k->args.sweep;
   a.node_params = m->node_params;
   a.status = m->status;
-  a.options = b.options;
-  for (int f = 0; f < 2; f++) {
-    a.xsend[f] = m->xsend[f];
-    a.xrecv[f] = m->xrecv[f];
+  if (k->kind == slf::KK_COLLIDE_AND_PROPAGATE || k->kind == slf::KK_COMPUTE_MACRO) {
+    for (int f = 0; f < 2; f++) {
+      a.xsend[f] = m->xsend[f];
+      a.xrecv[f] = m->xrecv[f];
+    }
+    a.rows = m->rows.map ? &m->rows : nullptr;
+    if (k->kind == slf::KK_COLLIDE_AND_PROPAGATE) {
+      if (m->phys.accel_field) a.accf = m->accf;
+      if (m->geo.indirect && m->slots.nodes == a.nodes) a.slots = &m->slots;
+    }
+  } else if (m->sc.enabled) {
+    sc_planes_of(m, a);
   }
+  return a;
+}
+
+// what a pair sweep (slf_kernel_set_pair) reads of them
+slf::SweepArgs pair_args(const slf::SweepArgs& a) {
+  slf::SweepArgs p = {};
+  p.nodes = a.nodes;
+  p.map = a.map;
+  p.dist_in = a.dist_in;
+  p.dist_out = a.dist_out;
+  p.node_params = a.node_params;
+  p.status = a.status;
+  p.options = a.options;
+  for (int f = 0; f < 2; f++) {
+    p.xsend[f] = a.xsend[f];
+    p.xrecv[f] = a.xrecv[f];
+  }
+  return p;
 }
 
 }  // namespace
@@ -1525,8 +1454,6 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
   if (rows_per_strip < 0 || planes_per_chunk < 0) return fail(SLF_ERR_INVALID, "pair sweep: negative strip / chunk size");
   const slf_module* m = k->mod;
   if (on_lat(m)) return fail(SLF_ERR_UNSUPPORTED, std::string("pair sweep: not implemented on ") + lat_name(m) + " (D3Q19, single precision, BGK modules only)");
-  const int rows = rows_per_strip ? rows_per_strip : slf::pair_default_rows(m->geo);
-  const int zc = planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk(m->geo);
   // The knobs of the kernel, read here, per kernel object (unset or empty: the default; not a small non-negative integer:
   // -1, which pair_refusal names).  SLF_PAIR_PREFETCH: the load path of phase A (0: synchronous); SLF_PAIR_XCD_LOG2:
   // neighbouring strips on one XCD, at most 1 << this each (0: off); SLF_PAIR_MARCH: 1 = odd strips walk downwards
@@ -1537,20 +1464,15 @@ int slf_kernel_set_pair(slf_kernel* k, int rows_per_strip, int planes_per_chunk)
     const long v = strtol(e, &end, 10);
     return (end && !*end && v >= 0 && v < 1000) ? (int)v : -1;
   };
-  const int prefetch = knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch());
-  const int xcd_log2 = knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2());
-  const int march = knob("SLF_PAIR_MARCH", slf::pair_default_march());
+  const slf::PairKnobs knobs = {rows_per_strip ? rows_per_strip : slf::pair_default_rows(m->geo),
+                                planes_per_chunk ? planes_per_chunk : slf::pair_default_zchunk(m->geo),
+                                knob("SLF_PAIR_PREFETCH", slf::pair_default_prefetch()),
+                                knob("SLF_PAIR_XCD_LOG2", slf::pair_default_xcd_log2()), knob("SLF_PAIR_MARCH", slf::pair_default_march())};
   if (m->sc.enabled || m->fe.enabled || m->sc3.enabled || m->sel.lattice != SLF_D3Q19 || k->args.alpha_arg)
     return fail(SLF_ERR_UNSUPPORTED, "pair sweep: D3Q19, single precision, BGK modules only");
-  slf::SweepArgs a = {};
-  pair_args(k, a);
-  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, a, rows, zc, prefetch, xcd_log2, march))
+  if (const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, m->geo, m->phys, pair_args(launch_args(k)), knobs))
     return fail(SLF_ERR_UNSUPPORTED, why);
-  k->pair_rows = rows;
-  k->pair_zc = zc;
-  k->pair_prefetch = prefetch;
-  k->pair_xcd_log2 = xcd_log2;
-  k->pair_march = march;
+  k->pair = knobs;
   return SLF_OK;
 }
 
@@ -1564,113 +1486,66 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
   SLF_HIP(hipSetDevice(m->ctx->device));   // several contexts may live in one process (one per GPU): launch on ours
   hipStream_t s = native(stream);
   hipError_t e = hipSuccess;
-  slf::SweepArgs a = b.sweep;     // the sweeps: the bound arguments, then the module state that may have changed since
-  SweepShape sh;
-  switch (kk) {
-    case slf::KK_COLLIDE_AND_PROPAGATE:
-    case slf::KK_COMPUTE_MACRO: {
-      if (k->pair_rows) {
-        // two steps per launch: whatever has changed since slf_kernel_set_pair accepted (a body force, face buffers)
-        // is an error here, never a quiet single step
-        slf::SweepArgs pa = {};
-        pair_args(k, pa);
-        if (region) return fail(SLF_ERR_UNSUPPORTED, "pair sweep: whole-box launches only");
-        if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc, k->pair_prefetch,
-                                    k->pair_xcd_log2, k->pair_march, s, &e)) {
-          const char* why = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair_rows, k->pair_zc,
-                                              k->pair_prefetch, k->pair_xcd_log2, k->pair_march);
-          return fail(SLF_ERR_UNSUPPORTED, why ? why : "pair sweep: no kernel for this strip size");
-        }
-        break;
-      }
-      for (int f = 0; f < 2; f++) {
-        a.xsend[f] = m->xsend[f];
-        a.xrecv[f] = m->xrecv[f];
-      }
-      a.rows = m->rows.map ? &m->rows : nullptr;
-      if (m->phys.accel_field && kk == slf::KK_COLLIDE_AND_PROPAGATE) {
-        if (!m->accf)
-          return fail(SLF_ERR_INVALID, "CollideAndPropagate: the module was created with accel_field, but no field is set "
-                                       "(slf_module_set_accel_field)");
-        a.accf = m->accf;
-      }
-      if (int rc = sweep_common(k, a)) return rc;
-      if (int rc = nodes_given(k)) return rc;
-      // (the slot table is built when the arguments are bound, slf_kernel_set_args: a launch may be part of a graph capture)
-      if (g.indirect && kk == slf::KK_COLLIDE_AND_PROPAGATE && m->slots.nodes == a.nodes) a.slots = &m->slots;
-      if (int rc = sweep_shape(k, region, kk == slf::KK_COMPUTE_MACRO, &sh)) return rc;
-      if (on_lat(m)) {
-        if (kk == slf::KK_COMPUTE_MACRO) e = slf::launch_lat_macro(m->sel, sh.prop, g, m->phys, a, s);
-        else e = slf::launch_lat_sweep(m->sel, sh.prop, g, m->phys, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-        break;
-      }
-      if (kk == slf::KK_COMPUTE_MACRO) e = slf::launch_macro(m->sel, sh.prop, g, m->phys, a, s);
-      else e = slf::launch_sweep(m->sel, sh.prop, g, m->phys, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-      break;
+  // what may be launched, where and with which propagation step: slf_bind.h part (f)
+  slf::LaunchShape sh;
+  slf::FaceBox box;
+  std::string why;
+  const slf::LaunchState state = {k->needs_iteration, k->iteration, m->accf != nullptr, k->pair.rows != 0};
+  if (int rc = slf::launch_check(*m, *k->row, b, state, region, &sh, &box, &why)) return fail(rc, why);
+  const slf::SweepArgs a = launch_args(k);
+  const slf::Launch lc = {m->sel, sh.prop, g, m->phys, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s};
+  if (k->pair.rows) {
+    // two steps per launch: whatever has changed since slf_kernel_set_pair accepted (a body force, face buffers)
+    // is an error here, never a quiet single step
+    const slf::SweepArgs pa = pair_args(a);
+    if (!slf::launch_sweep_pair(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair, s, &e)) {
+      const char* refusal = slf::pair_refusal(m->sel, m->access_pattern == SLF_AB, g, m->phys, pa, k->pair);
+      return fail(SLF_ERR_UNSUPPORTED, refusal ? refusal : "pair sweep: no kernel for this strip size");
     }
-    case slf::KK_SC_MACRO:
+  } else switch (kk) {
+    case slf::KK_COLLIDE_AND_PROPAGATE: e = on_lat(m) ? slf::launch_lat_sweep(lc, a) : slf::launch_sweep(lc, a); break;
+    case slf::KK_COMPUTE_MACRO: e = on_lat(m) ? slf::launch_lat_macro(lc, a) : slf::launch_macro(lc, a); break;
+    case slf::KK_SC_MACRO: e = slf::launch_sc_macro(lc, m->sc, a); break;
     case slf::KK_SC_SWEEP0:
-    case slf::KK_SC_SWEEP1:
-    case slf::KK_SC_FUSED:
-    case slf::KK_SCS_MACRO:
-    case slf::KK_SCS_SWEEP: {
-      if (int rc = nodes_given(k)) return rc;
-      sc_planes_of(m, a);
-      if (int rc = sweep_common(k, a)) return rc;
-      if (int rc = sweep_shape(k, region, kk == slf::KK_SCS_MACRO, &sh)) return rc;
-      if (kk == slf::KK_SC_MACRO) e = slf::launch_sc_macro(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, s);
-      else if (kk == slf::KK_SC_FUSED) e = slf::launch_sc_fused(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-      else if (kk == slf::KK_SCS_MACRO) e = slf::launch_scs_macro(m->sel, sh.prop, g, m->phys, m->sc, a, s);
-      else if (kk == slf::KK_SCS_SWEEP) e = slf::launch_scs_sweep(m->sel, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-      else e = slf::launch_sc_sweep(m->sel, kk == slf::KK_SC_SWEEP0 ? 0 : 1, sh.prop, g, m->phys, m->sc, a, sh.y0, sh.y1, sh.z0, sh.z1,
-                                    m->block_x, s);
-      break;
-    }
-    case slf::KK_FE_MACRO:
+    case slf::KK_SC_SWEEP1: e = slf::launch_sc_sweep(lc, m->sc, a, kk == slf::KK_SC_SWEEP0 ? 0 : 1); break;
+    case slf::KK_SC_FUSED: e = slf::launch_sc_fused(lc, m->sc, a); break;
+    case slf::KK_SCS_MACRO: e = slf::launch_scs_macro(lc, m->sc, a); break;
+    case slf::KK_SCS_SWEEP: e = slf::launch_scs_sweep(lc, m->sc, a); break;
+    case slf::KK_FE_MACRO: e = slf::launch_fe_macro(lc, m->fe, a); break;
     case slf::KK_FE_FLUID:
-    case slf::KK_FE_ORDER: {
-      if (int rc = sweep_common(k, a)) return rc;
-      if (int rc = sweep_shape(k, region, false, &sh)) return rc;
-      if (kk == slf::KK_FE_MACRO) e = slf::launch_fe_macro(m->sel, sh.prop, g, m->fe, a, sh.y0, sh.y1, sh.z0, sh.z1, s);
-      else e = slf::launch_fe_sweep(m->sel, kk == slf::KK_FE_FLUID ? 0 : 1, sh.prop, g, m->fe, a, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-      break;
-    }
+    case slf::KK_FE_ORDER: e = slf::launch_fe_sweep(lc, m->fe, a, kk == slf::KK_FE_FLUID ? 0 : 1); break;
     case slf::KK_SC3_MACRO:
     case slf::KK_SC3_SWEEP0:
     case slf::KK_SC3_SWEEP1:
     case slf::KK_SC3_SWEEP2:
     case slf::KK_SC3_FUSED: {
       slf::Sc3Args a3 = b.sc3;
-      if (m->sel.general && !a3.map) return fail(SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
       if (!m->sel.general) a3.map = nullptr;
-      if (int rc = sweep_shape(k, region, false, &sh)) return rc;
-      if (kk == slf::KK_SC3_MACRO) e = slf::launch_sc3_macro(m->sel, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1, s);
-      else if (kk == slf::KK_SC3_FUSED) e = slf::launch_sc3_fused(m->sel, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1, m->block_x, s);
-      else e = slf::launch_sc3_sweep(m->sel, (int)kk - (int)slf::KK_SC3_SWEEP0, sh.prop, g, m->phys, m->sc3, a3, sh.y0, sh.y1, sh.z0, sh.z1,
-                                     m->block_x, s);
+      if (kk == slf::KK_SC3_MACRO) e = slf::launch_sc3_macro(lc, m->sc3, a3);
+      else if (kk == slf::KK_SC3_FUSED) e = slf::launch_sc3_fused(lc, m->sc3, a3);
+      else e = slf::launch_sc3_sweep(lc, m->sc3, a3, (int)kk - (int)slf::KK_SC3_SWEEP0);
       break;
     }
     case slf::KK_RESIDENT: {
       // dist_in / dist_in2: source a / b, dist_out / dist_out2: destination a / b; the kernel's SweepArgs carry the map only
       const void* src[2] = {a.dist_in, a.dist_in2};
       void* dst[2] = {a.dist_out, a.dist_out2};
-      a = slf::SweepArgs{};
-      a.map = b.sweep.map;
-      a.options = b.sweep.options & ~1u;       // no field output from inside a stretch of resident steps
-      if (int rc = sweep_common(k, a)) return rc;
-      e = slf::launch_resident(m->sel, m->access_pattern == SLF_AA, g, m->phys, a, src, dst, (int)k->iteration, (int)b.ints[1],
+      slf::SweepArgs r = {};
+      r.map = a.map;
+      r.options = a.options & ~1u;       // no field output from inside a stretch of resident steps
+      r.node_params = a.node_params;
+      r.status = a.status;
+      e = slf::launch_resident(m->sel, m->access_pattern == SLF_AA, g, m->phys, r, src, dst, (int)k->iteration, (int)b.ints[1],
                                (int)b.ints[2], (int)b.ints[3], (int)b.ints[4], s);
       break;
     }
     // the initial conditions: (dist.., v.., rho[, phi[, theta]]) in the order of the reference (lb_single.py:72-94,
     // lb_binary.py:107-127, lb_ternary.py:118-142)
     case slf::KK_SET_INITIAL_CONDITIONS:
-      if (int rc = nodes_given(k)) return rc;
       if (on_lat(m)) e = slf::launch_lat_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, s);
       else e = slf::launch_init(m->sel, g, m->phys, a.dist_in, a.rho, a.v, a.nodes, s);
       break;
     case slf::KK_SC_INIT:
-      if (int rc = nodes_given(k)) return rc;
       e = slf::launch_sc_init(m->sel, g, m->phys, a.dist_in, a.dist_in2, a.rho, a.phi, a.v, a.nodes, s);
       break;
     case slf::KK_FE_INIT:
@@ -1689,28 +1564,14 @@ int slf_kernel_launch(slf_kernel* k, const slf_region* region, slf_stream* strea
       break;
     case slf::KK_COLLECT_BOX:
     case slf::KK_DISTRIBUTE_BOX:
-      if (b.n_ints >= 6) {
-        int dirs[32], nd = 0;
-        for (int q = 0; q < 32; q++) if (((unsigned int)b.ints[0] >> q) & 1u) dirs[nd++] = q;    // ascending
-        if (nd > 12) return fail(SLF_ERR_INVALID, "Collect/DistributeContinuousData: at most 12 directions per launch (a face of D3Q19 carries 5)");
-        e = slf::launch_box(m->sel, g, kk == slf::KK_COLLECT_BOX, (void*)b.ptrs[0], (void*)b.ptrs[1], dirs, nd,
-                            (unsigned long long)(uint32_t)b.ints[1], (long long)b.ints[2], (int)b.ints[3],
-                            (long long)b.ints[4], (int)b.ints[5], b.n_ints == 8 ? (long long)b.ints[6] : 0,
-                            b.n_ints == 8 ? (long long)b.ints[7] : 0, false, s);
-        break;
-      }
-      [[fallthrough]];      // the reference's own argument list
     case slf::KK_COLLECT_FACE_SWAP:
     case slf::KK_DISTRIBUTE_FACE_SWAP:
     case slf::KK_COLLECT_MACRO_FACE:
-    case slf::KK_DISTRIBUTE_MACRO_FACE: {
-      slf::FaceBox box;
-      const char* why = nullptr;
-      if (int rc = slf::face_box(g, kk, b.ints, &box, &why)) return fail(rc, why);
+    case slf::KK_DISTRIBUTE_MACRO_FACE: {      // `box`: the direction mask and the box, or the reference's face (launch_check)
       slf::Geometry gm = g;
       if (box.macro) gm.dist_size = 0;
-      e = slf::launch_box(m->sel, gm, box.collect, (void*)b.ptrs[0], (void*)b.ptrs[1], box.dirs, box.nd, box.base, 1, box.ncols,
-                          box.row_stride, box.nrows, 0, 0, box.macro, s);
+      e = slf::launch_box(m->sel, gm, box.collect, (void*)b.ptrs[0], (void*)b.ptrs[1], box.dirs, box.nd, box.base, box.col_stride,
+                          box.ncols, box.row_stride, box.nrows, box.buf_k_stride, box.buf_row_stride, box.macro, s);
       break;
     }
     case slf::KK_COLLECT_SPARSE:
@@ -1739,13 +1600,15 @@ struct PlanOp {
   std::vector<slf_comm_op> ops;
   void* dst = nullptr;
   const void* src = nullptr;
-  int value = 0;
+  int value = 0;             // PL_MEMSET: the byte
   size_t bytes = 0;
   slf_module* mod = nullptr;
+  int xface_set = -1;        // PL_XFACE: -1 the single-fluid buffers, 0 .. 2 that set of planes
   void* xf[4] = {nullptr, nullptr, nullptr, nullptr};
   slf_peer* peer = nullptr;
   std::vector<int32_t> ranks;
   int channel = 0;
+  int count = 0;             // PL_PEER_WAIT: the signals to wait for
 };
 }  // namespace
 
@@ -1848,29 +1711,28 @@ int slf_plan_add_copy(slf_plan* p, void* dst, const void* src, size_t bytes, slf
   return SLF_OK;
 }
 
-int slf_plan_add_xface_buffers(slf_plan* p, slf_module* m, void* send_low, void* send_high, void* recv_low, void* recv_high) {
+// planes: set `which` of them, else the buffers.  Validated now, with the module's rules, so that slf_plan_run cannot fail on it
+static int plan_add_xface(slf_plan* p, slf_module* m, bool planes, int32_t which, void* send_low, void* send_high, void* recv_low,
+                          void* recv_high) {
   if (!p || !m) return fail(SLF_ERR_INVALID, "NULL argument");
-  // validated now, with the module's rules, so that slf_plan_run cannot fail on it
-  if (int e = check_xface_buffers(m, send_low, send_high, recv_low, recv_high)) return e;
   PlanOp o;
   o.kind = PL_XFACE;
   o.mod = m;
+  o.xface_set = planes ? which : -1;
   o.xf[0] = send_low; o.xf[1] = send_high; o.xf[2] = recv_low; o.xf[3] = recv_high;
+  std::string why;
+  if (int rc = planes ? slf::xface_planes_check(m, which, o.xf, &why) : slf::xface_buffers_check(m, o.xf, &why)) return fail(rc, why);
   p->ops.push_back(o);
   return SLF_OK;
 }
 
+int slf_plan_add_xface_buffers(slf_plan* p, slf_module* m, void* send_low, void* send_high, void* recv_low, void* recv_high) {
+  return plan_add_xface(p, m, false, 0, send_low, send_high, recv_low, recv_high);
+}
+
 int slf_plan_add_xface_planes(slf_plan* p, slf_module* m, int32_t which, void* send_low, void* send_high, void* recv_low,
                               void* recv_high) {
-  if (!p || !m) return fail(SLF_ERR_INVALID, "NULL argument");
-  if (int e = check_xface_planes(m, which, send_low, send_high, recv_low, recv_high)) return e;
-  PlanOp o;
-  o.kind = PL_XFACE;
-  o.mod = m;
-  o.value = which + 1;        // 0: the single-fluid buffers
-  o.xf[0] = send_low; o.xf[1] = send_high; o.xf[2] = recv_low; o.xf[3] = recv_high;
-  p->ops.push_back(o);
-  return SLF_OK;
+  return plan_add_xface(p, m, true, which, send_low, send_high, recv_low, recv_high);
 }
 
 static int plan_add_peer(slf_plan* p, PlanKind kind, slf_peer* peer, const int32_t* ranks, int n, int channel, int count,
@@ -1885,7 +1747,7 @@ static int plan_add_peer(slf_plan* p, PlanKind kind, slf_peer* peer, const int32
   o.peer = peer;
   o.ranks.assign(ranks, ranks + n);
   o.channel = channel;
-  o.value = count;
+  o.count = count;
   o.stream = stream;
   p->ops.push_back(o);
   return SLF_OK;
@@ -1913,17 +1775,9 @@ int slf_plan_run(slf_plan* p, uint32_t iteration) {
       case PL_EXCHANGE: e = slf_comm_exchange(o.comm, o.ops.data(), (int)o.ops.size(), o.stream); break;
       case PL_MEMSET: e = slf_memset(p->ctx, o.dst, o.value, o.bytes, o.stream); break;
       case PL_COPY: e = slf_memcpy_d2d_async(p->ctx, o.dst, o.src, o.bytes, o.stream); break;
-      case PL_XFACE:
-        if (o.value > 0) {
-          o.mod->sc_send[o.value - 1][0] = o.xf[0]; o.mod->sc_send[o.value - 1][1] = o.xf[1];
-          o.mod->sc_recv[o.value - 1][0] = o.xf[2]; o.mod->sc_recv[o.value - 1][1] = o.xf[3];
-          break;
-        }
-        o.mod->xsend[0] = o.xf[0]; o.mod->xsend[1] = o.xf[1];
-        o.mod->xrecv[0] = o.xf[2]; o.mod->xrecv[1] = o.xf[3];
-        break;
+      case PL_XFACE: store_xface(o.mod, o.xface_set, o.xf); break;
       case PL_PEER_SIGNAL: e = slf_peer_signal(o.peer, o.ranks.data(), (int)o.ranks.size(), o.channel, o.stream); break;
-      case PL_PEER_WAIT: e = slf_peer_wait(o.peer, o.ranks.data(), (int)o.ranks.size(), o.channel, o.value, o.stream); break;
+      case PL_PEER_WAIT: e = slf_peer_wait(o.peer, o.ranks.data(), (int)o.ranks.size(), o.channel, o.count, o.stream); break;
     }
     if (e) return e;
   }

@@ -1,6 +1,6 @@
 // Host logic of the C ABI that needs no GPU (used by slf_api.hip; exercised on the CPU by tests/abi_bind_main.cpp):
 // a module descriptor into the module's configuration, the table of kernels the library serves with their argument
-// lists, and the index arithmetic of the reference's face kernels.  Calls no HIP function, allocates nothing, and reads
+// lists, the index arithmetic of the reference's face kernels, and (part (f)) what a launch and the x-face setters check.  Calls no HIP function, allocates nothing, and reads
 // no global state beyond the environment knobs SLF_BC_LEVEL, SLF_VARIANT and SLF_BLOCK_X.
 #pragma once
 #include <stdlib.h>
@@ -439,6 +439,7 @@ inline int family_of(const ModuleConfig& c) {
 //   r rho  p phi  t theta (ternary: field[0..2]) | v velocity, one pointer per dimension | l phi_laplacian |
 //   x a pointer the launch reads from BoundArgs::ptrs by position (halo and PBC kernels)
 // n_ints: the integer arguments; in the sweeps the first one is the options word.  FACE_INTS / BOX_INTS: see bind().
+// launch: what slf_kernel_launch checks for this kind, one letter per check in order (part (f), launch_check()).
 // nodes_in_front: modules with indirect addressing put the `nodes` table in front of the list (reference
 // _add_indirect_args, subdomain_runner.py:1153-1157).  local_velocity: SweepArgs::sc_local_velocity.
 constexpr int FACE_INTS = -1, BOX_INTS = -2;
@@ -449,49 +450,50 @@ struct KernelRow {
   const char* slots;
   int n_ints;
   bool nodes_in_front, local_velocity;
+  const char* launch;      // the checks of slf_kernel_launch, in order: part (f), launch_check()
 };
 
 inline constexpr KernelRow KERNEL_TABLE[] = {
   // single fluid (lb_single.py:72-133); single-component Shan-Chen shares the lists
-  {"CollideAndPropagate", KK_COLLIDE_AND_PROPAGATE, F_SINGLE, "maArv", 1, true, false},     // [, alpha]: bind()
-  {"CollideAndPropagate", KK_SCS_SWEEP, F_SCS, "maArv", 1, true, false},
-  {"ComputeMacroFields", KK_COMPUTE_MACRO, F_SINGLE | F_SCS, "maArv", 1, true, false},
-  {"PrepareMacroFields", KK_SCS_MACRO, F_SCS, "mar", 1, true, false},
-  {"SetInitialConditions", KK_SET_INITIAL_CONDITIONS, F_SINGLE | F_SCS, "avrm", 0, true, false},
-  {"SetInitialConditions", KK_SC_INIT, F_SC2, "mabvrp", 0, true, false},                    // lb_binary.py:107-127
-  {"SetInitialConditions", KK_FE_INIT, F_FE, "mabvrp", 0, false, false},
-  {"SetInitialConditions", KK_SC3_INIT, F_SC3, "mabcvrpt", 0, false, false},                // lb_ternary.py:118-142
+  {"CollideAndPropagate", KK_COLLIDE_AND_PROPAGATE, F_SINGLE, "maArv", 1, true, false, "pfmns"},     // [, alpha]: bind()
+  {"CollideAndPropagate", KK_SCS_SWEEP, F_SCS, "maArv", 1, true, false, "nms"},
+  {"ComputeMacroFields", KK_COMPUTE_MACRO, F_SINGLE | F_SCS, "maArv", 1, true, false, "pmnS"},
+  {"PrepareMacroFields", KK_SCS_MACRO, F_SCS, "mar", 1, true, false, "nmS"},
+  {"SetInitialConditions", KK_SET_INITIAL_CONDITIONS, F_SINGLE | F_SCS, "avrm", 0, true, false, "n"},
+  {"SetInitialConditions", KK_SC_INIT, F_SC2, "mabvrp", 0, true, false, "n"},                    // lb_binary.py:107-127
+  {"SetInitialConditions", KK_FE_INIT, F_FE, "mabvrp", 0, false, false, ""},
+  {"SetInitialConditions", KK_SC3_INIT, F_SC3, "mabcvrpt", 0, false, false, ""},                // lb_ternary.py:118-142
   // several steps inside one launch: map, src a, src b, dst a, dst b | options, steps, tile x, tile y, halo
-  {"CollideAndPropagateResident", KK_RESIDENT, F_ALL & ~F_SC3, "mabAB", 5, false, false},
+  {"CollideAndPropagateResident", KK_RESIDENT, F_ALL & ~F_SC3, "mabAB", 5, false, false, "m"},
   // binary Shan-Chen (lb_binary.py:457-465): the pass reads both lattices (dist_in, dist_out)
-  {"ShanChenPrepareMacroFields", KK_SC_MACRO, F_SC2, "maArpv", 1, true, false},
-  {"ShanChenCollideAndPropagate0", KK_SC_SWEEP0, F_SC2, "maArpv", 1, true, false},
-  {"ShanChenCollideAndPropagate1", KK_SC_SWEEP1, F_SC2, "maArpv", 1, true, false},
-  {"ShanChenCollideAndPropagateFused", KK_SC_FUSED, F_SC2, "maAbBrpv", 1, false, false},
-  {"ShanChenPrepareDensities", KK_SC_MACRO, F_SC2, "maArpv", 1, true, true},
-  {"ShanChenCollideAndPropagateFusedV", KK_SC_FUSED, F_SC2, "maAbBrpv", 1, false, true},
+  {"ShanChenPrepareMacroFields", KK_SC_MACRO, F_SC2, "maArpv", 1, true, false, "nms"},
+  {"ShanChenCollideAndPropagate0", KK_SC_SWEEP0, F_SC2, "maArpv", 1, true, false, "nms"},
+  {"ShanChenCollideAndPropagate1", KK_SC_SWEEP1, F_SC2, "maArpv", 1, true, false, "nms"},
+  {"ShanChenCollideAndPropagateFused", KK_SC_FUSED, F_SC2, "maAbBrpv", 1, false, false, "nms"},
+  {"ShanChenPrepareDensities", KK_SC_MACRO, F_SC2, "maArpv", 1, true, true, "nms"},
+  {"ShanChenCollideAndPropagateFusedV", KK_SC_FUSED, F_SC2, "maAbBrpv", 1, false, true, "nms"},
   // ternary Shan-Chen (lb_ternary.py:220-333): the names it shares with the binary model take the ternary lists
-  {"ShanChenPrepareMacroFields", KK_SC3_MACRO, F_SC3, "mabcrptv", 1, false, false},
-  {"ShanChenCollideAndPropagate0", KK_SC3_SWEEP0, F_SC3, "maArptv", 1, false, false},
-  {"ShanChenCollideAndPropagate1", KK_SC3_SWEEP1, F_SC3, "maArptv", 1, false, false},
-  {"ShanChenCollideAndPropagate2", KK_SC3_SWEEP2, F_SC3, "maArptv", 1, false, false},
-  {"ShanChenCollideAndPropagateFused", KK_SC3_FUSED, F_SC3, "maAbBcCrptv", 1, false, false},
+  {"ShanChenPrepareMacroFields", KK_SC3_MACRO, F_SC3, "mabcrptv", 1, false, false, "Ms"},
+  {"ShanChenCollideAndPropagate0", KK_SC3_SWEEP0, F_SC3, "maArptv", 1, false, false, "Ms"},
+  {"ShanChenCollideAndPropagate1", KK_SC3_SWEEP1, F_SC3, "maArptv", 1, false, false, "Ms"},
+  {"ShanChenCollideAndPropagate2", KK_SC3_SWEEP2, F_SC3, "maArptv", 1, false, false, "Ms"},
+  {"ShanChenCollideAndPropagateFused", KK_SC3_FUSED, F_SC3, "maAbBcCrptv", 1, false, false, "Ms"},
   // free energy (lb_binary.py:295-308)
-  {"FreeEnergyPrepareMacroFields", KK_FE_MACRO, F_FE, "maArp", 1, false, false},
-  {"FreeEnergyCollideAndPropagateFluid", KK_FE_FLUID, F_FE, "maArpvl", 1, false, false},
-  {"FreeEnergyCollideAndPropagateOrderParam", KK_FE_ORDER, F_FE, "maApvl", 1, false, false},
+  {"FreeEnergyPrepareMacroFields", KK_FE_MACRO, F_FE, "maArp", 1, false, false, "ms"},
+  {"FreeEnergyCollideAndPropagateFluid", KK_FE_FLUID, F_FE, "maArpvl", 1, false, false, "ms"},
+  {"FreeEnergyCollideAndPropagateOrderParam", KK_FE_ORDER, F_FE, "maApvl", 1, false, false, "ms"},
   // ghost layers and halo, every family: dist | field, axis
-  {"ApplyPeriodicBoundaryConditions", KK_PBC, F_ALL, "x", 1, false, false},
-  {"ApplyPeriodicBoundaryConditionsWithSwap", KK_PBC_SWAP, F_ALL, "x", 1, false, false},
-  {"ApplyMacroPeriodicBoundaryConditions", KK_MACRO_PBC, F_ALL, "x", 1, false, false},
-  {"CollectSparseData", KK_COLLECT_SPARSE, F_ALL, "xxx", 1, false, false},                  // idx_array, dist, buffer, n
-  {"DistributeSparseData", KK_DISTRIBUTE_SPARSE, F_ALL, "xxx", 1, false, false},
-  {"CollectContinuousData", KK_COLLECT_BOX, F_ALL, "xx", BOX_INTS, false, false},
-  {"DistributeContinuousData", KK_DISTRIBUTE_BOX, F_ALL, "xx", BOX_INTS, false, false},
-  {"CollectContinuousDataWithSwap", KK_COLLECT_FACE_SWAP, F_ALL, "xx", FACE_INTS, false, false},
-  {"DistributeContinuousDataWithSwap", KK_DISTRIBUTE_FACE_SWAP, F_ALL, "xx", FACE_INTS, false, false},
-  {"CollectContinuousMacroData", KK_COLLECT_MACRO_FACE, F_ALL, "xx", FACE_INTS, false, false},
-  {"DistributeContinuousMacroData", KK_DISTRIBUTE_MACRO_FACE, F_ALL, "xx", FACE_INTS, false, false},
+  {"ApplyPeriodicBoundaryConditions", KK_PBC, F_ALL, "x", 1, false, false, ""},
+  {"ApplyPeriodicBoundaryConditionsWithSwap", KK_PBC_SWAP, F_ALL, "x", 1, false, false, ""},
+  {"ApplyMacroPeriodicBoundaryConditions", KK_MACRO_PBC, F_ALL, "x", 1, false, false, ""},
+  {"CollectSparseData", KK_COLLECT_SPARSE, F_ALL, "xxx", 1, false, false, ""},                  // idx_array, dist, buffer, n
+  {"DistributeSparseData", KK_DISTRIBUTE_SPARSE, F_ALL, "xxx", 1, false, false, ""},
+  {"CollectContinuousData", KK_COLLECT_BOX, F_ALL, "xx", BOX_INTS, false, false, "b"},
+  {"DistributeContinuousData", KK_DISTRIBUTE_BOX, F_ALL, "xx", BOX_INTS, false, false, "b"},
+  {"CollectContinuousDataWithSwap", KK_COLLECT_FACE_SWAP, F_ALL, "xx", FACE_INTS, false, false, "F"},
+  {"DistributeContinuousDataWithSwap", KK_DISTRIBUTE_FACE_SWAP, F_ALL, "xx", FACE_INTS, false, false, "F"},
+  {"CollectContinuousMacroData", KK_COLLECT_MACRO_FACE, F_ALL, "xx", FACE_INTS, false, false, "F"},
+  {"DistributeContinuousMacroData", KK_DISTRIBUTE_MACRO_FACE, F_ALL, "xx", FACE_INTS, false, false, "F"},
 };
 
 inline bool is_ternary_kind(KernelKind kk) { return kk >= KK_SC3_MACRO && kk <= KK_SC3_INIT; }
@@ -717,6 +719,7 @@ struct FaceBox {
   unsigned long long base;
   long long row_stride;
   int ncols, nrows;
+  long long col_stride, buf_k_stride, buf_row_stride;      // a face: 1 and the dense buffer [k][r][c] (0, 0)
 };
 
 inline int face_box(const Geometry& g, KernelKind kind, const long long* ints, FaceBox* box, const char** err) {
@@ -769,6 +772,7 @@ inline int face_box(const Geometry& g, KernelKind kind, const long long* ints, F
   box->collect = collect; box->macro = macro; box->layer = layer;
   for (int i = 0; i < nd; i++) box->dirs[i] = dirs[i];
   box->nd = nd; box->base = base; box->row_stride = row_stride; box->ncols = ncols; box->nrows = nrows;
+  box->col_stride = 1; box->buf_k_stride = box->buf_row_stride = 0;
   return SLF_OK;
 }
 
@@ -836,6 +840,153 @@ inline int thermal_check(const ModuleConfig& c, bool has_field, const char* what
                                             "writes the other");
   if (c.geo.lat_ny - 2 > 4 * 65535 || c.geo.lat_nz - 2 > 65535)
     return refuse(err, SLF_ERR_UNSUPPORTED, w + "more than 262140 rows or 65535 layers (the launch grid runs over them)");
+  return SLF_OK;
+}
+
+// ---- (f) the launch (slf_kernel_launch) and the setters' argument checks ------------------------------------------------------
+// What stands between a caller and an out-of-bounds kernel.  Which checks a kind gets, and in which order, is the column
+// `launch` of its row in KERNEL_TABLE, one letter per check; the first that fails answers:
+//   p  a pair sweep is armed (slf_kernel_set_pair): whole-box launches only, and nothing further is asked
+//   f  an accel_field module has its field (slf_module_set_accel_field)
+//   m  the node map is not NULL in a module with node types; M: the same for the ternary kinds' own argument list
+//   n  the `nodes` table is not NULL under indirect addressing
+//   s  the kernel takes a propagation step and rows: an AA kernel has its iteration, the region lies inside the real nodes
+//      (y0 == y1 is an empty launch; 2-D: z0 = 0, z1 = 1, the region's z is not read); S: the same for a kernel that
+//      always covers every real node (the region is neither read nor validated)
+//   b  a box transfer: at most 12 directions per launch, or the reference's face argument list (face_box)
+//   F  the reference's face argument list (face_box)
+// A kind without s / S uses no propagation step.  A new kernel kind puts its rule into that column.
+struct LaunchState {      // what the kernel and module objects hold when the launch is asked for
+  int needs_iteration;
+  uint32_t iteration;
+  bool has_field;         // slf_module_set_accel_field was called
+  bool pair_armed;        // slf_kernel_set_pair accepted
+};
+struct LaunchShape {
+  Prop prop;
+  int y0, y1, z0, z1;
+};
+
+// *shape: the step and the rows of the launch; *box: what a box / face kind moves (those kinds only).  Builds no string and
+// allocates nothing unless a check fails.
+inline int launch_check(const ModuleConfig& c, const KernelRow& row, const BoundArgs& b, const LaunchState& st,
+                        const slf_region* region, LaunchShape* shape, FaceBox* box, std::string* err) {
+  const Geometry& g = c.geo;
+  *shape = LaunchShape{PROP_AB, 1, g.lat_ny - 1, g.dim == 2 ? 0 : 1, g.dim == 2 ? 1 : g.lat_nz - 1};
+  for (const char* rule = row.launch; *rule; rule++) {
+    switch (*rule) {
+      case 'p':
+        if (!st.pair_armed) break;
+        if (region) return refuse(err, SLF_ERR_UNSUPPORTED, "pair sweep: whole-box launches only");
+        return SLF_OK;
+      case 'f':
+        if (c.phys.accel_field && !st.has_field)
+          return refuse(err, SLF_ERR_INVALID, "CollideAndPropagate: the module was created with accel_field, but no field is set "
+                                              "(slf_module_set_accel_field)");
+        break;
+      case 'm': case 'M':
+        if (c.sel.general && !(*rule == 'M' ? b.sc3.map : b.sweep.map))
+          return refuse(err, SLF_ERR_INVALID, "node map is NULL but the module is not fluid_only");
+        break;
+      case 'n':
+        if (g.indirect && !b.sweep.nodes) return refuse(err, SLF_ERR_INVALID, "indirect addressing: the nodes table is NULL");
+        break;
+      case 's': case 'S':
+        if (c.access_pattern == SLF_AA) {
+          if (!st.needs_iteration) return refuse(err, SLF_ERR_INVALID, "AA kernels need the iteration argument");
+          shape->prop = (st.iteration & 1u) ? PROP_AA_ODD : PROP_AA_EVEN;
+        }
+        if (region && *rule == 's') {
+          shape->y0 = region->y0; shape->y1 = region->y1;
+          if (g.dim == 3) { shape->z0 = region->z0; shape->z1 = region->z1; }
+          if (shape->y0 < 1 || shape->y1 > g.lat_ny - 1 || shape->y0 > shape->y1 ||
+              (g.dim == 3 && (shape->z0 < 1 || shape->z1 > g.lat_nz - 1 || shape->z0 > shape->z1)))
+            return refuse(err, SLF_ERR_INVALID, "region outside the real nodes of the subdomain");
+        }
+        break;
+      case 'b':
+        if (b.n_ints >= 6) {      // dirs (a bit mask, ascending), base, col_stride, ncols, row_stride, nrows [, buffer strides]
+          *box = FaceBox{};
+          box->collect = row.kind == KK_COLLECT_BOX;
+          for (int q = 0; q < 32; q++) if (((unsigned int)b.ints[0] >> q) & 1u) box->dirs[box->nd++] = q;
+          if (box->nd > 12)
+            return refuse(err, SLF_ERR_INVALID, "Collect/DistributeContinuousData: at most 12 directions per launch (a face of D3Q19 carries 5)");
+          box->base = (unsigned long long)(uint32_t)b.ints[1]; box->col_stride = b.ints[2]; box->ncols = (int)b.ints[3];
+          box->row_stride = b.ints[4]; box->nrows = (int)b.ints[5];
+          if (b.n_ints == 8) { box->buf_k_stride = b.ints[6]; box->buf_row_stride = b.ints[7]; }
+          break;
+        }
+        [[fallthrough]];      // the reference's own argument list
+      case 'F': {
+        const char* why = nullptr;
+        if (int rc = face_box(g, row.kind, b.ints, box, &why)) return refuse(err, rc, why);
+        break;
+      }
+    }
+  }
+  return SLF_OK;
+}
+
+// CollideAndPropagateResident: what its integer arguments (options, steps, tile x, tile y, halo) and arrays must satisfy
+inline int resident_check(const ModuleConfig& c, const BoundArgs& b, int needs_iteration, std::string* err) {
+  const SweepArgs& a = b.sweep;      // dist_in / dist_in2: source a / b, dist_out / dist_out2: destination a / b
+  const bool aa = c.access_pattern == SLF_AA;
+  const int steps = (int)b.ints[1], tx = (int)b.ints[2], ty = (int)b.ints[3], halo = (int)b.ints[4];
+  if (!needs_iteration) return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident needs the iteration argument (its first step)");
+  if (steps < 1 || tx < 1 || ty < 1 || halo < 1) return refuse(err, SLF_ERR_INVALID, "steps, tile and halo must be positive");
+  if (!a.dist_in || !a.dist_out || (!aa && (!a.dist_in2 || !a.dist_out2)))
+    return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination arrays (both copies of the two-copy pattern)");
+  if (a.dist_in == a.dist_out || (!aa && a.dist_in2 == a.dist_out2))
+    return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident: source and destination must be different buffers");
+  // the halo that `steps` steps need depends on the parity of the first one: the worse of the two must fit
+  const int even = resident_halo(aa, 0, steps), odd = resident_halo(aa, 1, steps);
+  if (halo < (even > odd ? even : odd)) return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident: halo too small for this many steps");
+  const long long nw = (long long)(tx + 2 * halo) * (long long)(ty + 2 * halo);
+  if (nw > 2 * 1024) return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident: window larger than 2048 nodes");
+  const int q = 9;
+  // the window (dynamic LDS) + the kernel's own tables (static: the list of a window's boundary-condition nodes,
+  // slf_resident.hip) share the 160 KiB of a workgroup
+  if (resident_lds_bytes(q, c.sel.precision, aa, tx + 2 * halo, ty + 2 * halo) + 4352 > 160 * 1024)
+    return refuse(err, SLF_ERR_INVALID, "CollideAndPropagateResident: window does not fit the 160 KiB of LDS");
+  return SLF_OK;
+}
+
+// slf_module_set_xface_buffers / slf_plan_add_xface_buffers: [0] send low, [1] send high, [2] receive low, [3] receive high
+inline int xface_buffers_check(const ModuleConfig* c, const void* const xf[4], std::string* err) {
+  if (!c) return refuse(err, SLF_ERR_INVALID, "module is NULL");
+  if (!xf[0] && !xf[1] && !xf[2] && !xf[3]) return SLF_OK;
+  const Geometry& g = c->geo;
+  if (is_lat_lattice(c->sel.lattice))
+    return refuse(err, SLF_ERR_UNSUPPORTED, std::string(c->sel.lattice == SLF_D3Q15 ? "D3Q15" : "D3Q27") +
+                                                ": x-face buffers are not implemented on this lattice (D3Q19 only)");
+  if (c->sel.lattice != 1 || g.indirect || c->sc.enabled || c->fe.enabled || c->sc3.enabled || !(g.variant & 8))
+    return refuse(err, SLF_ERR_UNSUPPORTED, "x-face buffers: D3Q19 single-fluid modules with direct addressing (whole-row kernels) only");
+  if (g.wrap[0]) return refuse(err, SLF_ERR_INVALID, "x-face buffers make no sense with x wrapped inside the sweep");
+  if (g.lat_nx - 2 > 1024) return refuse(err, SLF_ERR_UNSUPPORTED, "x-face buffers: rows of at most 1024 nodes");
+  if ((xf[0] == nullptr) != (xf[2] == nullptr) || (xf[1] == nullptr) != (xf[3] == nullptr))
+    return refuse(err, SLF_ERR_INVALID, "a connected face needs both its send and its receive buffer");
+  return SLF_OK;
+}
+
+// slf_module_set_xface_planes / slf_plan_add_xface_planes: the planes of set `which`, in the order of xface_buffers_check
+inline int xface_planes_check(const ModuleConfig* c, int32_t which, const void* const xf[4], std::string* err) {
+  if (!c) return refuse(err, SLF_ERR_INVALID, "module is NULL");
+  if (which < 0 || which > 2) return refuse(err, SLF_ERR_INVALID, "x-face planes: 0 / 1 = populations of lattice 0 / 1, 2 = densities");
+  if (!xf[0] && !xf[1] && !xf[2] && !xf[3]) return SLF_OK;
+  const Geometry& g = c->geo;
+  if (c->sc3.enabled)
+    return refuse(err, SLF_ERR_UNSUPPORTED, "x-face planes: not implemented for simtype = SLF_SIM_SHAN_CHEN_TERNARY (the planes carry two "
+                                            "lattices and two density fields); connected x faces go through ghost columns and index lists");
+  if (is_lat_lattice(c->sel.lattice))
+    return refuse(err, SLF_ERR_UNSUPPORTED, std::string(c->sel.lattice == SLF_D3Q15 ? "D3Q15" : "D3Q27") +
+                                                ": x-face planes are not implemented on this lattice (D3Q19 only)");
+  if (c->sel.lattice != 1 || g.indirect || !c->sc.enabled || !(g.variant & 8))
+    return refuse(err, SLF_ERR_UNSUPPORTED, "x-face planes: D3Q19 Shan-Chen modules with direct addressing (whole-row kernels)");
+  if (c->sc.enabled == 2 && which == 1) return refuse(err, SLF_ERR_INVALID, "x-face planes: the single-component model has one lattice");
+  if (g.wrap[0]) return refuse(err, SLF_ERR_INVALID, "x-face planes make no sense with x wrapped inside the sweep");
+  if (g.lat_nx - 2 > 1024 || g.lat_nx - 2 < 2) return refuse(err, SLF_ERR_UNSUPPORTED, "x-face planes: rows of 2 .. 1024 nodes");
+  if ((xf[0] == nullptr) != (xf[2] == nullptr) || (xf[1] == nullptr) != (xf[3] == nullptr))
+    return refuse(err, SLF_ERR_INVALID, "a connected face needs both its send and its receive plane");
   return SLF_OK;
 }
 

@@ -319,8 +319,8 @@ static FeParams<R> make_fe(const Geometry& g, const FreeEnergy& fe, const SweepA
 }
 
 // a.dist_out: lattice 1 (read), a.phi: written
-hipError_t launch_fe_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const FreeEnergy& fe, const SweepArgs& a,
-                           int y0, int y1, int z0, int z1, hipStream_t s) {
+hipError_t launch_fe_macro(const Launch& lc, const FreeEnergy& fe, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
   return pick_lr(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;
@@ -336,8 +336,8 @@ hipError_t launch_fe_macro(const KernelSelector& sel, Prop prop, const Geometry&
 }
 
 // which = 0: fluid lattice, 1: order parameter
-hipError_t launch_fe_sweep(const KernelSelector& sel, int which, Prop prop, const Geometry& g, const FreeEnergy& fe,
-                           const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+hipError_t launch_fe_sweep(const Launch& lc, const FreeEnergy& fe, const SweepArgs& a, int which) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
   return pick_lr(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;

@@ -185,8 +185,14 @@ struct KernelSelector {
   bool general;  // reads the node map / handles BC nodes
 };
 
-hipError_t launch_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                        const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+// Where and how a region launcher runs: the module's selector, geometry and physics, the propagation step of this launch and
+// the rows [y0, y1) x [z0, z1) it covers (slf_bind.h launch_check), the module's workgroup width and the stream.
+struct Launch {
+  const KernelSelector& sel; Prop prop; const Geometry& g; const Physics& ph;
+  int y0, y1, z0, z1; int block_x; hipStream_t s;
+};
+
+hipError_t launch_sweep(const Launch& lc, const SweepArgs& a);
 
 hipError_t launch_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist,
                        const void* rho, const void* const v[3], const void* nodes, hipStream_t s);
@@ -203,8 +209,7 @@ hipError_t launch_box(const KernelSelector& sel, const Geometry& g, bool collect
                       const int* dirs, int nd, unsigned long long base, long long col_stride, int ncols, long long row_stride,
                       int nrows, long long buf_k_stride, long long buf_row_stride, bool deliver_all, hipStream_t s);
 
-hipError_t launch_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                        const SweepArgs& a, hipStream_t s);
+hipError_t launch_macro(const Launch& lc, const SweepArgs& a);      // every real node, whatever the rows of lc
 
 // Builds the tables of RowClasses for `map` (device buffers seg_class, row_class, bc_rows and the counters
 // {class-2 rows, class-0 segments} are the caller's); the counts are read back by the caller.
@@ -215,56 +220,42 @@ hipError_t launch_classify_rows(const Geometry& g, const void* map, uint32_t* se
 
 // ---- binary Shan-Chen (slf_sc.hip) ----
 // macro pass: a.dist_in = lattice 0, a.dist_out = lattice 1 (both read), writes rho, phi, v
-hipError_t launch_sc_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                           const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s);
+hipError_t launch_sc_macro(const Launch& lc, const ShanChen& sc, const SweepArgs& a);
 // collide-and-stream of lattice `grid_idx`: reads rho, phi, v
-hipError_t launch_sc_sweep(const KernelSelector& sel, int grid_idx, Prop prop, const Geometry& g, const Physics& ph,
-                           const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                           hipStream_t s);
+hipError_t launch_sc_sweep(const Launch& lc, const ShanChen& sc, const SweepArgs& a, int grid_idx);
 // both lattices in one pass: a.dist_in / dist_out = lattice 0, a.dist_in2 / dist_out2 = lattice 1
-hipError_t launch_sc_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen& sc,
-                           const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_sc_fused(const Launch& lc, const ShanChen& sc, const SweepArgs& a);
 // single-component Shan-Chen: density pass (a.dist_in -> a.rho) and the sweep with the force
-hipError_t launch_scs_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen& sc, const SweepArgs& a, hipStream_t s);
-hipError_t launch_scs_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                            hipStream_t s);
+hipError_t launch_scs_macro(const Launch& lc, const ShanChen& sc, const SweepArgs& a);      // every real node
+hipError_t launch_scs_sweep(const Launch& lc, const ShanChen& sc, const SweepArgs& a);
 hipError_t launch_sc_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist1, void* dist2,
                           const void* rho, const void* phi, const void* const v[3], const void* nodes, hipStream_t s);
 
 // ---- free-energy binary fluid (slf_fe.hip) ----
 // macro pass: a.dist_out = lattice 1 (read), writes a.phi (wetting walls: phi of the helper node minus the constant)
-hipError_t launch_fe_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const FreeEnergy& fe, const SweepArgs& a,
-                           int y0, int y1, int z0, int z1, hipStream_t s);
+hipError_t launch_fe_macro(const Launch& lc, const FreeEnergy& fe, const SweepArgs& a);
 // collide-and-stream of the fluid lattice (which = 0: reads phi, writes v and a.lap) or of the order parameter (1: reads them)
-hipError_t launch_fe_sweep(const KernelSelector& sel, int which, Prop prop, const Geometry& g, const FreeEnergy& fe,
-                           const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_fe_sweep(const Launch& lc, const FreeEnergy& fe, const SweepArgs& a, int which);
 hipError_t launch_fe_init(const KernelSelector& sel, const Geometry& g, const FreeEnergy& fe, void* dist1, void* dist2,
                           const void* rho, const void* phi, const void* const v[3], const void* map, hipStream_t s);
 
 // ---- ternary Shan-Chen mixture (slf_sc3.hip) ----
 // pass in front: a.dist_in[0..2] (read) -> a.field[0..2], a.v
-hipError_t launch_sc3_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
-                            const Sc3Args& a, int y0, int y1, int z0, int z1, hipStream_t s);
+hipError_t launch_sc3_macro(const Launch& lc, const ShanChen3& sc, const Sc3Args& a);
 // collide-and-stream of lattice `lattice` (a.dist_in[0] -> a.dist_out[0]): reads the three fields and v
-hipError_t launch_sc3_sweep(const KernelSelector& sel, int lattice, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen3& sc, const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_sc3_sweep(const Launch& lc, const ShanChen3& sc, const Sc3Args& a, int lattice);
 // the three lattices in one pass: a.dist_in[k] -> a.dist_out[k]
-hipError_t launch_sc3_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
-                            const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_sc3_fused(const Launch& lc, const ShanChen3& sc, const Sc3Args& a);
 hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* const dist[3], const void* const field[3],
                            const void* const v[3], hipStream_t s);
 
 // ---- D3Q15 and D3Q27 (slf_lat.hip): BGK single-fluid modules, direct addressing ----
 // the counterparts of launch_sweep / launch_init / launch_pbc / launch_macro; any other lattice: hipErrorInvalidValue
-hipError_t launch_lat_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                            int y0, int y1, int z0, int z1, int block_x, hipStream_t s);
+hipError_t launch_lat_sweep(const Launch& lc, const SweepArgs& a);
 hipError_t launch_lat_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist, const void* rho,
                            const void* const v[3], hipStream_t s);
 hipError_t launch_lat_pbc(const KernelSelector& sel, const Geometry& g, void* dist, int axis, bool with_swap, hipStream_t s);
-hipError_t launch_lat_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                            hipStream_t s);
+hipError_t launch_lat_macro(const Launch& lc, const SweepArgs& a);
 
 // ---- several steps inside one launch (slf_resident.hip): 2-D lattices ----
 // src / dst: the raw distribution arrays ([0] = the array of the in-place pattern / copy A of the two-copy pattern, [1] =
@@ -272,19 +263,33 @@ hipError_t launch_lat_macro(const KernelSelector& sel, Prop prop, const Geometry
 hipError_t launch_resident(const KernelSelector& sel, bool aa, const Geometry& g, const Physics& ph, const SweepArgs& a,
                            const void* const src[2], void* const dst[2], int it0, int steps, int tile_x, int tile_y, int halo,
                            hipStream_t s);
-int resident_halo(bool aa, int it0, int steps);
-size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y);
+// How far what is wrong has spread from the window's ring after `steps` steps from iteration it0 (the head of
+// slf_resident.hip): the halo the tile needs.
+inline int resident_halo(bool aa, int it0, int steps) {
+  if (!aa) return steps + 1;
+  int odd = 0;
+  for (int s = 0; s < steps; s++) odd += (it0 + s) & 1;
+  return odd ? 2 * odd : 1;
+}
+// in place: the array and the staging block of the odd steps; two-copy: copy A and copy B
+inline size_t resident_lds_bytes(int q, int precision, bool /*aa*/, int win_x, int win_y) {
+  const size_t nw = (size_t)win_x * (size_t)win_y;
+  return nw * (size_t)q * (size_t)precision * 2 + nw * 8;
+}
 
 // ---- two steps per launch of the two-copy sweep (slf_pair.hip): periodic D3Q19 / f32 / BGK boxes ----
-// a.dist_in: the populations of step t, a.dist_out: where those of step t + 2 go; strips of `rows` rows (2 or 4), chunks
-// of `zc` planes; prefetch: 0 = phase A loads into registers and waits, 1 = the next row is in flight to LDS while the
-// current one collides; xcd_log2: neighbouring strips go to one XCD, at most 1 << this each (0: strips as they come); march:
-// 1 = odd strips walk phase A's rows downwards.  pair_refusal: why the module / the arguments do not qualify, NULL if they do; launch_sweep_pair
-// returns false (nothing launched) in exactly those cases.
+// a.dist_in: the populations of step t, a.dist_out: where those of step t + 2 go.  PairKnobs: strips of `rows` rows (2 or 4;
+// 0: no pair sweep is armed), chunks of `zc` planes; prefetch: 0 = phase A loads into registers and waits, 1 = the next row is
+// in flight to LDS while the current one collides; xcd_log2: neighbouring strips go to one XCD, at most 1 << this each (0:
+// strips as they come); march: 1 = odd strips walk phase A's rows downwards.  pair_refusal: why the module / the arguments do
+// not qualify, NULL if they do; launch_sweep_pair returns false (nothing launched) in exactly those cases.
+struct PairKnobs {
+  int rows, zc, prefetch, xcd_log2, march;
+};
 const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                         int rows, int zc, int prefetch, int xcd_log2, int march);
+                         const PairKnobs& k);
 bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                       int rows, int zc, int prefetch, int xcd_log2, int march, hipStream_t s, hipError_t* err);
+                       const PairKnobs& k, hipStream_t s, hipError_t* err);
 int pair_default_rows(const Geometry& g);
 int pair_default_zchunk(const Geometry& g);
 int pair_default_prefetch();

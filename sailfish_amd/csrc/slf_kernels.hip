@@ -198,11 +198,11 @@ hipError_t launch_box(const KernelSelector& sel, const Geometry& g, bool collect
 // ---------------------------------------------------------------------------
 
 template <class L, class R>
-static hipError_t launch_sweep2(LR<L, R>, const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                                const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+static hipError_t launch_sweep2(LR<L, R>, const Launch& lc, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, module_block_x, s] = lc;
   const SweepParams<L, R> p = make_params<L, R>(g, ph, a, y0, z0);
   const SweepVariant v = per_node_variant_of(sel, g, ph, prop);
-  if (block_x > sweep_max_threads(v)) block_x = sweep_max_threads(v);      // the instantiation's launch bound
+  const int block_x = module_block_x > sweep_max_threads(v) ? sweep_max_threads(v) : module_block_x;      // the instantiation's launch bound
   dim3 block(block_x, 1, 1);
   dim3 grid((g.lat_nx - 2 + block_x - 1) / block_x, y1 - y0, L::dim == 3 ? z1 - z0 : 1);
   if (grid.y == 0 || grid.z == 0) return hipSuccess;
@@ -232,16 +232,13 @@ static hipError_t launch_sweep2(LR<L, R>, const KernelSelector& sel, Prop prop, 
   return e;
 }
 
-hipError_t launch_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                        const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
-  if (!g.indirect) {   // the tuned kernels address the dense layout
+hipError_t launch_sweep(const Launch& lc, const SweepArgs& a) {
+  if (!lc.g.indirect) {   // the tuned kernels address the dense layout
     hipError_t fe = hipSuccess;
-    if (launch_sweep_fast(sel, prop, g, ph, a, y0, y1, z0, z1, block_x, s, &fe)) return fe;
-    if (launch_sweep_row(sel, prop, g, ph, a, y0, y1, z0, z1, s, &fe)) return fe;
+    if (launch_sweep_fast(lc.sel, lc.prop, lc.g, lc.ph, a, lc.y0, lc.y1, lc.z0, lc.z1, lc.block_x, lc.s, &fe)) return fe;
+    if (launch_sweep_row(lc.sel, lc.prop, lc.g, lc.ph, a, lc.y0, lc.y1, lc.z0, lc.z1, lc.s, &fe)) return fe;
   }
-  return pick_lr(sel, [&](auto lr) {
-    return launch_sweep2(lr, sel, prop, g, ph, a, y0, y1, z0, z1, block_x, s);
-  });
+  return pick_lr(lc.sel, [&](auto lr) { return launch_sweep2(lr, lc, a); });
 }
 
 hipError_t launch_init(const KernelSelector& sel, const Geometry& g, const Physics& ph, void* dist, const void* rho,
@@ -282,9 +279,8 @@ hipError_t launch_sparse(const KernelSelector& sel, bool collect, const unsigned
   });
 }
 
-hipError_t launch_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                        const SweepArgs& a, hipStream_t s) {
-  return pick_lr(sel, [&](auto lr) { return launch_macro2(lr, prop, sel.general, g, ph, a, s); });
+hipError_t launch_macro(const Launch& lc, const SweepArgs& a) {
+  return pick_lr(lc.sel, [&](auto lr) { return launch_macro2(lr, lc.prop, lc.sel.general, lc.g, lc.ph, a, lc.s); });
 }
 
 }  // namespace slf

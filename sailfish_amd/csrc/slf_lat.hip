@@ -81,8 +81,8 @@ static hipError_t pick_lat(const KernelSelector& sel, F&& f) {
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_lat_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                            int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+hipError_t launch_lat_sweep(const Launch& lc, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
   if (sel.model != SLF_BGK || g.indirect) return hipErrorInvalidValue;      // (refused at module creation)
   return pick_lat(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
@@ -114,12 +114,11 @@ hipError_t launch_lat_pbc(const KernelSelector& sel, const Geometry& g, void* di
   return pick_lat(sel, [&](auto lr) { return launch_pbc2(lr, g, dist, axis, with_swap, s); });
 }
 
-hipError_t launch_lat_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                            hipStream_t s) {
-  return pick_lat(sel, [&](auto lr) {
+hipError_t launch_lat_macro(const Launch& lc, const SweepArgs& a) {
+  return pick_lat(lc.sel, [&](auto lr) {
     SweepArgs b = a;
     b.nodes = nullptr;
-    return launch_macro2(lr, prop, sel.general, g, ph, b, s);
+    return launch_macro2(lr, lc.prop, lc.sel.general, lc.g, lc.ph, b, lc.s);
   });
 }
 

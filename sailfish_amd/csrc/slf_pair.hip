@@ -306,7 +306,8 @@ int pair_xcd_shift(int strips, int limit) {
 }
 
 const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                         int rows, int zc, int prefetch, int xcd_log2, int march) {
+                         const PairKnobs& k) {
+  const auto [rows, zc, prefetch, xcd_log2, march] = k;
   if (sel.lattice != 1 || sel.precision != 4 || sel.model != 0) return "pair sweep: D3Q19, single precision, BGK modules only";
   if (!two_copy) return "pair sweep: the two-copy (AB) access pattern only";
   if (sel.general || a.map) return "pair sweep: modules without a node map only";
@@ -331,11 +332,11 @@ const char* pair_refusal(const KernelSelector& sel, bool two_copy, const Geometr
 }
 
 bool launch_sweep_pair(const KernelSelector& sel, bool two_copy, const Geometry& g, const Physics& ph, const SweepArgs& a,
-                       int rows, int zc, int prefetch, int xcd_log2, int march, hipStream_t s, hipError_t* err) {
-  if (pair_refusal(sel, two_copy, g, ph, a, rows, zc, prefetch, xcd_log2, march)) return false;
+                       const PairKnobs& k, hipStream_t s, hipError_t* err) {
+  if (pair_refusal(sel, two_copy, g, ph, a, k)) return false;
   const SweepParams<D3Q19, float> p = make_params<D3Q19, float>(g, ph, a, 1, 1);
   const int nx = g.lat_nx - 2, ny = g.lat_ny - 2, nz = g.lat_nz - 2;
-  if (zc > nz) zc = nz;
+  const int rows = k.rows, prefetch = k.prefetch, xcd_log2 = k.xcd_log2, march = k.march, zc = k.zc > nz ? nz : k.zc;
   dim3 block(nx, 1, 1);
   dim3 grid(1, ny / rows, (nz + zc - 1) / zc);
   // grid.x = 1: the flat index of a workgroup modulo 8 is blockIdx.y % 8 in every chunk where 8 divides the strip count,

@@ -268,21 +268,7 @@ __global__ void __launch_bounds__(1024) resident_kernel(const ResidentParams<L, 
   }
 }
 
-// How far what is wrong has spread from the window's ring after `steps` steps from iteration it0 (see the header):
-// the halo the tile needs.
-int resident_halo(bool aa, int it0, int steps) {
-  if (!aa) return steps + 1;
-  int odd = 0;
-  for (int s = 0; s < steps; s++) odd += (it0 + s) & 1;
-  return odd ? 2 * odd : 1;
-}
-
-size_t resident_lds_bytes(int q, int precision, bool aa, int win_x, int win_y) {
-  (void)aa;      // in place: the array and the staging block of the odd steps; two-copy: copy A and copy B
-  const size_t nw = (size_t)win_x * (size_t)win_y;
-  return nw * (size_t)q * (size_t)precision * 2 + nw * 8;
-}
-
+// (resident_halo(), resident_lds_bytes(): slf_kernels.h, beside the argument check that reads them)
 template <class L, class R>
 static hipError_t launch_resident2(const KernelSelector& sel, bool aa, const Geometry& g, const Physics& ph, const SweepArgs& a,
                                    const void* const src[2], void* const dst[2], int it0, int steps, int tile_x, int tile_y,

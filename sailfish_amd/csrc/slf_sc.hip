@@ -716,8 +716,9 @@ static inline bool sc_row_pull_ok(const Geometry& g) {
 }
 
 template <class L, class R>
-static hipError_t sc_macro2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
-                            const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s) {
+static hipError_t sc_macro2(LR<L, R>, const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
+  const bool general = sel.general;
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
   const NNShape sh = nn_shape<L>(g, false, prop, y0, y1, z0, z1, nn_pass_block_x(g.lat_nx - 2));
   if (sh.empty) return hipSuccess;
@@ -755,9 +756,9 @@ static hipError_t sc_macro2(LR<L, R>, Prop prop, bool general, const Geometry& g
 }
 
 template <class L, class R>
-static hipError_t sc_sweep2(LR<L, R>, int grid_idx, Prop prop, bool general, const Geometry& g, const Physics& ph,
-                            const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                            hipStream_t s) {
+static hipError_t sc_sweep2(LR<L, R>, const Launch& lc, const ShanChen& sc, const SweepArgs& a, int grid_idx) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
+  const bool general = sel.general;
   if (sc_xface_in_use(a)) return hipErrorInvalidValue;       // planes: the fused sweep only
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, grid_idx, y0, z0);
   const NNShape sh = nn_shape<L>(g, sc_rows_on(g) && !g.indirect, prop, y0, y1, z0, z1, block_x);
@@ -779,22 +780,18 @@ static hipError_t sc_sweep2(LR<L, R>, int grid_idx, Prop prop, bool general, con
   return e;
 }
 
-hipError_t launch_sc_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                           const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, hipStream_t s) {
-  return pick_lr(sel, [&](auto lr) { return sc_macro2(lr, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, s); });
+hipError_t launch_sc_macro(const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  return pick_lr(lc.sel, [&](auto lr) { return sc_macro2(lr, lc, sc, a); });
 }
 
-hipError_t launch_sc_sweep(const KernelSelector& sel, int grid_idx, Prop prop, const Geometry& g, const Physics& ph,
-                           const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                           hipStream_t s) {
-  return pick_lr(sel, [&](auto lr) {
-    return sc_sweep2(lr, grid_idx, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
-  });
+hipError_t launch_sc_sweep(const Launch& lc, const ShanChen& sc, const SweepArgs& a, int grid_idx) {
+  return pick_lr(lc.sel, [&](auto lr) { return sc_sweep2(lr, lc, sc, a, grid_idx); });
 }
 
 template <class L, class R>
-static hipError_t sc_fused2(LR<L, R>, Prop prop, bool general, const Geometry& g, const Physics& ph, const ShanChen& sc,
-                            const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+static hipError_t sc_fused2(LR<L, R>, const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
+  const bool general = sel.general;
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
   const NNShape sh = nn_shape<L>(g, sc_rows_on(g), prop, y0, y1, z0, z1, block_x);
   if (sh.empty) return hipSuccess;
@@ -827,15 +824,14 @@ static hipError_t sc_fused2(LR<L, R>, Prop prop, bool general, const Geometry& g
   return e;
 }
 
-hipError_t launch_sc_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen& sc,
-                           const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
-  return pick_lr(sel, [&](auto lr) { return sc_fused2(lr, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s); });
+hipError_t launch_sc_fused(const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  return pick_lr(lc.sel, [&](auto lr) { return sc_fused2(lr, lc, sc, a); });
 }
 
 template <class L, class R>
-static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, const Geometry& g, const Physics& ph,
-                              const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                              hipStream_t s) {
+static hipError_t scs_launch2(LR<L, R>, bool macro, const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
+  const bool general = sel.general;
   ScParams<L, R> p = make_sc<L, R>(g, ph, sc, a, 0, y0, z0);
   p.G[0] = (R)sc.G[0];
   p.G[1] = (R)0;
@@ -886,21 +882,15 @@ static hipError_t scs_launch2(LR<L, R>, bool macro, Prop prop, bool general, con
   return e;
 }
 
-hipError_t launch_scs_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen& sc, const SweepArgs& a, hipStream_t s) {
-  const int z0 = g.dim == 3 ? 1 : 0, z1 = g.dim == 3 ? g.lat_nz - 1 : 1;
-  const int bx = nn_pass_block_x(g.lat_nx - 2);
-  return pick_lr(sel, [&](auto lr) {
-    return scs_launch2(lr, true, prop, sel.general, g, ph, sc, a, 1, g.lat_ny - 1, z0, z1, bx, s);
-  });
+hipError_t launch_scs_macro(const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  const Geometry& g = lc.g;      // every real node, in blocks of the pass's own width
+  const Launch all{lc.sel, lc.prop, g, lc.ph, 1, g.lat_ny - 1, g.dim == 3 ? 1 : 0, g.dim == 3 ? g.lat_nz - 1 : 1,
+                   nn_pass_block_x(g.lat_nx - 2), lc.s};
+  return pick_lr(lc.sel, [&](auto lr) { return scs_launch2(lr, true, all, sc, a); });
 }
 
-hipError_t launch_scs_sweep(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen& sc, const SweepArgs& a, int y0, int y1, int z0, int z1, int block_x,
-                            hipStream_t s) {
-  return pick_lr(sel, [&](auto lr) {
-    return scs_launch2(lr, false, prop, sel.general, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
-  });
+hipError_t launch_scs_sweep(const Launch& lc, const ShanChen& sc, const SweepArgs& a) {
+  return pick_lr(lc.sel, [&](auto lr) { return scs_launch2(lr, false, lc, sc, a); });
 }
 
 template <class L, class R>

@@ -252,8 +252,8 @@ static Sc3Params<R> make_sc3(const Geometry& g, const Physics& ph, const ShanChe
   return p;
 }
 
-hipError_t launch_sc3_macro(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
-                            const Sc3Args& a, int y0, int y1, int z0, int z1, hipStream_t s) {
+hipError_t launch_sc3_macro(const Launch& lc, const ShanChen3& sc, const Sc3Args& a) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
   return pick_lr(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;
@@ -268,8 +268,8 @@ hipError_t launch_sc3_macro(const KernelSelector& sel, Prop prop, const Geometry
 }
 
 // which: 0 .. 2 the sweep of that lattice (a.dist_in[0] -> a.dist_out[0]), 3 the fused sweep of all of them
-static hipError_t sc3_sweep(const KernelSelector& sel, int which, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen3& sc, const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+static hipError_t sc3_sweep(const Launch& lc, const ShanChen3& sc, const Sc3Args& a, int which) {
+  const auto& [sel, prop, g, ph, y0, y1, z0, z1, block_x, s] = lc;
   return pick_lr(sel, [&](auto lr) {
     using L = typename decltype(lr)::L;
     using R = typename decltype(lr)::R;
@@ -298,16 +298,12 @@ static hipError_t sc3_sweep(const KernelSelector& sel, int which, Prop prop, con
   });
 }
 
-hipError_t launch_sc3_sweep(const KernelSelector& sel, int lattice, Prop prop, const Geometry& g, const Physics& ph,
-                            const ShanChen3& sc, const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
+hipError_t launch_sc3_sweep(const Launch& lc, const ShanChen3& sc, const Sc3Args& a, int lattice) {
   if (lattice < 0 || lattice > 2) return hipErrorInvalidValue;
-  return sc3_sweep(sel, lattice, prop, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
+  return sc3_sweep(lc, sc, a, lattice);
 }
 
-hipError_t launch_sc3_fused(const KernelSelector& sel, Prop prop, const Geometry& g, const Physics& ph, const ShanChen3& sc,
-                            const Sc3Args& a, int y0, int y1, int z0, int z1, int block_x, hipStream_t s) {
-  return sc3_sweep(sel, 3, prop, g, ph, sc, a, y0, y1, z0, z1, block_x, s);
-}
+hipError_t launch_sc3_fused(const Launch& lc, const ShanChen3& sc, const Sc3Args& a) { return sc3_sweep(lc, sc, a, 3); }
 
 hipError_t launch_sc3_init(const KernelSelector& sel, const Geometry& g, void* const dist[3], const void* const field[3],
                            const void* const v[3], hipStream_t s) {

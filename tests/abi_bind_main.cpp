@@ -1,7 +1,7 @@
 // Walks the host logic of the C ABI (sailfish_amd/csrc/slf_bind.h) on the CPU and prints one line per case:
 //   section \t subject \t configuration \t try \t code \t message \t detail
 // tests/test_abi_bind.py builds it with AddressSanitizer and UBSan, runs it and compares the lines with
-// tests/golden/abi_binding.json and tests/golden/abi_support.tsv.  Nothing here touches a GPU.
+// tests/golden/abi_binding.json, tests/golden/abi_support.tsv and tests/golden/abi_launch.tsv.  Nothing here touches a GPU.
 #include <stdio.h>
 
 #include <string>
@@ -408,6 +408,327 @@ void face_boxes(const slf::ModuleConfig& c2, const slf::ModuleConfig& c3) {
   }
 }
 
+// ---- launch-time checks and the setters' argument checks (slf_bind.h part (f)) ---------------------------------------------
+struct Answer {
+  int code;
+  std::string message, detail;
+};
+
+// what the launch would hand to launch_box
+std::string dump_box(bool collect, const int* dirs, int nd, unsigned long long base, long long col_stride, int ncols, long long row_stride,
+                     int nrows, long long buf_k_stride, long long buf_row_stride, bool deliver_all) {
+  return "collect=" + num(collect) + " dirs=" + list(dirs, nd) + " base=" + std::to_string(base) + " col_stride=" + std::to_string(col_stride) +
+         " ncols=" + num(ncols) + " row_stride=" + std::to_string(row_stride) + " nrows=" + num(nrows) + " buf_strides=" +
+         std::to_string(buf_k_stride) + "," + std::to_string(buf_row_stride) + " deliver_all=" + num(deliver_all);
+}
+
+// the kinds whose launch takes a propagation step and rows (this program's own list, not the table's column)
+bool takes_rows(slf::KernelKind kk) {
+  switch (kk) {
+    case slf::KK_COLLIDE_AND_PROPAGATE: case slf::KK_COMPUTE_MACRO: case slf::KK_SC_MACRO: case slf::KK_SC_SWEEP0: case slf::KK_SC_SWEEP1:
+    case slf::KK_SC_FUSED: case slf::KK_SCS_MACRO: case slf::KK_SCS_SWEEP: case slf::KK_FE_MACRO: case slf::KK_FE_FLUID: case slf::KK_FE_ORDER:
+    case slf::KK_SC3_MACRO: case slf::KK_SC3_SWEEP0: case slf::KK_SC3_SWEEP1: case slf::KK_SC3_SWEEP2: case slf::KK_SC3_FUSED: return true;
+    default: return false;
+  }
+}
+bool whole_box_kind(slf::KernelKind kk) { return kk == slf::KK_COMPUTE_MACRO || kk == slf::KK_SCS_MACRO; }
+
+// ---- the functions under test, each answering with (code, message, what the launch would use) ----
+struct State {
+  int needs_iteration;
+  uint32_t iteration;
+  bool has_field, pair_armed;
+};
+
+Answer launch_answer(const slf::ModuleConfig& c, const slf::KernelRow& row, const slf::BoundArgs& b, const State& st, const slf_region* region) {
+  slf::LaunchShape sh = {};
+  slf::FaceBox box = {};
+  std::string err;
+  const slf::LaunchState state = {st.needs_iteration, st.iteration, st.has_field, st.pair_armed};
+  const int rc = slf::launch_check(c, row, b, state, region, &sh, &box, &err);
+  if (rc) return {rc, err, ""};
+  const slf::KernelKind kk = row.kind;
+  if (st.pair_armed && (kk == slf::KK_COLLIDE_AND_PROPAGATE || kk == slf::KK_COMPUTE_MACRO)) return {0, "", "pair"};
+  if (takes_rows(kk)) return {0, "", "prop=" + num(sh.prop) + " rows=" + num(sh.y0) + "," + num(sh.y1) + "," + num(sh.z0) + "," + num(sh.z1)};
+  if (slf::is_box_kind(kk) || slf::is_face_kind(kk))
+    return {0, "", dump_box(box.collect, box.dirs, box.nd, box.base, box.col_stride, box.ncols, box.row_stride, box.nrows, box.buf_k_stride,
+                            box.buf_row_stride, box.macro)};
+  return {0, "", ""};
+}
+Answer resident_answer(const slf::ModuleConfig& c, const slf::BoundArgs& b, int needs_iteration) {
+  std::string err;
+  const int rc = slf::resident_check(c, b, needs_iteration, &err);
+  return {rc, err, ""};
+}
+Answer xface_buffers_answer(const slf::ModuleConfig* c, const void* const xf[4]) {
+  std::string err;
+  const int rc = slf::xface_buffers_check(c, xf, &err);
+  return {rc, err, ""};
+}
+Answer xface_planes_answer(const slf::ModuleConfig* c, int which, const void* const xf[4]) {
+  std::string err;
+  const int rc = slf::xface_planes_check(c, which, xf, &err);
+  return {rc, err, ""};
+}
+// ---- end of the functions under test ----
+
+// the arguments `fmt` binds: pointer i is 0x1000 * (i + 1), integer i is 100 + i
+int bind_call(const slf::ModuleConfig& c, const slf::KernelRow& row, const std::string& fmt, slf::BoundArgs* bound) {
+  std::vector<unsigned long long> pv(fmt.size() + 1);
+  std::vector<int32_t> iv(fmt.size() + 1);
+  std::vector<const void*> argv(fmt.size() + 1);
+  for (size_t i = 0; i < fmt.size(); i++) {
+    pv[i] = 0x1000ull * (i + 1);
+    iv[i] = 100 + (int)i;
+    argv[i] = fmt[i] == 'i' ? (const void*)&iv[i] : (const void*)&pv[i];
+  }
+  std::string err;
+  return slf::bind(c, row, fmt.c_str(), argv.data(), (int)fmt.size(), bound, &err);
+}
+
+void launch_sections(const std::vector<Config>& configs) {
+  // the modules: a 2-D and a 3-D one of every family, both access patterns and both addressings among them (the collision
+  // model is nothing a launch asks about), then those the launch rules single out
+  std::vector<Config> mods;
+  for (const char* name : {"bgk-d2q9-ab-direct", "bgk-d2q9-aa-direct", "bgk-d3q19-ab-direct", "bgk-d3q19-aa-direct", "bgk-d3q19-ab-indirect",
+                           "sc2-d2q9-ab-direct", "sc2-d3q19-aa-direct", "sc2-d3q19-ab-indirect", "scs-d2q9-aa-direct", "scs-d3q19-ab-direct", "scs-d3q19-aa-indirect",
+                           "fe-d2q9-aa-direct", "fe-d3q19-ab-direct", "sc3-d2q9-ab-direct", "sc3-d3q19-aa-direct"})
+    for (const Config& cc : configs)
+      if (cc.name == name && !cc.code) mods.push_back(cc);
+  auto add = [&mods](const std::string& name, slf_module_desc d) {
+    Config c{name, d, {}, 0};
+    const char* err = "";
+    c.code = slf::module_config(&c.desc, &c.cfg, &err);
+    if (c.code) line("launch", "-", name, "module", c.code, err, "");
+    else mods.push_back(c);
+  };
+  const int DIR = SLF_ADDR_DIRECT;
+  slf_module_desc d = base_desc(SLF_D2Q9, SLF_AB, SLF_SIM_LBM, SLF_BGK, DIR);
+  d.accel_field = 1; add("accf-d2q9-ab-direct", d);
+  d = base_desc(SLF_D3Q19, SLF_AA, SLF_SIM_LBM, SLF_BGK, DIR);
+  d.accel_field = 1; add("accf-d3q19-aa-direct", d);
+  add("d3q15-ab-direct", base_desc(SLF_D3Q15, SLF_AB, SLF_SIM_LBM, SLF_BGK, DIR));
+  struct Fam { const char* name; int simtype; };
+  for (const Fam& f : {Fam{"bgk", SLF_SIM_LBM}, Fam{"sc3", SLF_SIM_SHAN_CHEN_TERNARY}}) {      // the two map rules
+    d = base_desc(SLF_D3Q19, SLF_AB, f.simtype, SLF_BGK, DIR);
+    d.fluid_only = 1; d.n_types = 0;
+    add(std::string(f.name) + "-d3q19-ab-fluid-only", d);
+  }
+
+  std::vector<std::string> names;
+  for (const slf::KernelRow& r : slf::KERNEL_TABLE) {
+    bool seen = false;
+    for (const std::string& n : names) seen = seen || n == r.name;
+    if (!seen) names.push_back(r.name);
+  }
+  for (const Config& cc : mods) {
+    const slf::ModuleConfig& c = cc.cfg;
+    const slf::Geometry& g = c.geo;
+    const bool d3 = g.dim == 3, aa = c.access_pattern == SLF_AA;
+    const bool halo = cc.name == "bgk-d3q19-aa-direct" || cc.name == "bgk-d2q9-ab-direct";      // the modules that show the halo kinds
+    for (const std::string& name : names) {
+      const slf::KernelRow* row = nullptr;
+      std::string err;
+      if (slf::resolve(c, name.c_str(), &row, &err)) continue;
+      const slf::KernelKind kk = row->kind;
+      if (kk == slf::KK_RESIDENT) continue;      // its launch asks for the map alone: the `resident` section
+      if (row->families == slf::F_ALL && !halo) continue;
+      // the region at each edge: one sweep per family, in a module with direct addressing
+      const bool edges = !g.indirect && c.sel.general && !c.phys.accel_field &&
+                         (kk == slf::KK_COLLIDE_AND_PROPAGATE || kk == slf::KK_SC_SWEEP1 || kk == slf::KK_SCS_SWEEP || kk == slf::KK_FE_ORDER || kk == slf::KK_SC3_FUSED);
+      const slf::KernelRow* sig = signature_of(name.c_str(), kk);
+      slf::BoundArgs bound = {};
+      if (bind_call(c, *row, calls_for(c, *sig)[0].second.fmt, &bound)) continue;      // (indirect addressing has no fused binary sweep)
+      if (slf::is_face_kind(kk) || slf::is_box_kind(kk)) {      // a face the module has
+        const bool macro = kk == slf::KK_COLLECT_MACRO_FACE || kk == slf::KK_DISTRIBUTE_MACRO_FACE;
+        const long long f3[5] = {2, 1, 1, 4, macro ? 2 : 10}, f2[5] = {2, 1, 10, 0, 0}, m2[5] = {1, 4, 2, 0, 0};
+        if (slf::is_face_kind(kk))
+          for (int i = 0; i < 5; i++) bound.ints[i] = d3 ? f3[i] : (macro ? m2[i] : f2[i]);
+      }
+      struct Try {
+        std::string name;
+        slf::BoundArgs b;
+        State st;
+        bool has_region;
+        slf_region region;
+      };
+      const State plain = {1, 0, true, false};
+      const slf_region inner = {2, 3, 2, 3};
+      std::vector<Try> tries;
+      tries.push_back({"no-region", bound, plain, false, inner});
+      if (whole_box_kind(kk) || (!takes_rows(kk) && halo)) tries.push_back({"region-out-of-range", bound, plain, true, {-5, 400, -7, 900}});
+      if (edges) {
+        tries.push_back({"inner-region", bound, plain, true, inner});
+        tries.push_back({"y0-0", bound, plain, true, {0, 3, 1, 2}});
+        tries.push_back({"y1-lat-ny", bound, plain, true, {1, g.lat_ny, 1, 2}});
+        tries.push_back({"y0-above-y1", bound, plain, true, {3, 2, 1, 2}});
+        tries.push_back({"y0-equals-y1", bound, plain, true, {2, 2, 1, 2}});
+        tries.push_back({"all-rows", bound, plain, true, {1, g.lat_ny - 1, 1, d3 ? g.lat_nz - 1 : 1}});
+        tries.push_back({"z-far-out", bound, plain, true, {1, 2, -40, 900}});         // (2-D: z is not read)
+        if (d3) {
+          tries.push_back({"z0-0", bound, plain, true, {1, 2, 0, 2}});
+          tries.push_back({"z1-lat-nz", bound, plain, true, {1, 2, 1, g.lat_nz}});
+          tries.push_back({"z0-above-z1", bound, plain, true, {1, 2, 3, 2}});
+          tries.push_back({"z0-equals-z1", bound, plain, true, {1, 2, 2, 2}});
+        }
+      }
+      if (aa) tries.push_back({"no-iteration", bound, {0, 7, true, false}, false, inner});
+      if (aa && takes_rows(kk)) {
+        tries.push_back({"iteration-odd", bound, {1, 7, true, false}, false, inner});
+        tries.push_back({"iteration-even", bound, {1, 8, true, false}, !whole_box_kind(kk), inner});
+      }
+      if (aa && edges) tries.push_back({"no-iteration-region-out", bound, {0, 0, true, false}, true, {0, 900, 0, 900}});
+      slf::BoundArgs nomap = bound, nonodes = bound, neither = bound;
+      nomap.sweep.map = nomap.sc3.map = nullptr;
+      nonodes.sweep.nodes = nullptr;
+      neither.sweep.map = neither.sc3.map = neither.sweep.nodes = nullptr;
+      tries.push_back({"null-map", nomap, plain, false, inner});
+      if (edges) tries.push_back({"null-map-region-out", nomap, plain, true, {0, 900, 0, 900}});
+      if (aa && edges) tries.push_back({"null-map-no-iteration", nomap, {0, 0, true, false}, false, inner});
+      if (g.indirect) {
+        tries.push_back({"null-nodes", nonodes, plain, false, inner});
+        tries.push_back({"null-nodes-null-map", neither, plain, false, inner});
+        tries.push_back({"null-nodes-region-out", nonodes, plain, true, {0, 900, 0, 900}});
+      }
+      if (c.phys.accel_field) {
+        tries.push_back({"no-field", bound, {1, 0, false, false}, false, inner});
+        tries.push_back({"no-field-null-map", nomap, {1, 0, false, false}, false, inner});
+        tries.push_back({"no-field-region-out", bound, {1, 0, false, false}, true, {0, 900, 0, 900}});
+      }
+      if (cc.name == "bgk-d3q19-ab-direct" || cc.name == "bgk-d3q19-ab-fluid-only") {      // (only CollideAndPropagate kernels are ever armed)
+        tries.push_back({"pair-armed", bound, {1, 0, true, true}, false, inner});
+        tries.push_back({"pair-armed-region", bound, {1, 0, true, true}, true, inner});
+        tries.push_back({"pair-armed-region-null-map-no-field", nomap, {0, 0, false, true}, true, {0, 900, 0, 900}});
+        tries.push_back({"pair-armed-null-map-no-field", nomap, {0, 0, false, true}, false, inner});
+      }
+      if (slf::is_box_kind(kk)) {
+        for (const char* fmt : {"PPiiiiii", "PPiiiiiiii"}) {
+          slf::BoundArgs bx = {};
+          if (bind_call(c, *row, fmt, &bx)) continue;
+          const std::string form = std::string(fmt).size() == 8 ? "box-6-ints" : "box-8-ints";
+          for (long long mask : {0ll, 0xFFFll, 0x1FFFll, 0xFFF00000ll, (long long)(int32_t)0x80000000u, -1ll}) {
+            bx.ints[0] = mask;
+            char hex[32];
+            snprintf(hex, sizeof hex, "%llx", (unsigned long long)mask & 0xFFFFFFFFull);
+            tries.push_back({form + "-mask-" + hex, bx, plain, false, inner});
+          }
+          bx.ints[0] = 0x1FFF; bx.ints[1] = -1;
+          tries.push_back({form + "-13-dirs-negative-base", bx, plain, false, inner});
+        }
+        slf::BoundArgs ref = {};
+        if (!bind_call(c, *row, d3 ? "PiiiiiP" : "PiiiP", &ref)) {
+          const long long f3[5] = {3, 1, 1, 4, 10}, f2[5] = {3, 1, 10, 0, 0};
+          for (int i = 0; i < 5; i++) ref.ints[i] = d3 ? f3[i] : f2[i];
+          tries.push_back({"reference-form", ref, plain, false, inner});
+          ref.ints[0] = 1;
+          tries.push_back({"reference-form-x-face", ref, plain, false, inner});
+          ref.ints[0] = 2; ref.ints[1] = 7;
+          tries.push_back({"reference-form-outside", ref, plain, true, inner});
+        }
+      }
+      if (slf::is_face_kind(kk)) {
+        slf::BoundArgs bad = bound;
+        bad.ints[d3 ? 1 : 0] = 7;
+        tries.push_back({"face-outside", bad, plain, false, inner});
+        bad = bound;
+        bad.ints[d3 ? 4 : (kk == slf::KK_COLLECT_MACRO_FACE || kk == slf::KK_DISTRIBUTE_MACRO_FACE ? 1 : 2)] = 7;
+        tries.push_back({"face-count-7", bad, plain, false, inner});
+      }
+      for (const Try& t : tries) {
+        const Answer a = launch_answer(c, *row, t.b, t.st, t.has_region ? &t.region : nullptr);
+        line("launch", name, cc.name, t.name, a.code, a.message, a.detail);
+      }
+    }
+  }
+
+  // CollideAndPropagateResident: the arguments at bind time (one line per return of the check) and the map at launch time
+  for (const Config& cc : mods) {
+    const slf::ModuleConfig& c = cc.cfg;
+    const slf::KernelRow* row = nullptr;
+    std::string err;
+    if (slf::resolve(c, "CollideAndPropagateResident", &row, &err)) continue;
+    slf::BoundArgs bound = {};
+    if (bind_call(c, *row, "PPPPPiiiii", &bound)) continue;
+    struct Try { std::string name; long long steps, tx, ty, halo; int needs_iteration; int change; };
+    const Try tries[] = {
+      {"fits", 2, 16, 8, 4, 1, 0}, {"no-iteration", 2, 16, 8, 4, 0, 0}, {"steps-0", 0, 16, 8, 4, 1, 0}, {"tile-x-0", 2, 0, 8, 4, 1, 0},
+      {"tile-y-negative", 2, 16, -8, 4, 1, 0}, {"halo-0", 2, 16, 8, 0, 1, 0}, {"no-source", 2, 16, 8, 4, 1, 1}, {"no-destination", 2, 16, 8, 4, 1, 2},
+      {"no-source-b", 2, 16, 8, 4, 1, 3}, {"no-destination-b", 2, 16, 8, 4, 1, 4}, {"same-buffer", 2, 16, 8, 4, 1, 5}, {"same-buffer-b", 2, 16, 8, 4, 1, 6},
+      {"halo-1-steps-1", 1, 16, 8, 1, 1, 0}, {"halo-2-steps-1", 1, 16, 8, 2, 1, 0}, {"halo-2-steps-2", 2, 16, 8, 2, 1, 0}, {"halo-3-steps-2", 2, 16, 8, 3, 1, 0},
+      {"halo-3-steps-4", 4, 16, 8, 3, 1, 0}, {"halo-4-steps-4", 4, 16, 8, 4, 1, 0}, {"halo-5-steps-4", 4, 16, 8, 5, 1, 0},
+      {"window-2048", 1, 60, 28, 2, 1, 0}, {"window-2112", 1, 62, 28, 2, 1, 0}, {"window-46x44", 1, 42, 40, 2, 1, 0}, {"window-huge", 1, 1 << 30, 1 << 30, 2, 1, 0},
+      {"no-iteration-steps-0-no-source", 0, 16, 8, 4, 0, 1}, {"steps-0-no-source", 0, 16, 8, 4, 1, 1}, {"no-source-halo-small", 4, 16, 8, 1, 1, 1},
+      {"same-buffer-halo-small", 4, 16, 8, 1, 1, 5}, {"halo-small-window-large", 40, 60, 60, 2, 1, 0},
+    };
+    for (const Try& t : tries) {
+      slf::BoundArgs b = bound;
+      b.ints[1] = t.steps; b.ints[2] = t.tx; b.ints[3] = t.ty; b.ints[4] = t.halo;
+      if (t.change == 1) b.sweep.dist_in = nullptr;
+      if (t.change == 2) b.sweep.dist_out = nullptr;
+      if (t.change == 3) b.sweep.dist_in2 = nullptr;
+      if (t.change == 4) b.sweep.dist_out2 = nullptr;
+      if (t.change == 5) b.sweep.dist_out = b.sweep.dist_in;
+      if (t.change == 6) b.sweep.dist_out2 = b.sweep.dist_in2;
+      const Answer a = resident_answer(c, b, t.needs_iteration);
+      line("resident", "args", cc.name, t.name, a.code, a.message, a.detail);
+    }
+    slf::BoundArgs nomap = bound;
+    nomap.sweep.map = nullptr;
+    const slf_region out = {0, 900, 0, 900};
+    for (int needs_iteration : {0, 1}) {
+      const State st = {needs_iteration, 3, false, false};
+      Answer a = launch_answer(c, *row, bound, st, &out);
+      line("resident", "launch", cc.name, "iteration-flag-" + num(needs_iteration), a.code, a.message, a.detail);
+      a = launch_answer(c, *row, nomap, st, nullptr);
+      line("resident", "launch", cc.name, "null-map-iteration-flag-" + num(needs_iteration), a.code, a.message, a.detail);
+    }
+  }
+
+  // the x-face setters: buffers (single fluid) and planes (Shan-Chen), per module and per combination of the four pointers
+  for (int mi = -1; mi < (int)mods.size(); mi++) {
+    if (mi >= 0 && mods[mi].cfg.geo.dim == 2 && mods[mi].name != "sc2-d2q9-ab-direct" && mods[mi].name != "bgk-d2q9-ab-direct") continue;
+    if (mi >= 0 && (mods[mi].cfg.phys.accel_field || !mods[mi].cfg.sel.general)) continue;
+    const slf::ModuleConfig* c = mi < 0 ? nullptr : &mods[mi].cfg;
+    std::vector<std::pair<std::string, slf::ModuleConfig>> variants;
+    if (c) {
+      variants.push_back({mods[mi].name, *c});
+      if (mods[mi].name == "bgk-d3q19-ab-direct" || mods[mi].name == "scs-d3q19-ab-direct") {      // one that takes buffers, one that takes planes
+        slf::ModuleConfig v = *c;
+        v.geo.wrap[0] = 1; variants.push_back({mods[mi].name + "+x-wrapped", v});
+        v = *c; v.geo.lat_nx = 1027; variants.push_back({mods[mi].name + "+rows-1025", v});
+        v = *c; v.geo.lat_nx = 1026; variants.push_back({mods[mi].name + "+rows-1024", v});
+        v = *c; v.geo.lat_nx = 3; variants.push_back({mods[mi].name + "+rows-1", v});
+        v = *c; v.geo.lat_nx = 4; variants.push_back({mods[mi].name + "+rows-2", v});
+        v = *c; v.geo.variant &= ~8; variants.push_back({mods[mi].name + "+no-whole-rows", v});
+        v = *c; v.geo.wrap[0] = 1; v.geo.lat_nx = 1027; variants.push_back({mods[mi].name + "+wrapped-1025", v});
+      }
+    } else {
+      variants.push_back({"null-module", slf::ModuleConfig{}});
+    }
+    for (const auto& v : variants) {
+      const slf::ModuleConfig* vc = c ? &v.second : nullptr;
+      const bool base = c && v.first == mods[mi].name && !c->geo.indirect && c->geo.dim == 3 && !c->fe.enabled && !c->sc3.enabled;
+      for (int bits : {0, 1, 4, 5, 10, 15}) {
+        if (!base && bits != 5 && bits != 0) continue;      // every pointer set where they can be accepted, else nothing and one face
+        const void* xf[4];
+        std::string what;
+        for (int i = 0; i < 4; i++) {
+          xf[i] = ((bits >> i) & 1) ? (const void*)(0x1000ull * (i + 1)) : nullptr;
+          what += ((bits >> i) & 1) ? "SsRr"[i] : '-';      // S / s: send low / high, R / r: receive low / high
+        }
+        Answer a = xface_buffers_answer(vc, xf);
+        if (base || bits == 5) line("xface-buffers", "-", v.first, what, a.code, a.message, a.detail);
+        for (int which = -1; which <= 3; which++) {
+          if ((which < 0 || which > 2) && (bits != 5 || !(base || !c))) continue;      // no such set: with one face
+          if (!base && (bits == 0) != (which == 2)) continue;                         // ... set 2 with nothing, sets 0 and 1 with one face
+          a = xface_planes_answer(vc, which, xf);
+          line("xface-planes", "set" + num(which), v.first, what, a.code, a.message, a.detail);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -480,5 +801,6 @@ int main() {
     if (cc.name == "bgk-d3q19-aa-direct") c3 = &cc.cfg;
   }
   face_boxes(*c2, *c3);
+  launch_sections(configs);
   return 0;
 }
